@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- lip-sync frames/s of the MI355X frame generator (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--long 1]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, ...);
+--dump-outputs DIR also writes what the last timed step returned.  Everything else below (roofline, PMC passes, parity,
+CPU baselines, the other precision, multi-session and the secondary workloads) runs only with --full.
 
 BASELINE.json's metric is "lip-sync frames/sec @256x256": the headline workload is configs[2], the MuseTalk
 step of musereal.py:100-108 -- pe(audio) -> UNet(t=0) -> VAE.decode_latents -> uint8 256x256 BGR frames --
 on a batch of 8 latents + 8 Whisper chunks already resident in HBM (the reference's own
 "actual avg infer fps" brackets exactly this, musereal.py:99-115).  `--workload wav2lip` selects
-configs[1] instead (Wav2Lip generator 96x96, batch 16), which is also reported in the default line
+configs[1] instead (Wav2Lip generator 96x96, batch 16), which is also reported in the --full line
 under "wav2lip".  One process per GPU; sessions are independent so ranks share nothing but the barrier and the
 MAX of the elapsed time ("weak").
-Rank 0 prints ONE JSON line.  Extra objects on that line:
+Rank 0 prints ONE JSON line.  Extra objects on that line (--full):
   roofline     : the dominant HIP kernel's algorithmic TFLOP/s (HIP events around every launch,
                  mf_wav2lip_profile) against the dense MFMA peak of the arithmetic mode
   cpu_baseline : the oracle (torch fp32 restatement of the reference) timed on this box's host cores
@@ -40,6 +44,9 @@ from mere_fusion_amd.wav2lip.models import Wav2Lip  # noqa: E402
 GFLOP_PER_FRAME = 7.934          # 2 x 3.967 GMAC, the 51 conv layers
 BF16_DENSE_PEAK_TF = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
 MFMA_PASSES = {"bf16": 1, "bf16x3": 3}
+WAV2LIP_WORKLOAD = "Wav2Lip generator 96x96, batch=16 mel-chunks, inputs resident in HBM (BASELINE.json configs[1])"
+ERNERF_WORKLOAD = ("ER-NeRF frame 512x512 (nerfreal.py path): audio nets -> enc_a, torso deform / colour nets over the background, near/far + "
+                   "(march -> tri-plane field -> composite) x <= 16 steps, uint8 frame; synthetic occupancy, rays resident in HBM (BASELINE.json configs[4])")
 
 
 def cpu_model():
@@ -166,7 +173,8 @@ class MuseTalkRunner:
 
     def step(self):
         pred = self.unet.model(self.lat, self.t0, encoder_hidden_states=self.unet.pe(self.aud)).sample
-        return self.vae.decode_latents_device(pred)
+        self.last = self.vae.decode_latents_device(pred)
+        return self.last
 
     def step_d2h(self):
         """The reference's own "actual avg infer fps" bracket (musereal.py:99-115) ends after `vae.decode_latents`, whose last line copies the
@@ -555,7 +563,7 @@ def wav2lip_report(args, device, world, rank, value=None, ms_per_step=None, run=
         el = harness.timed_steps(run.step, steps, 20, sync_fn=torch.cuda.synchronize)
         value, ms_per_step = args.w2l_batch * steps / el, el / steps * 1e3
     out = {"value": round(value, 1), "unit": "frames/s", "ms_per_step": round(ms_per_step, 4), "dtype": args.precision,
-           "workload": "Wav2Lip generator 96x96, batch=16 mel-chunks, inputs resident in HBM (BASELINE.json configs[1])",
+           "workload": WAV2LIP_WORKLOAD,
            "net_tflops": round(value / world * GFLOP_PER_FRAME / 1e3, 2)}
     if args.profile_iters <= 0:            # child of a PMC pass: the timed steps are all it needs to run
         return out
@@ -641,9 +649,9 @@ def muse_multi_session(args, device):
     if getattr(args, "paced", 1):
         _stage("paced sessions")
         lean = lean_runner(args.precision, S * B, device)            # the serving rank's handles: eager, single stream (host-lean)
-        rep["paced_sessions"] = muse_paced_sessions(lean, args, device, rep["value"], full=bool(getattr(args, "full", 0)), lean=True)
+        rep["paced_sessions"] = muse_paced_sessions(lean, args, device, rep["value"], full=bool(getattr(args, "long", 0)), lean=True)
         rep["paced_sessions"]["rank_mode"] = "host-lean: handles under MF_NO_GRAPH=2 (eager launch chain, no side branches), single-stream scheduler"
-        if getattr(args, "full", 0):
+        if getattr(args, "long", 0):
             # the same search with graph-replayed handles and the copy / Whisper side streams (round 4's rank): what the host-lean mode costs in sessions
             _stage("paced sessions, graph-mode handles")
             big2 = MuseTalkRunner(args.precision, S * B, device)
@@ -893,9 +901,9 @@ def muse_paced_sessions(big, args, device, free_fps, full=True, lean=False):
     cap = max(int(free_fps / 25.0), 1)
     rig = PacedRig(big, args, device, n_max=cap + 4, lean=lean)
     try:
-        # default run: 3 s screening trials + ONE 15 s confirmation (the whole bench stays under ~4 minutes); --full 1: the 40 s confirmation, N + 1 shown failing
+        # --full run: 3 s screening trials + ONE 15 s confirmation (the whole bench stays under ~4 minutes); --full --long 1: the 40 s confirmation, N + 1 shown failing
         # over 20 s, the UNet + VAE only search and the per-stage trials (round 4's measurement, ~150 s)
-        long_ = bool(getattr(args, "full", 0))
+        long_ = bool(getattr(args, "long", 0))
         e2e, e2e_trials = rig.search(cap, ("whisper", "paste", "ring"), screen_s=4.0 if long_ else 3.0, confirm_s=40.0 if long_ else 15.0, fail_s=20.0 if long_ else 0.0)
         rep = {"criterion": f"p99 latency of a session's {B}-frame batch <= {B} x 40 ms = {P * 1e3:.0f} ms, every batch delivered, and no queue growth (mean latency of the "
                             f"last third of the batches - of the first third <= {P * 100:.0f} ms); real time, seeded random phases, one batch per session per {P * 1e3:.0f} ms",
@@ -1421,9 +1429,7 @@ def ernerf_report(args, device, world, rank, value=None, ms_per_step=None, run=N
         el = harness.timed_steps(run.step, steps, 10, sync_fn=torch.cuda.synchronize)
         value, ms_per_step = steps / el, el / steps * 1e3
     smp = run.samples_per_frame()
-    rep = {"workload": "ER-NeRF frame 512x512 (nerfreal.py path): audio nets -> enc_a, torso deform / colour nets over the background, near/far + "
-                       "(march -> tri-plane field -> composite) x <= 16 steps, uint8 frame; synthetic occupancy, rays resident in HBM "
-                       "(BASELINE.json configs[4])",
+    rep = {"workload": ERNERF_WORKLOAD,
            "value": round(value, 1), "unit": "frames/s", "ms_per_step": round(ms_per_step, 3), "dtype": args.precision,
            "samples_per_frame": int(smp), "march_iterations": len(run.trace), "loop": run.loop, "launched_rounds": run.launched_rounds(),
            "field_tflops_algorithmic": round(smp * 46368 * value / max(world, 1) / 1e12, 2)}
@@ -1638,6 +1644,67 @@ def _stage(name):
     print(f"[bench +{time.perf_counter() - _T0:6.1f} s] {name}", file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every tensor the timed path returned in its last step as out_dir/<name>.npy -- float64 where the values are 32 / 64-bit integers
+    or doubles, float32 otherwise.  Over DUMP_LIMIT_BYTES in all, each array is cut to the same fraction of its elements, a seeded (fixed) sorted sample
+    of its flattened positions, so two builds given the same arguments write comparable files."""
+    host = {}
+    for name, t in outputs.items():
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)
+        host[name] = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    if not host:
+        raise RuntimeError("--dump-outputs: the timed step returned no tensors")
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for i, name in enumerate(sorted(host)):
+            a = host[name].reshape(-1)
+            k = max(int(a.size * frac), 1)
+            idx = np.sort(np.random.default_rng(1000 + i).choice(a.size, k, replace=False))
+            host[name] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
+
+
+def muse_headline(run, value, elapsed, args, world):
+    """The MuseTalk headline's line: the contract keys, the workload, the algorithmic GFLOP per frame and what `dtype` stands for."""
+    q_on = args.precision == "bf16x3" and os.environ.get("MF_CONV_Q", "1") != "0"
+    gf_frame = run.gflop_per_frame()      # summed over the handles' own op lists (tests/test_musetalk_full.py holds it to SURVEY Appendix C)
+    line = {"metric": "lip-sync frames/sec @256x256", "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16x3+f16q" if q_on else args.precision, "data": "synthetic",
+            "config": {"workload": "MuseTalk step 256x256: pe(audio) + UNet(t=0) + VAE decode to uint8 frames, batch=8 latents + "
+                                   "Whisper chunks per GPU, inputs resident in HBM (BASELINE.json configs[2]); assumed MuseTalk-v1 / "
+                                   "sd-vae-ft-mse architecture, seeded random-init weights",
+                       "batch_per_gpu": args.batch, "sessions_at_25fps": round(value / 25.0, 1),
+                       "algorithmic_gflop_per_frame": round(gf_frame, 1),
+                       "parallelism": f"{world} independent replicas, sessions sharded by GPU, no collective"},
+            "net_tflops": round(value / world * gf_frame / 1e3, 1)}
+    if q_on:
+        line["dtype_note"] = ("bf16x3 (hi, lo bf16 pairs, three MFMAs per product) everywhere except the VAE decoder's 3x3 resnet convs and upsamplers on maps >= 32 x 32 "
+                              "(28 % of the step's time): f16 + FP6 (e2m3, MX block scales) correction terms, 1.5 pass-equivalents per product, outputs bf16 (hi, lo); "
+                              "parity bound unchanged (tests/test_musetalk_full.py)")
+    return line
+
+
+def _finish_plain(line):
+    """the plain run's result: the headline line alone, no detail file"""
+    sys.stdout.flush()
+    print(json.dumps(line), flush=True)
+
+
+# the options only a --full run acts on, with their defaults there (None on the command line = not given)
+FULL_ONLY_DEFAULTS = {"cpu_seconds": 10.0, "cpu_threads": 0, "profile_iters": 5, "sessions": 8, "paced": 1, "pmc_traffic": 1, "extras": 1, "long": 0}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1647,22 +1714,35 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="MuseTalk frames per step (configs[2]: 8)")
     ap.add_argument("--w2l-batch", type=int, default=16, help="Wav2Lip frames per step (configs[1]: 16)")
     ap.add_argument("--precision", default=os.environ.get("MF_PRECISION", "bf16x3"), choices=sorted(MFMA_PASSES))
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="0 skips the CPU baseline legs")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = cores available to this process (capped at 64)")
-    ap.add_argument("--profile-iters", type=int, default=5)
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="0 skips the CPU baseline legs")
+    ap.add_argument("--cpu-threads", type=int, default=None, help="0 = cores available to this process (capped at 64)")
+    ap.add_argument("--profile-iters", type=int, default=None)
     ap.add_argument("--dump-layers", default=None, help="write the per-launch tables (JSON) to this path")
-    ap.add_argument("--sessions", type=int, default=8, help="concurrent sessions per GPU for the multi_session legs (0 = skip)")
-    ap.add_argument("--paced", type=int, default=1, help="0 skips the real-time paced-sessions measurement of the multi_session leg")
-    ap.add_argument("--pmc-traffic", type=int, default=1, help="0 skips the two rocprofv3 PMC passes behind roofline.traffic")
-    ap.add_argument("--extras", type=int, default=1, help="0: only the headline workload (no second workload, alt mode, CPU legs)")
-    ap.add_argument("--full", type=int, default=0, help="1: the long variants of the secondary legs (40 s paced confirmation + failing N + 1, UNet + VAE only search, per-stage trials, "
-                                                        "8 ranks x 2 sessions on one GPU, the GRBM clock pass): ~6.5 min instead of ~3.5")
+    ap.add_argument("--sessions", type=int, default=None, help="concurrent sessions per GPU for the multi_session legs (0 = skip)")
+    ap.add_argument("--paced", type=int, default=None, help="0 skips the real-time paced-sessions measurement of the multi_session leg")
+    ap.add_argument("--pmc-traffic", type=int, default=None, help="0 skips the two rocprofv3 PMC passes behind roofline.traffic")
+    ap.add_argument("--extras", type=int, default=None, help="0: only the headline workload (no second workload, alt mode, CPU legs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other leg: repeats, roofline, PMC passes, parity, alt precision, CPU baselines, "
+                                                        "multi-session, the other workloads (~3.5 min); without it the run times the headline steps and nothing else")
+    ap.add_argument("--long", type=int, default=None, help="1 (with --full): the long variants of the secondary legs (40 s paced confirmation + failing N + 1, UNet + VAE only "
+                                                        "search, per-stage trials, 8 ranks x 2 sessions on one GPU, the GRBM clock pass): ~6.5 min instead of ~3.5")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--ranks-on-one-gpu", type=int, default=0, help="R > 0: ONLY the host-readiness leg -- R processes sharing GPU 0, each driving --sessions end-to-end "
-                                                                      "sessions (default 2) in real time; the default line runs it with R = 8")
+                                                                      "sessions (default 2) in real time; the --full line runs it with R = 8")
     ap.add_argument("--worker-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--worker-dir", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--worker-seconds", type=float, default=20.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full and args.ranks_on_one_gpu <= 0:
+        # a plain run times the headline and nothing else: an option that asks for a --full leg is an error, not silently ignored ("0" forms are fine)
+        asked = [name for name, v in (("--dump-layers", args.dump_layers), ("--long", args.long), ("--sessions", args.sessions), ("--paced", args.paced),
+                                      ("--profile-iters", args.profile_iters), ("--cpu-seconds", args.cpu_seconds), ("--cpu-threads", args.cpu_threads),
+                                      ("--pmc-traffic", args.pmc_traffic), ("--extras", args.extras)) if v]
+        if asked:
+            ap.error(f"{', '.join(asked)} only take effect with --full (a plain run times the headline steps and nothing else)")
+    for k, v in FULL_ONLY_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
     if args.ranks_on_one_gpu > 0:
         if not torch.cuda.is_available():
             raise SystemExit("bench.py needs an MI355X; there is no CPU path to measure")
@@ -1687,11 +1767,19 @@ def main():
     torch.cuda.set_device(local_rank)
     extras = bool(args.extras) and world == 1
 
+    plain_config = {"parallelism": f"{world} independent replicas, sessions sharded by GPU, no collective"}
     if args.workload == "ernerf":
         run = ErNeRFRunner(args.precision, 512, device, seed=rank)
         elapsed = harness.timed_steps(run.step, args.steps, args.warmup, sync_fn=torch.cuda.synchronize, device=device)
         value = harness.aggregate_value(1, args.steps, elapsed, world)
-        if rank == 0:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, run.last)
+        if rank == 0 and not args.full:
+            _finish_plain({"metric": "lip-sync frames/sec", "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                           "dtype": args.precision, "data": "synthetic",
+                           "config": dict(workload=ERNERF_WORKLOAD + "; seeded random-init field", sessions_at_25fps=round(value / 25.0, 1), **plain_config)})
+        elif rank == 0:
             if not extras:
                 args.cpu_seconds = 0
             rep = ernerf_report(args, device, world, rank, value, elapsed / args.steps * 1e3, run)
@@ -1708,7 +1796,15 @@ def main():
         run = Runner(args.precision, args.w2l_batch, device, seed=rank)
         elapsed = harness.timed_steps(run.step, args.steps, args.warmup, sync_fn=torch.cuda.synchronize, device=device)
         value = harness.aggregate_value(args.w2l_batch, args.steps, elapsed, world)
-        if rank == 0:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"pred": run.out})
+        if rank == 0 and not args.full:
+            _finish_plain({"metric": "lip-sync frames/sec", "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                           "dtype": args.precision, "data": "synthetic",
+                           "config": dict(workload=WAV2LIP_WORKLOAD + "; seeded random-init weights", batch_per_gpu=args.w2l_batch,
+                                          sessions_at_25fps=round(value / 25.0, 1), **plain_config)})
+        elif rank == 0:
             if not extras:
                 args.sessions, args.cpu_seconds = 0, 0
             rep = wav2lip_report(args, device, world, rank, value, elapsed / args.steps * 1e3, run)
@@ -1728,6 +1824,15 @@ def main():
         _stage("timed steps")
         elapsed = harness.timed_steps(run.step, args.steps, args.warmup, sync_fn=torch.cuda.synchronize, device=device)
         value = harness.aggregate_value(args.batch, args.steps, elapsed, world)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"frames": run.last})
+        if not args.full:
+            if rank == 0:
+                _finish_plain(muse_headline(run, value, elapsed, args, world))
+            if world > 1:
+                torch.distributed.barrier()
+                torch.distributed.destroy_process_group()
+            return
         repeats = None
         if world == 1 and bool(args.extras) and args.profile_iters > 0:
             # the headline's own run-to-run spread (the timed region is short: K steps of ~19 ms): five more repeats of the same K steps, with the package power
@@ -1747,26 +1852,11 @@ def main():
                 repeats["power"] = pw
         _stage("per-op profile")
         solo = world == 1
-        q_on = args.precision == "bf16x3" and os.environ.get("MF_CONV_Q", "1") != "0"
         line = None
         if rank == 0:
-            gf_frame = run.gflop_per_frame()      # summed over the handles' own op lists (tests/test_musetalk_full.py holds it to SURVEY Appendix C)
-            line = {"metric": "lip-sync frames/sec @256x256", "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
-                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-                    "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16x3+f16q" if q_on else args.precision, "data": "synthetic",
-                    "config": {"workload": "MuseTalk step 256x256: pe(audio) + UNet(t=0) + VAE decode to uint8 frames, batch=8 latents + "
-                                           "Whisper chunks per GPU, inputs resident in HBM (BASELINE.json configs[2]); assumed MuseTalk-v1 / "
-                                           "sd-vae-ft-mse architecture, seeded random-init weights",
-                               "batch_per_gpu": args.batch, "sessions_at_25fps": round(value / 25.0, 1),
-                               "algorithmic_gflop_per_frame": round(gf_frame, 1),
-                               "parallelism": f"{world} independent replicas, sessions sharded by GPU, no collective"},
-                    "net_tflops": round(value / world * gf_frame / 1e3, 1)}
+            line = muse_headline(run, value, elapsed, args, world)
             if repeats:
                 line["repeats"] = repeats
-            if q_on:
-                line["dtype_note"] = ("bf16x3 (hi, lo bf16 pairs, three MFMAs per product) everywhere except the VAE decoder's 3x3 resnet convs and upsamplers on maps >= 32 x 32 "
-                                      "(28 % of the step's time): f16 + FP6 (e2m3, MX block scales) correction terms, 1.5 pass-equivalents per product, outputs bf16 (hi, lo); "
-                                      "parity bound unchanged (tests/test_musetalk_full.py)")
             if args.profile_iters <= 0:          # child of a PMC pass: the timed steps above are all it needs to run
                 print(json.dumps(line), flush=True)
                 return
@@ -1774,7 +1864,7 @@ def main():
             rf, by = roofline(rows, args.precision, only_mfma=True)
             if extras and args.pmc_traffic:
                 _stage("musetalk PMC traffic passes")
-                rf["traffic"], rf["traffic_note"], clk = pmc_traffic(rf["kernel"], "musetalk", args.precision, ["--batch", str(args.batch)], want_clock=bool(args.full), grids=set(rf["launch_grids"]))
+                rf["traffic"], rf["traffic_note"], clk = pmc_traffic(rf["kernel"], "musetalk", args.precision, ["--batch", str(args.batch)], want_clock=bool(args.long), grids=set(rf["launch_grids"]))
                 if rf["traffic"]:
                     rf["traffic"] = round(rf["traffic"])
                     rf["traffic_gbytes_per_s"] = round(rf["traffic"] / (rf["avg_launch_us"] * 1e-6) / 1e9, 1)
@@ -1891,9 +1981,9 @@ def main():
             torch.cuda.empty_cache()
             # 8 x 2 sessions load ONE GPU to ~85 % from eight time-sharing processes (the ranks' p99 then mostly measures that sharing); 8 x 1 leaves it half idle and
             # shows the host side by itself
-            if args.full:
+            if args.long:
                 line.setdefault("node", {})["ranks_on_one_gpu"] = ranks_on_one_gpu(args, 8, 2, 20.0)
-            light = ranks_on_one_gpu(args, 8, 1, 12.0 if args.full else 8.0)
+            light = ranks_on_one_gpu(args, 8, 1, 12.0 if args.long else 8.0)
             line.setdefault("node", {})
             line["node"]["ranks_on_one_gpu_one_session_each"] = {k: light.get(k) for k in ("ranks", "sessions_per_rank", "seconds", "wall_s", "worst_rank_p99_ms", "all_sustained",
                                                                                               "host_cpu_s_per_wall_s_per_rank", "host_cpu_s_per_wall_s_total", "frames_per_s_total", "error")}

@@ -73,3 +73,30 @@ def test_emit_prints_one_line_and_writes_the_detail_file(tmp_path, monkeypatch, 
     out = capsys.readouterr().out
     assert out.count("\n") == 1 and json.loads(out)["value"] == full["value"]
     assert json.load(open(os.path.join(str(tmp_path), bench.DETAIL_NAME)))["multi_session"] == full["multi_session"]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    frames = torch.arange(2 * 4 * 4 * 3, dtype=torch.uint8).reshape(2, 4, 4, 3)
+    counts = torch.tensor([1, 2, 3], dtype=torch.int32)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"frames": frames, "counts": counts, "trace": [1, 2]})
+    assert shapes == {"frames": [2, 4, 4, 3], "counts": [3]}
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frames.numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "counts.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)                      # a larger output: a fixed, seeded sample, the same on every call
+    big = torch.randn(4096, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "b"), {"image": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"image": big})
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert b.nbytes <= 1024 and np.array_equal(b, c) and np.isin(b, big.numpy()).all()
+
+
+def test_plain_run_refuses_options_only_full_acts_on(monkeypatch, capsys):
+    import pytest
+    for argv in (["--dump-layers", "layers.json"], ["--sessions", "8"], ["--long", "1"], ["--profile-iters", "5"]):
+        monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "2"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err, argv

@@ -728,8 +728,9 @@ def test_oracle_torso_matches_reference_golden(ref, nerf_golden):
     from oracle import ernerf_net_ref as NR
     g = nerf_golden
     got = NR.run_torso(_torso_sd(g), g["torso_bg_coords"], g["torso_pose"], g["torso_bg_in"], g["torso_offsets"], float(g["torso_log2_per_level_scale"]))
-    np.testing.assert_allclose(got["bg_color"].numpy(), g["torso_bg_color"], atol=3e-6)
-    np.testing.assert_allclose(got["torso_alpha"].numpy(), g["torso_alpha"], atol=3e-6)
+    # fp32 both sides: the host BLAS's kernel (AVX-512 or AVX2 paths) sets the summation order of the linear layers -- up to 1.8e-5 relative apart
+    np.testing.assert_allclose(got["bg_color"].numpy(), g["torso_bg_color"], rtol=2e-5, atol=3e-6)
+    np.testing.assert_allclose(got["torso_alpha"].numpy(), g["torso_alpha"], rtol=2e-5, atol=3e-6)
     m = got["mask"].numpy()
     assert 0.15 < m.mean() < 0.85 and (g["torso_alpha"][~m] == 0).all() and g["torso_alpha"][m].std() > 0.01
 
