@@ -2278,6 +2278,7 @@ std::map<std::string, ConvTuned>& tune_cache() {
         const std::string path = env ? std::string(env) : shipped_tune_table();
         // Entries are validated on load: a stale or hand-edited file must not put a tile the library no longer compiles, an impossible split or an
         // operand path that was removed into launch selection.  Keys carry the kernel generation ("g950k4": tile list / operand paths of round 4's library).
+        // KEEP IN SYNC with loader_rejects() in tests/test_tune_table.py, which holds the shipped table to these rules.
         auto valid = [](const std::string& k, const ConvTuned& c) {
             if (k.rfind("g950k4:", 0) != 0) return false;
             if (c.tile.bm == 0) return true;                                          // "the cost model's pick stays"

@@ -10,6 +10,7 @@ import torch
 
 from mere_fusion_amd import weights as W
 from mere_fusion_amd.musetalk.config import MUSETALK_V1, unet_config_json, vae_config_json
+from mere_fusion_amd.tune_grid import batches as grid_batches
 
 pytestmark = pytest.mark.gpu
 
@@ -20,6 +21,11 @@ B = 8
 TOL_LATENT = 1e-4          # measured 2.8e-5 (bound 1e-3)
 TOL_IMAGE = 6e-4           # decoder output before the clamp, values in about [-4, 4]; measured 1.8e-4 (bound 1e-3 relative = 4e-3)
 TOL_U8_FRACTION = 0.007    # fraction of uint8 pixels off by one level (round-half ties); measured 0.0019 - 0.0024
+# The single-pass bf16 mode (bench.py's `alt` legs) is not held to the north star's bound; its gates sit at about 3 x what it first measured on an
+# MI355X (batch 1 / 8 of the grid, 8-frame handles), and its error must stay at least 10 x the bf16x3 error, or the handle did not switch mode.
+TOL_BF16_LATENT = 4.5e-2   # measured 1.40e-2 / 1.49e-2 (bf16x3 on the same handles: 2.3e-5 / 2.8e-5)
+TOL_BF16_IMAGE = 2e-1      # measured 5.5e-2 / 6.8e-2 (bf16x3: 1.5e-4 / 1.7e-4)
+TOL_BF16_U8 = 24           # uint8 max diff; measured 7 / 8, with 55-56 % of the pixels differing
 
 
 @pytest.fixture(scope="module")
@@ -201,3 +207,94 @@ def test_algorithmic_flops_match_the_oracle_count(hip_full):
     fu, fv = algorithmic_flops_per_frame(*hip_full)
     m = R.count_macs(MUSETALK_V1)
     assert abs(fu / (2 * m["unet"]) - 1) < 5e-3 and abs(fv / (2 * m["vae"]) - 1) < 5e-3, (fu, 2 * m["unet"], fv, 2 * m["vae"])
+
+
+def _grid_order(b):
+    """The oracle's frame at each of b positions: frame (3 k + b) % 8 at position k, so a frame lands at other positions from batch size to batch size
+    (3 is prime to 8: positions k and k % 8 hold the same frame)."""
+    return [(3 * k + b) % B for k in range(b)]
+
+
+@pytest.fixture(scope="module")
+def hip_full_64(lib_built, full_sd):
+    """A UNet + VAE pair built for 64 frames per step, as tools/make_tune_cache.py and MuseBatcher build them: one handle serves every step size up to it."""
+    from mere_fusion_amd.musetalk.models.unet import UNet
+    from mere_fusion_amd.musetalk.models.vae import VAE
+    usd, vsd = full_sd
+    return (UNet(unet_config_json(MUSETALK_V1["unet"]), usd, max_batch=64),
+            VAE(config=vae_config_json(MUSETALK_V1["vae"]), state_dict=vsd, max_batch=64))
+
+
+def _vae_vs_oracle(vae, o, idx):
+    """the decoder alone on the oracle's latents in the order idx: (frames, image L-inf, uint8 max diff, fraction of differing uint8 pixels)"""
+    frames, image = vae.decode_latents_device(o["pred"][idx].cuda(), want_image=True)
+    ierr = (image.cpu() - o["img"][idx]).abs().max().item()
+    d = np.abs(frames.cpu().numpy().astype(int) - o["u8"][idx].astype(int))
+    return frames, ierr, int(d.max()), float((d > 0).mean())
+
+
+def test_full_every_grid_batch_on_a_64_frame_handle_vs_oracle(hip_full_64, oracle_full):
+    """Every bf16x3 batch size of the tuning table's grid (tune/gfx950.txt: a launch configuration per layer for each, and the handle's capacity switches
+    formats -- q_dual_min() in mf_musetalk.hip) on the 64-frame handles, in ascending order: the oracle's 8 frames in a batch-dependent order, each row held
+    to the oracle's latents / image / uint8 frames, copies of a frame bit-identical, and the step bit-identical through eager, capture and replay.  Then 64
+    and 8 again, identical to their first results after every other size has run (split-K workspaces, captured graphs)."""
+    unet, vae = hip_full_64
+    o = oracle_full
+    first, failed = {}, []
+    for b in grid_batches("musetalk", "bf16x3"):
+        idx = _grid_order(b)
+        lat, aud = o["lat"][idx].cuda(), o["aud"][idx].cuda()
+        calls = [tuple(t.clone() for t in _step(unet, vae, lat, aud)) for _ in range(3)]          # eager, capture, replay
+        pred, frames = calls[0]
+        first[b] = (pred.cpu(), frames.cpu())
+        lerr = (pred.cpu() - o["pred"][idx]).abs().max().item()
+        vframes, ierr, u8max, u8frac = _vae_vs_oracle(vae, o, idx)
+        print(f"MuseTalk bf16x3, batch {b:2d} (64-frame handles): latents L-inf {lerr:.3e}, image L-inf {ierr:.3e}, "
+              f"uint8 max diff {u8max}, differing pixels {100 * u8frac:.3f} %")
+        if not (lerr <= TOL_LATENT and ierr <= TOL_IMAGE and u8max <= 1 and u8frac < TOL_U8_FRACTION):
+            failed.append((b, "vs oracle", lerr, ierr, u8max, u8frac))
+        for c, (p, f) in enumerate(calls[1:], 1):
+            if not (torch.equal(p, pred) and torch.equal(f, frames)):
+                failed.append((b, f"call {c + 1} differs from call 1", float((p - pred).abs().max())))
+        for k in range(B, b):                                  # position k holds the frame of position k % 8
+            j = k % B
+            if not (torch.equal(pred[k], pred[j]) and torch.equal(frames[k], frames[j]) and torch.equal(vframes[k], vframes[j])):
+                failed.append((b, f"copies at positions {j} and {k} differ", float((pred[k] - pred[j]).abs().max())))
+                break
+    for b in (64, 8):
+        idx = _grid_order(b)
+        pred, frames = _step(unet, vae, o["lat"][idx].cuda(), o["aud"][idx].cuda())
+        if not (torch.equal(pred.cpu(), first[b][0]) and torch.equal(frames.cpu(), first[b][1])):
+            failed.append((b, "after the sweep, differs from its first result"))
+    assert not failed, failed
+
+
+@pytest.fixture(scope="module")
+def hip_full_bf16(lib_built, full_sd):
+    from mere_fusion_amd.musetalk.models.unet import UNet
+    from mere_fusion_amd.musetalk.models.vae import VAE
+    usd, vsd = full_sd
+    return (UNet(unet_config_json(MUSETALK_V1["unet"]), usd, precision="bf16", max_batch=B),
+            VAE(config=vae_config_json(MUSETALK_V1["vae"]), precision="bf16", state_dict=vsd, max_batch=B))
+
+
+@pytest.mark.parametrize("b", grid_batches("musetalk", "bf16"))
+def test_full_bf16_at_its_grid_batches_vs_oracle(hip_full, hip_full_bf16, oracle_full, b):
+    """The single-pass bf16 mode at the batch sizes of its rows in the tuning table, on handles built for 8 frames: gated against the oracle, at least 10 x the
+    bf16x3 handles' error at the same batch (the mode switch is real), and the step bit-identical through eager, capture and replay."""
+    o = oracle_full
+    idx = _grid_order(b)
+    lat, aud = o["lat"][idx].cuda(), o["aud"][idx].cuda()
+    errs, same = {}, {}
+    for prec, (unet, vae) in (("bf16x3", hip_full), ("bf16", hip_full_bf16)):
+        calls = [tuple(t.clone() for t in _step(unet, vae, lat, aud)) for _ in range(3)]          # eager, capture, replay
+        same[prec] = all(torch.equal(p, calls[0][0]) and torch.equal(f, calls[0][1]) for p, f in calls[1:])
+        lerr = (calls[0][0].cpu() - o["pred"][idx]).abs().max().item()
+        _, ierr, u8max, u8frac = _vae_vs_oracle(vae, o, idx)
+        errs[prec] = (lerr, ierr, u8max, u8frac)
+        print(f"MuseTalk {prec}, batch {b} (8-frame handles): latents L-inf {lerr:.3e}, image L-inf {ierr:.3e}, "
+              f"uint8 max diff {u8max}, differing pixels {100 * u8frac:.3f} %")
+    assert all(same.values()), same
+    lerr, ierr, u8max, _ = errs["bf16"]
+    assert lerr <= TOL_BF16_LATENT and ierr <= TOL_BF16_IMAGE and u8max <= TOL_BF16_U8, errs["bf16"]
+    assert lerr >= 10 * errs["bf16x3"][0] and ierr >= 10 * errs["bf16x3"][1], errs

@@ -14,6 +14,7 @@ import torch
 
 import geometry_cases as G
 from mere_fusion_amd import weights as W
+from mere_fusion_amd.tune_grid import batches as grid_batches
 from oracle import glue_ref
 from oracle import wav2lip_ref as R
 
@@ -79,15 +80,25 @@ def test_conv_geometry_ragged_batch(lib_built, batch):
     assert (got - want).abs().max().item() <= 2e-4 * want.abs().max().item()
 
 
-@pytest.mark.parametrize("batch", [2, 1, 16, 5])
+def _grid_inputs(batch):
+    """(mel, face, oracle rows): a batch above 16 is 16 distinct inputs tiled, so the oracle runs 16 frames and row k is held to oracle row k % 16"""
+    n = min(batch, 16)
+    mel, face, _ = W.make_lip_inputs(n, batch)
+    reps = -(-batch // n)
+    return mel.repeat(reps, 1, 1, 1)[:batch], face.repeat(reps, 1, 1, 1)[:batch], [k % n for k in range(batch)]
+
+
+@pytest.mark.parametrize("batch", grid_batches("wav2lip", "bf16x3"))
 def test_generator_bf16x3_vs_oracle(gpu_model_factory, sd0, batch):
+    """Every batch size of the tuning table's grid (tune/gfx950.txt has a launch configuration per layer for each): 1, 2, 5, 16 and the cross-session 128."""
     m = gpu_model_factory("bf16x3")
-    mel, face, _ = W.make_lip_inputs(batch, batch)
-    want = R.wav2lip_forward(sd0, mel, face)
+    mel, face, rows = _grid_inputs(batch)
+    want = R.wav2lip_forward(sd0, mel[:16], face[:16])[rows]
     with torch.no_grad():
         got = m(mel.cuda(), face.cuda()).cpu()
     assert got.shape == want.shape == (batch, 3, 96, 96)
     err = (got - want).abs().max().item()
+    print(f"Wav2Lip bf16x3, batch {batch}: L-inf vs oracle {err:.3e} (gate {TOL_X3})")
     assert err <= TOL_X3, err
 
 
@@ -116,6 +127,20 @@ def test_generator_bf16_vs_oracle(gpu_model_factory, sd0):
     assert d.max().item() <= TOL_BF16_LINF and d.mean().item() <= TOL_BF16_MEAN, (d.max().item(), d.mean().item())
 
 
+@pytest.mark.parametrize("batch", grid_batches("wav2lip", "bf16"))
+def test_generator_bf16_vs_oracle_at_grid_batch(gpu_model_factory, sd0, batch):
+    """The single-pass bf16 mode at every batch size its rows of the tuning table serve (the B = 4 test above runs the cost model's picks instead)."""
+    m = gpu_model_factory("bf16")
+    mel, face, rows = _grid_inputs(batch)
+    want = R.wav2lip_forward(sd0, mel[:16], face[:16])[rows]
+    with torch.no_grad():
+        got = m(mel.cuda(), face.cuda()).cpu()
+    assert got.shape == want.shape == (batch, 3, 96, 96)
+    d = (got - want).abs()
+    print(f"Wav2Lip bf16, batch {batch}: L-inf vs oracle {d.max().item():.3e} (gate {TOL_BF16_LINF}), mean {d.mean().item():.3e} (gate {TOL_BF16_MEAN})")
+    assert d.max().item() <= TOL_BF16_LINF and d.mean().item() <= TOL_BF16_MEAN, (d.max().item(), d.mean().item())
+
+
 def test_graph_replay_is_deterministic(gpu_model_factory):
     """call 1 runs eagerly, call 2 captures the hipGraph, calls 3+ replay it."""
     m = gpu_model_factory("bf16x3")
@@ -140,7 +165,16 @@ def test_copies_of_an_input_are_bit_identical_at_every_batch_position(gpu_model_
     """A row's result may not depend on where its image sits in the batch: `batch` copies of ONE (mel, face) pair give `batch` identical frames, call after call
     (eager, capture, replay).  The check that caught the gfx950 packed-fp32 erratum in the UNet (tests/test_musetalk_full.py), held on this
     network too (VERDICT r05 item 2 iv): its kernels run their epilogues beside other workgroups' MFMA loops just the same."""
-    m = gpu_model_factory("bf16x3")
+    _copies_are_bit_identical(gpu_model_factory("bf16x3"), batch)
+
+
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
+def test_copies_of_an_input_are_bit_identical_at_the_cross_session_batch(gpu_model_factory, precision):
+    """As above at 128 frames per step (the cross-session batch, its own rows of the tuning table), in both precisions."""
+    _copies_are_bit_identical(gpu_model_factory(precision), 128)
+
+
+def _copies_are_bit_identical(m, batch):
     mel, face, _ = W.make_lip_inputs(1, 21)
     mel, face = mel.repeat(batch, 1, 1, 1).cuda(), face.repeat(batch, 1, 1, 1).cuda()
     first = None
