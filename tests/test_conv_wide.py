@@ -271,3 +271,68 @@ def test_thin_input_conv_matches_fp64(lib_built, monkeypatch, cin, cout, k, stri
             assert err <= (1e-3 if precision == "bf16x3" else 3e-2), (mode, err)
         finally:
             l.mf_conv2d_destroy(h)
+
+
+# ---- the statistics as their consumers use them: under a group mean of R sigma ----
+# Consumers form mean = sum / n and var = sumsq / n - mean^2 (mf_gn_affine_pair), so an error e in the sum of squares is an error of ~ e (R^2 + 1) in the
+# variance: the 2e-6 check above, relative to the sums themselves, cannot see it once a group's mean is large against its spread (trained networks have such
+# groups; the seeded weights do not).  Every STATS_CASES row again, with R sigma added to each group through the conv bias (sigma: that group's spread at
+# R = 0), and the f16 + FP6 format on UNet and VAE shapes: 320 -> 320 at 32 x 32 and 512 -> 512 at 32 x 32 on the halo tile's statistics epilogue (the 320-channel
+# row through odd_wide: cout % 128 != 0, a half-empty third channel tile), 256 -> 256 at 64 x 64 (VAE size) on the halo tile as well, and 640 -> 640 at 16 x 16
+# on the f16 + FP6 implicit GEMM -- through this seam q_small_maps is off, so that shape does NOT reach the halo tile the UNet runs it on (mf_musetalk.hip:336);
+# the UNet's own 16 x 16 halo statistics are covered end to end by tests/test_musetalk_unet_stress.py at 16 and 64 frames.  Against fp64
+# statistics of the stored y: |d mean| <= 1e-5 sigma and |d var| <= 1e-4 var (rstd within 5e-5).  First MI355X measurement, worst row (per-lane fp32 partials,
+# fp64 atomics): R = 0: 1.3e-7 / 4.3e-7, R = 16: 2.2e-6 / 6.3e-6, R = 64: 8.1e-6 / 8.6e-5 (the split-K 1280 -> 640 1x1; f16 + FP6 rows at most 1.8e-5).  The
+# variance error grows as R^2, as one-pass sums must: R = 64 is the edge of what the fp32 partials hold to this gate (a margin of 1.16 x); sums taken about a
+# per-group pivot (the conv bias is known at launch) would give the headroom back.
+F16Q_STATS_CASES = [(640, 640, 3, 16, 16, 8, 0, 0, 32), (320, 320, 3, 32, 32, 8, 0, 0, 32), (512, 512, 3, 32, 32, 8, 0, 0, 32), (256, 256, 3, 64, 64, 4, 0, 0, 32)]
+OFFSET_CASES = [c + ("bf16x3",) for c in STATS_CASES] + [c + ("f16q",) for c in F16Q_STATS_CASES]
+
+
+def _conv_stats(l, C_, d, w, b, prec, x, nb, groups, out_hw):
+    from mere_fusion_amd import _lib
+    h = C_.c_void_p()
+    _lib.check(l.mf_conv2d_create(C_.byref(d), C_.c_void_p(w.data_ptr()), C_.c_void_p(b.data_ptr()), None, None, None, None, _lib.PRECISIONS[prec], C_.byref(h)))
+    try:
+        y = torch.empty(nb, d.cout, *out_hw, device="cuda")
+        st = torch.zeros((nb, groups, 2), dtype=torch.float64, device="cuda")
+        _lib.check(l.mf_conv2d_forward_stats(h, C_.c_void_p(x.data_ptr()), C_.c_void_p(y.data_ptr()), groups, C_.c_void_p(st.data_ptr()), nb, None))
+        torch.cuda.synchronize()
+        return y, st
+    finally:
+        l.mf_conv2d_destroy(h)
+
+
+@pytest.mark.parametrize("cin,cout,k,H,W,B,res,up,groups,prec", OFFSET_CASES)
+def test_conv_groupnorm_statistics_under_a_group_offset(lib_built, cin, cout, k, H, W, B, res, up, groups, prec):
+    from mere_fusion_amd import _lib
+    l = _lib.lib()
+    _lib.init_device(0)
+    g = torch.Generator().manual_seed(cin + 3 * H + k)
+    w = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
+    b = torch.randn(cout, generator=g) * 0.3
+    d = _lib.MfConv2dDesc(cin=cin, cout=cout, kh=k, kw=k, stride_h=1, stride_w=1, pad_h=k // 2, pad_w=k // 2, transposed=0, output_padding=0,
+                          residual=res, act=0, in_h=H, in_w=W, upsample=up)
+    out_hw = (2 * H, 2 * W) if up else (H, W)
+    x = torch.randn(B, cin, H, W, generator=g).cuda() + 0.25
+    sigma = None
+    worst = {}
+    for R in (0, 16, 64):
+        bias = b if R == 0 else b + (R * sigma).repeat_interleave(cout // groups).float()
+        for nb in (B, max(1, B // 2)):
+            y, st = _conv_stats(l, C, d, w, bias, prec, x, nb, groups, out_hw)
+            yg = y.double().reshape(nb, groups, -1)
+            n = yg.shape[-1]
+            if sigma is None:
+                sigma = yg.std(-1, unbiased=False).mean(0).cpu()            # per group, R = 0
+            mean = st[..., 0] / n
+            var = (st[..., 1] / n - mean * mean).clamp_min(0)
+            dm = float(((mean - yg.mean(-1)).abs() / sigma.cuda()).max())
+            dv = float(((var - yg.var(-1, unbiased=False)).abs() / yg.var(-1, unbiased=False)).max())
+            w0 = worst.get(R, (0.0, 0.0))
+            worst[R] = (max(w0[0], dm), max(w0[1], dv))
+            assert float(((yg.mean(-1) / sigma.cuda()).abs().mean())) >= 0.8 * R      # the offset is there
+    print(f"[stats {prec} {cin}->{cout} k{k} {H}x{W} b{B}] |d mean| / sigma, |d var| / var at R = 0 / 16 / 64: "
+          + ", ".join(f"{worst[R][0]:.1e} {worst[R][1]:.1e}" for R in (0, 16, 64)))
+    for R in (0, 16, 64):
+        assert worst[R][0] <= 1e-5 and worst[R][1] <= 1e-4, (R, worst[R])

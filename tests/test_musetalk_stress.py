@@ -48,10 +48,20 @@ def test_vae_f16_fp6_under_channel_scale_stress(lib_built, seed, one_sided):
                            bf16x3 everywhere (MF_CONV_Q=0)                               7e-5
          one-sided         1.7e-4 / 1.9e-4 / 1.4e-4
        (no stress: 1.4e-4 / 1.4e-4 / 9e-5).  The equalisation exists because of this test."""
+    _vae_channel_scale_stress(seed, one_sided, 8)      # the batch-8 handle: every resnet conv of the 64^2 ... 256^2 levels on the f16 + FP6 halo tile
+
+
+def test_vae_f16_fp6_under_channel_scale_stress_on_a_64_frame_handle(lib_built):
+    """The same stress at 64 frames per step on a 64-frame handle (the cross-session batcher's step: every resnet conv and all three upsamplers on the
+    f16 + FP6 tiles at full occupancy); two distinct latents, repeated, and the copies of a frame bit-identical.  Measured on MI355X (seed 1, re-parametrised):
+    image L-inf 1.2e-4, 0.20 % of uint8 pixels off by one -- the batch-8 figures."""
+    _vae_channel_scale_stress(1, False, 64)
+
+
+def _vae_channel_scale_stress(seed, one_sided, B):
     import os
     from mere_fusion_amd.musetalk.models.vae import VAE
     from oracle import musetalk_ref as R
-    B = 8                                                      # (the batch-8 handle: every resnet conv of the 64^2 ... 256^2 levels on the f16 + FP6 halo tile)
     vsd0 = W.make_musetalk_vae_state_dict(MUSETALK_V1, 0)
     vsd, n_pairs = stressed_vae_state_dict(vsd0, seed, one_sided=one_sided)
     assert n_pairs >= 25
@@ -64,10 +74,12 @@ def test_vae_f16_fp6_under_channel_scale_stress(lib_built, seed, one_sided):
     scale = float(want_img.abs().max())
     ierr = (image.cpu()[:2] - want_img).abs().max().item()
     d = np.abs(frames.cpu().numpy()[:2].astype(int) - want_u8.astype(int))
-    print(f"stressed sd-vae-ft-mse decoder ({'one-sided' if one_sided else 're-parametrised'}, seed {seed}, {n_pairs} re-scaled norm -> conv pairs): image L-inf {ierr:.3e} "
+    print(f"stressed sd-vae-ft-mse decoder (batch {B}, {'one-sided' if one_sided else 're-parametrised'}, seed {seed}, {n_pairs} re-scaled norm -> conv pairs): image L-inf {ierr:.3e} "
           f"on values up to {scale:.2f} (gate {TOL_IMAGE}); uint8 max diff {d.max()}, differing pixels {100 * (d > 0).mean():.3f} %")
     assert np.isfinite(ierr) and ierr <= TOL_IMAGE, (ierr, scale)
     assert d.max() <= 1 and (d > 0).mean() < TOL_U8_FRACTION, (d.max(), (d > 0).mean())
+    if B > 8:
+        assert all(torch.equal(frames[k], frames[k % 2]) for k in range(2, B))
 
 
 def test_vae_on_a_map_that_is_not_a_multiple_of_64_pixels(lib_built):
