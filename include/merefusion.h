@@ -402,7 +402,9 @@ void mf_nerf_torso_destroy(mf_nerf_torso* h);
 
 /* ---- ER-NeRF audio features ------------------------------------------------------------------- */
 typedef struct mf_audio_encoder mf_audio_encoder;
-/* weights: "audio_net.*" and (use_att) "audio_att_net.*" of the NeRFNetwork state dict (network.py:9-66), fp32 host. */
+/* weights: "audio_net.*" and (use_att) "audio_att_net.*" of the NeRFNetwork state dict (network.py:9-66), fp32 host.  audio_in_dim (the
+ * second dimension of audio_net.encoder_conv.0.weight) is 1..1024: esperanto 44, deepspeech 29, default 32, hubert 1024; anything wider is
+ * refused.  Above 64 the first conv runs as a launch of its own into a buffer the handle owns, and the windows must be 16-byte aligned. */
 int mf_audio_encoder_create(const mf_tensor* weights, int n_weights, int use_att, mf_audio_encoder** out);
 /* Replaces `NeRFNetwork.encode_audio(a)` (network.py:222-237): auds device fp32 [n_windows, audio_in_dim, 16]
  * (8 windows with the attention net, 1 without) -> enc_a device fp32 [32]. */

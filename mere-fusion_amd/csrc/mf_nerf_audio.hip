@@ -5,6 +5,12 @@
 // which runs once per frame on an [8, audio_in_dim, 16] window: ~0.3 MFLOP, pure launch latency in the reference (about 25
 // kernels).  Here it is one launch: a workgroup per window through AudioNet, the last one to finish runs AudioAttNet; fp32, every
 // intermediate in LDS.
+//
+// HuBERT features (audio_in_dim 1024, network.py:107-108) do not fit that launch: conv[0]'s weights alone are 1024 x 32 x 3 fp32 = 384 KB, more than the
+// LDS arena.  For 64 < audio_in_dim <= 1024 conv[0] runs first, as a launch of its own (k_audio_wide_conv0), and k_audio_encode follows unchanged on what it
+// wrote: a [n, 32, 16] "window" that holds conv[0]'s output y[c][t] (before its LeakyReLU) at step 2t and zeros elsewhere, through an identity conv[0]
+// (weight 1 at the centre tap of channel c -> c, 0 elsewhere, bias 0).  That conv reproduces LeakyReLU(y) exactly (1 * y plus exact zeros), so the wide
+// path takes the same kernel, arena layout and LDS budget as audio_in_dim 32.
 #include "mf_common.h"
 #include <map>
 #include <memory>
@@ -16,6 +22,8 @@ namespace {
 constexpr int SEQ = 8, WIN = 16, AUD_DIM = 32;
 constexpr int ACT_A = 64 * 16;           // one window's largest intermediate: the input, in_dim <= 64 channels x 16 steps
 constexpr int ACT_B = 32 * 8;            // conv[0]'s output, 32 channels x 8 steps (every later one is smaller)
+constexpr int NARROW_MAX = 64, WIDE_MAX = 1024;   // audio_in_dim served by k_audio_encode alone / with k_audio_wide_conv0 in front
+constexpr int WIDE_THREADS = 256;
 
 // Every layer's weights and bias live in ONE arena (device copy made at create time; offsets in floats, each block padded to 4): a workgroup copies the
 // whole arena -- 132 KB at audio_in_dim 29, 145 KB at 64 -- into LDS with one burst of 16-byte loads before its first layer, so the 13 layers pay ONE
@@ -171,6 +179,43 @@ __global__ __launch_bounds__(1024) void k_audio_encode(const AudioArgs a, const 
     }
 }
 
+// AudioNet.encoder_conv.0 (Conv1d(in_dim, 32, k3, s2, p1), network.py:46) for 64 < in_dim <= 1024, before its LeakyReLU: y[n][co][t], t = 0..7, stored at
+// out[n][co][2 t] (out: [n, 32, 16], odd steps left at zero for the identity conv of k_audio_encode).
+// Grid (32 output channels, n windows), 256 threads: a workgroup reads its channel's 3 * in_dim weights (12 KB at 1024) and its window (64 KB), so 256
+// workgroups spread the 8 windows' reads over the chip instead of 8 CUs reading 448 KB each.  Each workgroup owns the whole reduction over 3 * in_dim: a lane
+// takes input channels ci = tid, tid + 256, ... with the 8 outputs' partial sums in registers, then the workgroup folds them by butterfly inside each wave
+// and over the 4 waves in a fixed order -- no atomics, the same bits on every run.  auds: [n, in_dim, 16], 16-byte aligned (a channel's row is four float4).
+__global__ __launch_bounds__(WIDE_THREADS) void k_audio_wide_conv0(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ auds,
+                                                                   int in_dim, float* __restrict__ out) {
+    const int co = blockIdx.x, n = blockIdx.y;
+    const float* wr = w + (size_t)co * in_dim * 3;
+    const float4* x4 = reinterpret_cast<const float4*>(auds + (size_t)n * in_dim * WIN);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int ci = threadIdx.x; ci < in_dim; ci += WIDE_THREADS) {
+        const float4 q0 = x4[ci * 4 + 0], q1 = x4[ci * 4 + 1], q2 = x4[ci * 4 + 2], q3 = x4[ci * 4 + 3];
+        const float x[WIN] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+        const float w0 = wr[ci * 3 + 0], w1 = wr[ci * 3 + 1], w2 = wr[ci * 3 + 2];
+        acc[0] += w1 * x[0] + w2 * x[1];                        // t = 0: the tap at step -1 is the zero padding
+#pragma unroll
+        for (int t = 1; t < 8; ++t) acc[t] += w0 * x[2 * t - 1] + w1 * x[2 * t] + w2 * x[2 * t + 1];
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] = group_sum(acc[t], 64);
+    __shared__ float part[WIDE_THREADS / 64][8];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) part[threadIdx.x >> 6][t] = acc[t];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        float s = part[0][threadIdx.x];
+#pragma unroll
+        for (int v = 1; v < WIDE_THREADS / 64; ++v) s += part[v][threadIdx.x];
+        out[((size_t)n * 32 + co) * WIN + 2 * threadIdx.x] = s + bias[co];
+    }
+}
+
 }  // namespace
 
 struct mf_audio_encoder {
@@ -178,6 +223,10 @@ struct mf_audio_encoder {
     float* feat_g = nullptr;
     int* done = nullptr;
     size_t lds = 0;
+    int in_dim = 0;                    // audio_in_dim of the audio net (a.in_dim is 32 on the wide path)
+    float* w0 = nullptr;               // in_dim > 64: conv[0]'s weight [32, in_dim, 3] and bias [32], outside the arena
+    float* b0 = nullptr;
+    float* conv0_out = nullptr;        // in_dim > 64: [SEQ, 32, 16], conv[0]'s output at the even steps (k_audio_wide_conv0)
     std::vector<float*> dev;
     ~mf_audio_encoder() { for (float* d : dev) (void)hipFree(d); }
 };
@@ -213,12 +262,38 @@ extern "C" int mf_audio_encoder_create(const mf_tensor* weights, int n_weights, 
     MF_REQUIRE(it != sd.end() && it->second->ndim == 3 && it->second->shape[0] == 32 && it->second->shape[2] == 3,
                "audio_encoder_create: audio_net.encoder_conv.0.weight [32, in_dim, 3] missing");
     const int in_dim = (int)it->second->shape[1];
-    MF_REQUIRE(in_dim >= 1 && in_dim <= 64, "audio_encoder_create: audio_in_dim %d (1..64 built: esperanto 44, deepspeech 29, default 32; hubert's 1024 is not)", in_dim);
-    h->a.in_dim = in_dim;
+    MF_REQUIRE(in_dim >= 1 && in_dim <= WIDE_MAX, "audio_encoder_create: audio_in_dim %d is outside 1..%d (esperanto 44, deepspeech 29, default 32, hubert 1024)",
+               in_dim, WIDE_MAX);
+    const bool wide = in_dim > NARROW_MAX;
+    h->in_dim = in_dim;
+    h->a.in_dim = wide ? 32 : in_dim;
     h->a.use_att = use_att ? 1 : 0;
     int rc;
     const int cc[5] = {in_dim, 32, 32, 64, 64};                 // network.py:46-53 (Sequential indices 0, 2, 4, 6)
-    for (int i = 0; i < 4; ++i)
+    if (wide) {
+        auto b = sd.find("audio_net.encoder_conv.0.bias");
+        MF_REQUIRE(b != sd.end(), "audio_encoder_create: tensor 'audio_net.encoder_conv.0.bias' missing");
+        int64_t nb = 1;
+        for (int d = 0; d < b->second->ndim; ++d) nb *= b->second->shape[d];
+        MF_REQUIRE(nb == 32, "audio_encoder_create: 'audio_net.encoder_conv.0.bias' has %lld elements, expected 32", (long long)nb);
+        const size_t nw = (size_t)32 * in_dim * 3, nout = (size_t)SEQ * 32 * WIN;
+        MF_HIP(hipMalloc(&h->w0, (nw + 32 + nout) * sizeof(float)));
+        h->dev.push_back(h->w0);
+        h->b0 = h->w0 + nw;
+        h->conv0_out = h->b0 + 32;
+        MF_HIP(hipMemcpy(h->w0, it->second->data, nw * sizeof(float), hipMemcpyHostToDevice));
+        MF_HIP(hipMemcpy(h->b0, b->second->data, 32 * sizeof(float), hipMemcpyHostToDevice));
+        MF_HIP(hipMemset(h->conv0_out, 0, nout * sizeof(float)));   // the odd steps stay zero
+        // the identity conv[0] k_audio_encode runs on conv0_out: weight [32, 32, 3] = 1 at [c][c][1], bias 0
+        Layer& L = h->a.conv[0];
+        L.cin = 32; L.cout = 32; L.woff = 0;
+        arena.assign((size_t)32 * 32 * 3 + 32, 0.f);
+        for (int c = 0; c < 32; ++c) arena[((size_t)c * 32 + c) * 3 + 1] = 1.f;
+        L.boff = 32 * 32 * 3;
+    } else if ((rc = layer("audio_net.encoder_conv.0", cc[0], cc[1], 3, &h->a.conv[0]))) {
+        return rc;
+    }
+    for (int i = 1; i < 4; ++i)
         if ((rc = layer("audio_net.encoder_conv." + std::to_string(2 * i), cc[i], cc[i + 1], 3, &h->a.conv[i]))) return rc;
     if ((rc = layer("audio_net.encoder_fc1.0", 64, 64, 1, &h->a.fc[0])) || (rc = layer("audio_net.encoder_fc1.2", 64, AUD_DIM, 1, &h->a.fc[1]))) return rc;
     if (use_att) {
@@ -248,6 +323,12 @@ static int audio_encoder_launch(mf_audio_encoder* h, const float* auds, int n_wi
     MF_REQUIRE(h && auds && enc_a, "audio_encoder_forward: null argument");
     MF_REQUIRE(h->a.use_att ? n_windows == SEQ : n_windows == 1,
                "audio_encoder_forward: %d windows (the attention net pools exactly 8, network.py:10; without it one window)", n_windows);
+    if (h->conv0_out) {
+        MF_REQUIRE(((uintptr_t)auds & 15) == 0, "audio_encoder_forward: the windows must be 16-byte aligned for audio_in_dim > %d", NARROW_MAX);
+        hipLaunchKernelGGL(k_audio_wide_conv0, dim3(32, n_windows), dim3(WIDE_THREADS), 0, (hipStream_t)stream, h->w0, h->b0, auds, h->in_dim, h->conv0_out);
+        MF_HIP(hipGetLastError());
+        auds = h->conv0_out;
+    }
     static bool attr_done = false;
     if (!attr_done) {
         MF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_audio_encode), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));   // (the kernel's static s_last shares the 160 KB)

@@ -38,6 +38,10 @@ class HipWav2Vec2ForCTC:
             raise RuntimeError("HipWav2Vec2ForCTC needs a HIP device; no CPU path exists here")
         if _cfg_get(config, "feat_extract_norm") != "layer":
             raise ValueError('only feat_extract_norm == "layer" checkpoints are supported (the xlsr-53 / large models app.py:660-662 names)')
+        fpln = config.get("feat_proj_layer_norm", True) if isinstance(config, dict) else getattr(config, "feat_proj_layer_norm", True)
+        if not fpln:                 # a HubertConfig field (Wav2Vec2 always has this LayerNorm); the kernel always applies it
+            raise ValueError("feat_proj_layer_norm=False (a HuBERT feature projection without its LayerNorm) is not supported: mf_wav2vec2_forward always "
+                             "applies feature_projection.layer_norm")
         self.device = torch.device(device)
         _lib.init_device(self.device.index if self.device.index is not None else torch.cuda.current_device())
         c = _lib.MfWav2Vec2Config()

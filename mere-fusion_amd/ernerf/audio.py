@@ -1,4 +1,5 @@
-"""`NeRFNetwork.encode_audio` (ernerf/nerf_triplane/network.py:222-237) on MI355X: AudioNet + AudioAttNet in one kernel launch.
+"""`NeRFNetwork.encode_audio` (ernerf/nerf_triplane/network.py:222-237) on MI355X: AudioNet + AudioAttNet in one kernel launch (two when
+audio_in_dim > 64, e.g. HuBERT's 1024: the first conv runs on its own in front).
 
     enc = HipAudioEncoder(model.state_dict(), att=opt.att)
     model.encode_audio = enc.encode_audio          # renderer.py:187 calls self.encode_audio(auds)
@@ -16,6 +17,8 @@ class HipAudioEncoder:
         _lib.init_device(self.device.index or 0)
         self._lib = _lib.lib()
         keep = {k: v for k, v in state_dict.items() if k.startswith(("audio_net.", "audio_att_net."))}
+        w0 = keep.get("audio_net.encoder_conv.0.weight")
+        self.in_dim = int(w0.shape[1]) if w0 is not None and w0.dim() == 3 else None     # audio_in_dim, network.py:102-110
         arr, self._keep = _lib.tensor_array(keep)
         self._h = C.c_void_p()
         self.att = int(att)
@@ -27,14 +30,21 @@ class HipAudioEncoder:
             self._lib.mf_audio_encoder_destroy(h)
             self._h = None
 
+    def _windows(self, a, who):
+        """a as the kernels read it: contiguous fp32 [n, in_dim, 16] on the device, 16-byte aligned (the wide first layer reads float4 rows)."""
+        if not (torch.is_tensor(a) and a.is_cuda):
+            raise RuntimeError(f"HipAudioEncoder.{who}: the window must be a CUDA tensor (there is no CPU path)")
+        if a.dim() != 3 or a.shape[1] != self.in_dim or a.shape[2] != 16:
+            raise RuntimeError(f"HipAudioEncoder.{who}: windows must be [n, {self.in_dim}, 16] (audio_in_dim of this audio net), got {list(a.shape)}")
+        a = a.float().contiguous()
+        return a if a.data_ptr() % 16 == 0 else a.clone()
+
     def encode_audio_smooth(self, a, prev):
         """`encode_audio(a)` followed by renderer.py:190-194's lip smoothing against the previous frame's features `prev` ([1, 32] CUDA fp32, or None on
         the first frame): 0.35 * prev + (1 - 0.35) * enc_a, inside the same launch (bit-identical to the torch expression)."""
         if a is None:
             return None
-        if not (torch.is_tensor(a) and a.is_cuda):
-            raise RuntimeError("HipAudioEncoder.encode_audio_smooth: the window must be a CUDA tensor (there is no CPU path)")
-        a = a.float().contiguous()
+        a = self._windows(a, "encode_audio_smooth")
         out = torch.empty(1, 32, device=a.device)
         pv = None
         if prev is not None:
@@ -50,9 +60,7 @@ class HipAudioEncoder:
         """a: [8, audio_in_dim, 16] (att > 0) or [1, audio_in_dim, 16] CUDA tensor -> [1, 32]; None passes through (network.py:227)."""
         if a is None:
             return None
-        if not (torch.is_tensor(a) and a.is_cuda):
-            raise RuntimeError("HipAudioEncoder.encode_audio: the window must be a CUDA tensor (there is no CPU path)")
-        a = a.float().contiguous()
+        a = self._windows(a, "encode_audio")
         out = torch.empty(1, 32, device=a.device)
         _lib.check(self._lib.mf_audio_encoder_forward(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0]), C.c_void_p(out.data_ptr()),
                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_audio_encoder_forward")

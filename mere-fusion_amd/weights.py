@@ -422,6 +422,19 @@ WAV2VEC2_XLSR_LARGE = dict(hidden_size=1024, num_hidden_layers=24, num_attention
 # reduced twin for quick tests: same structure, head dim 64 (the fused attention kernel's), 2 layers
 WAV2VEC2_SMALL = dict(WAV2VEC2_XLSR_LARGE, hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, vocab_size=44,
                       conv_dim=(64,) * 7, num_conv_pos_embedding_groups=2)
+# facebook/hubert-large-ls960-ft (nerfasr.py:41-43: HubertModel, `.last_hidden_state` -> audio_dim 1024) [upstream-knowledge: the published model config,
+# not read from a checkpoint here]: the large architecture with layer-norm feature extractor, stable (pre-)LayerNorm and the projection LayerNorm
+HUBERT_LARGE = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096, conv_dim=(512,) * 7,
+                    conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_bias=True, feat_extract_norm="layer",
+                    do_stable_layer_norm=True, feat_proj_layer_norm=True, num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16,
+                    layer_norm_eps=1e-5)
+
+
+def make_hubert_state_dict(cfg, seed=0):
+    """Seeded HubertModel weights under transformers' own names: the wav2vec2 body of make_wav2vec2_state_dict without its prefix and CTC head
+    (masked_spec_embed included, as in the real checkpoint)."""
+    sd = make_wav2vec2_state_dict(dict(cfg, vocab_size=1), seed)
+    return {k[len("wav2vec2."):]: v for k, v in sd.items() if k.startswith("wav2vec2.")}
 
 
 def make_wav2vec2_state_dict(cfg, seed=0, shapes_only=False):
