@@ -2063,6 +2063,10 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
         if (tc.bm > 128 && a.M <= 256) { tc.bm = 64; tc.bn = 64; tc.wgm = 2; tc.wgn = 2; }
         if (p->d.act == 5 && tc.bn < 32) tc.nsplit = 1;
     }
+    // the split-K partials ([split][B][Ho][Wo][N], unpadded rows) are written and combined in float4 channel quads: with a cout that is not a multiple
+    // of 4 the last quad of a row would overwrite the next pixel's first channels (and run past the workspace at the last one), and the combine would
+    // drop the row's last channels.  Such a layer takes the single-pass epilogue.
+    if (a.N % 4) tc.nsplit = 1;
     a.tiles_m = cdiv(a.M, tc.bm); a.tiles_n = cdiv(a.N, tc.bn);
     {
         // XCD tile order by which operand is heavier: weights N x K vs the input tensor M x Cin (both x planes)

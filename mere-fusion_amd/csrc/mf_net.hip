@@ -235,6 +235,9 @@ extern "C" int mf_net_conv(mf_net* h, const mf_conv2d_desc* d, const float* weig
 extern "C" int mf_net_maxpool(mf_net* h, int in_buf, int out_buf, int k, int stride, int pad) {
     MF_REQUIRE(h && k >= 1 && stride >= 1 && pad >= 0 && 2 * pad <= k, "net_maxpool: bad window");
     NET_BUF(ib, in_buf); NET_BUF(ob, out_buf);
+    // (C division truncates: without this a window larger than the padded map would pass below with a 1-pixel output that F.max_pool2d refuses)
+    MF_REQUIRE(ib->H + 2 * pad >= k && ib->W + 2 * pad >= k, "net_maxpool: bad window: %d x %d is larger than the padded %dx%d map", k, k, ib->H + 2 * pad,
+               ib->W + 2 * pad);
     MF_REQUIRE(ob->C == ib->C && ob->H == (ib->H + 2 * pad - k) / stride + 1 && ob->W == (ib->W + 2 * pad - k) / stride + 1,
                "net_maxpool: output buffer %dx%dx%d does not match floor((%dx%d + 2*%d - %d) / %d) + 1", ob->C, ob->H, ob->W, ib->H, ib->W, pad, k, stride);
     h->ops.push_back([ib, ob, k, stride, pad](int B, hipStream_t s) {

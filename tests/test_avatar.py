@@ -140,3 +140,46 @@ def test_hip_bisenet_full_size_matches_oracle(lib_built):
     want_p = want[0].argmax(0); want_p[want_p > 13] = 0; want_p[want_p >= 1] = 255
     assert (parsing == want_p).mean() >= 0.999
     assert torch.equal(net(torch.from_numpy(x))[0], net(torch.from_numpy(x))[0])      # graph replay is deterministic
+
+
+# bf16 (no lo plane: Pl::ld / Pl::st and every conv take their bf16 branch).  Gates at ~3 x the first MI355X measurement (S3FD levels 1-3 5.8e-3,
+# levels 4-6 1.33; BiSeNet 1.15e-2 x max |logit|, argmax agreement 0.99954); the bf16 error must stay at least 10 x the bf16x3 error of the same input
+# (measured: ~510 x), or one of the two handles did not run in the precision it was asked for.
+S3FD_BF16_GATES = (1.7e-2, 4.0)             # (levels 1-3, levels 4-6)
+BISENET_BF16_GATE = 3.5e-2                  # x max |logit|
+
+
+@pytest.mark.gpu
+def test_hip_s3fd_bf16_matches_oracle(lib_built):
+    rng = np.random.default_rng(1101)
+    x = (rng.uniform(0, 255, (1, 3, 101, 135)) - np.array([104, 117, 123]).reshape(1, 3, 1, 1)).astype(np.float32)
+    with torch.no_grad():
+        want = s3fd_ref.s3fd_forward(W.make_s3fd_state_dict(0), torch.from_numpy(x))
+    errs = {}
+    for prec in ("bf16x3", "bf16"):
+        got = _s3fd(precision=prec, max_batch=1)(torch.from_numpy(x))
+        errs[prec] = [float((g.cpu() - w).abs().max()) for g, w in zip(got, want)]
+    e3, e1 = errs["bf16x3"], errs["bf16"]
+    print("[s3fd 1x101x135 bf16 vs oracle] max |diff| per output: " + " ".join(f"{e:.1e}" for e in e1)
+          + f"; levels 1-3 {max(e1[:6]):.3e} ({max(e1[:6]) / max(e3[:6]):.0f} x bf16x3), levels 4-6 {max(e1[6:]):.3e} ({max(e1[6:]) / max(e3[6:]):.0f} x bf16x3)")
+    assert max(e3[:6]) <= 1e-3 and max(e3[6:]) <= 5e-3, e3
+    assert max(e1[:6]) <= S3FD_BF16_GATES[0] and max(e1[6:]) <= S3FD_BF16_GATES[1], e1
+    assert max(e1[:6]) >= 10 * max(e3[:6]) and max(e1[6:]) >= 10 * max(e3[6:]), (e1, e3)
+
+
+@pytest.mark.gpu
+def test_hip_bisenet_bf16_full_size_matches_oracle(lib_built):
+    rng = np.random.default_rng(5)
+    x = ((rng.uniform(0, 1, (1, 3, 512, 512)) - np.array([0.485, 0.456, 0.406]).reshape(1, 3, 1, 1)) / np.array([0.229, 0.224, 0.225]).reshape(1, 3, 1, 1)).astype(np.float32)
+    with torch.no_grad():
+        want = bisenet_ref.bisenet_forward(W.make_bisenet_state_dict(0), torch.from_numpy(x))[0].numpy()
+    scale = np.abs(want).max()
+    err, agree = {}, {}
+    for prec in ("bf16x3", "bf16"):
+        got = _bisenet(precision=prec)(torch.from_numpy(x))[0].cpu().numpy()
+        err[prec], agree[prec] = np.abs(got - want).max() / scale, (got.argmax(1) == want.argmax(1)).mean()
+    print(f"[bisenet 512x512 vs oracle] logits L-inf / max|logit|: bf16 {err['bf16']:.3e}, bf16x3 {err['bf16x3']:.3e} ({err['bf16'] / err['bf16x3']:.0f} x);"
+          f" argmax agreement bf16 {agree['bf16']:.6f}, bf16x3 {agree['bf16x3']:.6f}")
+    assert err["bf16x3"] <= 2e-3 and agree["bf16x3"] >= 0.999
+    assert err["bf16"] <= BISENET_BF16_GATE and agree["bf16"] >= 0.9985
+    assert err["bf16"] >= 10 * err["bf16x3"]
