@@ -142,6 +142,27 @@ int mf_conv2d_forward_stats(mf_conv2d* h, const float* x, float* y, int groups, 
  * `iters` repeats on the buffers of the last mf_conv2d_forward, bracketed by hipEvents on `stream`. */
 int mf_conv2d_time(mf_conv2d* h, int batch, int iters, float* ms, void* stream);
 void mf_conv2d_destroy(mf_conv2d* h);
+/* Test seam of the launch selection.  mf_conv2d_launch_config: what mf_conv2d_forward (stats_groups == 0) or mf_conv2d_forward_stats(stats_groups) at
+ * `batch` will launch -- resolved by the code the launch itself runs.  info[0 .. 11): family (MF_CONV_FAMILY_*), bm, bn, wgm, wgn (halo families: patch
+ * rows, channels, waves), the split that launches (after every clamp; halo families: the channel split), the operand path ld that runs (-1 resolved;
+ * -1 outside the implicit GEMM), K depth BK (halo families: the channel slice), phases, the GroupNorm statistics source (MF_CONV_STATS_*), and 1 when the
+ * configuration is pinned (by mf_conv2d_pin_config or the tuning table).  n >= 11.
+ * mf_conv2d_pin_config: the implicit-GEMM configuration (tile, split-K, ld) the layer launches at `batch`, in the slot the tuning table fills, with the
+ * table's split clamp; refused for a configuration no compiled kernel of the layer's precision runs, and for layers the table does not serve.
+ * bm == 0 unpins. */
+#define MF_CONV_FAMILY_IGEMM 0        /* implicit GEMM (mf_conv.hip) */
+#define MF_CONV_FAMILY_HALO 1         /* register-weights halo tile (mf_conv_halo.hip) */
+#define MF_CONV_FAMILY_HALO_W 2       /* LDS-weights halo tile (mf_conv_halo2.hip) */
+#define MF_CONV_FAMILY_HALO_W_SPLIT 3 /* ... its 256-channel tile with the channel slices split, combined by the split-K epilogue */
+#define MF_CONV_FAMILY_TWIN 4         /* the implicit-GEMM twin of a wide halo plan */
+#define MF_CONV_FAMILY_THIN 5         /* thin-input kernel (mf_conv_thin.hip) */
+#define MF_CONV_FAMILY_F16Q 6         /* f16 + FP6 halo tile */
+#define MF_CONV_STATS_NONE 0
+#define MF_CONV_STATS_EPILOGUE 1      /* the conv's own epilogue */
+#define MF_CONV_STATS_COMBINE 2       /* the split-K combine (k_splitk_epilogue_stats) */
+#define MF_CONV_STATS_PASS 3          /* a k_gn_stats pass behind the conv */
+int mf_conv2d_launch_config(const mf_conv2d* h, int batch, int stats_groups, int* info, int n);
+int mf_conv2d_pin_config(mf_conv2d* h, int batch, int bm, int bn, int wgm, int wgn, int nsplit, int ld);
 
 /* ---- Wav2Lip mel-spectrogram (H1) -------------------------------------------------------- */
 /* Replaces `audio.melspectrogram(inputs)` (lipasr.py:23 -> wav2lip/audio.py:45-51 with the

@@ -195,6 +195,19 @@ void mf_conv_plan_destroy(ConvPlan* p);
 // row stride = Wp*C).  Must be called once before launch; rebinding to another geometry is allowed.
 int mf_conv_bind(ConvPlan* p, const ActBuf& in);
 
+// The launch configuration mf_conv_launch runs at a batch, resolved in ONE place: conv_launch_impl launches what this returns, and mf_conv_kernel_name /
+// mf_conv2d_launch_config report it.  family: MF_CONV_FAMILY_* (include/merefusion.h); tile: implicit GEMM bm, bn, wgm, wgn and the split that launches
+// (after every clamp), halo families patch rows, channels, waves and the channel split; ld: the operand path that runs (-1 resolved; -1 outside the implicit
+// GEMM); bk: K depth of one stage (halo families: the channel slice); stats: where the GroupNorm statistics of a launch with `stats_groups` > 0 come from
+// (MF_CONV_STATS_*).  Returns MF_ERR_INVALID (with the reason in mf_last_error) for a configuration no compiled kernel of this plan's precision runs.
+struct ConvLaunchCfg { int family; ConvTile tile; int ld, bk, nphase, stats; bool pinned; };
+int mf_conv_resolve(const ConvPlan* p, int batch, int tokens, int stats_groups, ConvLaunchCfg* c);
+// The rules of a (tile, split, ld) entry of the tuning table, and of mf_conv_pin: false (reason in mf_last_error) for one that names no compiled kernel of
+// `precision` that serves activation `act`
+bool mf_conv_tuned_valid(const ConvTuned& c, int precision, int act);
+// Test seam (mf_conv2d_pin_config): c in p->tuned[batch], the slot the tuning table fills, with the table's split clamp -- refused (MF_ERR_INVALID) where the
+// table would not serve the layer or mf_conv_tuned_valid rejects c; bm == 0 unpins
+int mf_conv_pin(ConvPlan* p, int batch, const ConvTuned& c);
 // rocprofv3-style name of the kernel mf_conv_launch will use at this batch size
 void mf_conv_kernel_name(const ConvPlan* p, int batch, char* buf, int cap);
 // Workgroup tile the launch will use for this batch size (kernel = k_conv_igemm<bm,bn,wgm,wgn,x3>).

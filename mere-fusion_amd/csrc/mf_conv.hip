@@ -806,10 +806,6 @@ __global__ __launch_bounds__((WGM * WGN + (LD == 3 ? igemm_producers<BM, BN, BK>
                         else if (ACT == 4) x = x / (1.f + expf(-x));
                         v[e] = x + (after ? r[e] : 0.f);
                     }
-                    if (ST && row_ok) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { gs[i][e] += v[e]; gq[i][e] += v[e] * v[e]; }
-                    }
                     if (a.ln_out && n0 + cn0 + i * 16 + fk * 4 < a.N) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { row_s += v[e]; row_q += v[e] * v[e]; }
@@ -817,6 +813,11 @@ __global__ __launch_bounds__((WGM * WGN + (LD == 3 ? igemm_producers<BM, BN, BK>
                     uint32_t h[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) h[e] = f2bf(v[e]);
+                    if (ST && row_ok) {
+                        // statistics of the STORED values, as k_gn_stats reads them: bf16 stores the rounded hi alone (hi + lo is v to 2^-17)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { const float s = X3 ? v[e] : bf2f(h[e]); gs[i][e] += s; gq[i][e] += s * s; }
+                    }
                     pk_hi[i] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
                     if (X3) {
                         uint32_t l[4];
@@ -964,6 +965,10 @@ __device__ __forceinline__ void epilogue_store_pre(const ConvArgs& a, float (&v)
 #pragma unroll
         for (int e = 0; e < 4; ++e) l[e] = f2bf(v[e] - bf2f(h[e]));
         *reinterpret_cast<uint2*>(a.y_lo + yo + c) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
+    } else {
+        // v leaves as the value stored (bf16: the rounded hi alone), so that k_splitk_epilogue_stats sums the stored output, as k_gn_stats does
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = bf2f(h[e]);
     }
 }
 
@@ -1707,6 +1712,107 @@ int mf_q_split_count(const ConvPlan* p, int batch) {
     return best;
 }
 
+bool mf_conv_tuned_valid(const ConvTuned& c, int precision, int act) {
+    static const int tiles[][4] = {{64, 64, 2, 2}, {128, 64, 2, 2}, {128, 128, 2, 2}, {256, 128, 4, 2}, {256, 256, 2, 4}, {128, 80, 4, 1}};
+    bool tile_ok = false;
+    for (const auto& t : tiles) tile_ok |= c.tile.bm == t[0] && c.tile.bn == t[1] && c.tile.wgm == t[2] && c.tile.wgn == t[3];
+    const char* why = nullptr;
+    if (!tile_ok) why = "tile not compiled";
+    else if (c.tile.nsplit < 1 || c.tile.nsplit > 16) why = "split outside 1 .. 16";
+    else if (!(c.ld == -1 || c.ld == 0 || c.ld == 2 || c.ld == 3 || c.ld == 4)) why = "no such operand path";
+    else if ((c.ld == 3 || c.ld == 4) && c.tile.wgm * c.tile.wgn != 4) why = "the producer-wave path (ld 3 / 4) needs a 4-wave tile";
+    else if (c.tile.bn == 80 && c.ld != 3 && c.ld != 4) why = "the 128 x 80 tile runs on the producer-wave kernels (ld 3 / 4) only";
+    // the producer-wave kernels exist in bf16x3 only (launch_prec / launch_pw_only): in bf16 such an entry would fail at launch
+    else if ((c.ld == 3 || c.ld == 4 || c.tile.bn == 80) && precision != MF_PREC_BF16X3) why = "the producer-wave kernels (ld 3 / 4, the 128 x 80 tile) are bf16x3 only";
+    // the GEGLU epilogue pairs a wave's value and gate fragments: the 80-channel tile's five fragments per wave do not pair (mf_tile80_ok)
+    else if (c.tile.bn == 80 && act == 5) why = "the 128 x 80 tile cannot pair GEGLU value / gate fragments";
+    if (why) mf_set_error("conv: configuration %dx%d (%d x %d waves) split %d ld %d: %s", c.tile.bm, c.tile.bn, c.tile.wgm, c.tile.wgn, c.tile.nsplit, c.ld, why);
+    return !why;
+}
+
+int mf_conv_resolve(const ConvPlan* p, int batch, int tokens, int stats_groups, ConvLaunchCfg* c) {
+    *c = ConvLaunchCfg{MF_CONV_FAMILY_IGEMM, ConvTile{0, 0, 0, 0, 1}, -1, 0, p->nphase, MF_CONV_STATS_NONE, false};
+    const int groups = stats_groups > 0 ? stats_groups : 0;
+    // split-K / channel-split combines that leave the statistics (launch_combine_stats)
+    const bool combine_stats = groups && p->d.act != 5 && p->d.cout % 4 == 0 && p->d.cout % groups == 0 && groups <= 64;
+    const int halo_ck = p->precision != MF_PREC_BF16 ? 32 : 64;
+    auto stats = [&](int src) { c->stats = groups ? src : MF_CONV_STATS_NONE; return MF_OK; };
+    if (p->thin) {
+        c->family = MF_CONV_FAMILY_THIN; c->tile = ConvTile{p->out_h, p->d.cout, 1, 1, 1}; c->bk = p->d.cin <= 8 ? 8 : 16;
+        return stats(MF_CONV_STATS_PASS);
+    }
+    const bool q_gn = groups && p->d.cout % groups == 0 && (p->d.cout / groups == 4 || p->d.cout / groups == 8 || p->d.cout / groups == 16);
+    if (p->halo) {
+        c->bk = halo_ck;
+        if (p->q) {
+            const int ns = mf_q_split_count(p, batch);
+            c->family = MF_CONV_FAMILY_F16Q; c->tile = ConvTile{16, 128, 4, 2, ns};
+            return stats(ns > 1 ? (combine_stats ? MF_CONV_STATS_COMBINE : MF_CONV_STATS_PASS) : q_gn ? MF_CONV_STATS_EPILOGUE : MF_CONV_STATS_PASS);
+        }
+        const HaloTile tw = mf_halo_w_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin);
+        if (tw.ph) {
+            c->family = MF_CONV_FAMILY_HALO_W; c->tile = ConvTile{tw.ph, tw.bn, tw.wgm, tw.wgn, 1};
+            return stats(MF_CONV_STATS_PASS);
+        }
+        if (const int ns = mf_halo_split_count(p, batch)) {
+            c->family = MF_CONV_FAMILY_HALO_W_SPLIT; c->tile = ConvTile{16, 256, 2, 4, ns};
+            return stats(combine_stats ? MF_CONV_STATS_COMBINE : MF_CONV_STATS_PASS);
+        }
+        if (p->alt) {
+            const int rc = mf_conv_resolve(p->alt, batch, 0, stats_groups, c);
+            c->family = MF_CONV_FAMILY_TWIN;
+            return rc;
+        }
+        const HaloTile t = mf_halo_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin);
+        c->family = MF_CONV_FAMILY_HALO; c->tile = ConvTile{t.ph, t.bn, t.wgm, t.wgn, 1};
+        return stats(MF_CONV_STATS_PASS);
+    }
+    if (p->up_hi && p->q) {
+        c->family = MF_CONV_FAMILY_F16Q; c->tile = ConvTile{16, 128, 4, 2, 1}; c->bk = 32; c->nphase = 4;
+        return stats(q_gn ? MF_CONV_STATS_EPILOGUE : MF_CONV_STATS_PASS);
+    }
+    // ---- implicit GEMM
+    const bool x3 = p->precision != MF_PREC_BF16;
+    ConvTile tc = mf_conv_pick_tile(p, batch);
+    int ld = -1;
+    {
+        static const bool forced = getenv("MF_FORCE_TILE") || getenv("MF_FORCE_SPLIT") || getenv("MF_FORCE_LD");
+        auto it = p->tuned.find(batch);
+        if (it != p->tuned.end()) { ld = it->second.ld; c->pinned = !forced; }
+        static const int force_ld = [] { const char* e = getenv("MF_FORCE_LD"); return e ? atoi(e) : -1; }();   // (measurement, with MF_FORCE_TILE / MF_FORCE_SPLIT)
+        if (force_ld >= 0 && !(force_ld >= 3 && (!x3 || p->q || tc.wgm * tc.wgn != 4 || tc.bn < 64 || tc.bm < 64))) ld = force_ld;
+    }
+    const int Wq_eff = tokens > 0 ? tokens : p->Wq;
+    const int M = batch * p->Hq * Wq_eff;
+    if (tokens > 0) {
+        // the cost model priced the full sequence: re-balance the split for the rows actually computed
+        const int nt = cdiv(M, tc.bm) * cdiv(p->d.cout, tc.bn);
+        int kt_min = p->ph[0].KT;
+        tc.nsplit = nt >= 256 ? 1 : std::max(1, std::min(std::min(kt_min, cdiv(512, nt)), 16));
+        if (tc.bm > 128 && M <= 256) { tc.bm = 64; tc.bn = 64; tc.wgm = 2; tc.wgn = 2; }
+        if (p->d.act == 5 && tc.bn < 32) tc.nsplit = 1;
+    }
+    // the split-K partials ([split][B][Ho][Wo][N], unpadded rows) are written and combined in float4 channel quads: with a cout that is not a multiple
+    // of 4 the last quad of a row would overwrite the next pixel's first channels (and run past the workspace at the last one), and the combine would
+    // drop the row's last channels.  Such a layer takes the single-pass epilogue.
+    if (p->d.cout % 4) tc.nsplit = 1;
+    c->tile = tc;
+    // the operand path and stage depth launch_prec / launch_cfg / launch_pw_only take for this (tile, ld)
+    const bool four = tc.wgm * tc.wgn == 4;
+    const bool pw = ld == 3 || ld == 4;
+    MF_REQUIRE(!pw || (x3 && !p->q && four && tc.bm >= 64 && tc.bn >= 64), "conv: no producer-wave kernel (ld %d) for tile %dx%d in this precision", ld, tc.bm, tc.bn);
+    MF_REQUIRE(tc.bn != 80 || pw, "conv: the %dx%d tile has only the bf16x3 producer-wave kernels (ld 3 / 4)", tc.bm, tc.bn);
+    c->ld = pw ? ld : (four && (ld >= 0 ? ld : 2) == 2) ? 2 : 0;
+    c->bk = p->q ? (four ? 64 : 32) : pw ? (ld == 3 ? 64 : 32) : x3 ? (four ? 64 : 32) : 64;
+    if (groups && tokens == 0) {
+        if (tc.nsplit > 1) return stats(combine_stats ? MF_CONV_STATS_COMBINE : MF_CONV_STATS_PASS);
+        // in the epilogue: 4-wave tiles (k_conv_igemm's ST) whose pixel tile lies inside one sample
+        if (p->d.act != 5 && p->d.cout % groups == 0 && groups <= 64 && four && tc.bm * tc.bn < 128 * 128 && (p->Hq * Wq_eff) % tc.bm == 0)
+            return stats(MF_CONV_STATS_EPILOGUE);
+    }
+    return stats(MF_CONV_STATS_PASS);
+}
+
 static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, const ActView& res, int batch, hipStream_t stream, int tokens, bool* stats_done);
 
 // split-K combine that also leaves the consumer GroupNorm's statistics (k_splitk_epilogue_stats); false = not applicable, run the plain combine
@@ -1850,8 +1956,10 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
     const bool x3 = p->precision != MF_PREC_BF16;                      // two planes per tensor (bf16x3, and the f16 + FP6 format)
     MF_REQUIRE(!x3 || (ib.lo && ob.lo), "conv: BF16X3 needs lo planes");
     MF_REQUIRE(p->precision != MF_PREC_F16Q || p->q, "conv (f16q): the plan was not packed in this format");
+    ConvLaunchCfg cfg;
+    if (const int rc = mf_conv_resolve(p, batch, tokens, p->out_stats ? p->out_stats_groups : 0, &cfg)) return rc;
 
-    if (p->thin) {
+    if (cfg.family == MF_CONV_FAMILY_THIN) {
         MF_REQUIRE(!res.buf && ib.halo >= p->d.pad_h, "thin conv: no residual, and the input buffer's zero ring must cover the padding");
         ThinArgs ta{};
         ta.x_hi = ib.hi + in.coff; ta.x_lo = x3 ? ib.lo + in.coff : nullptr;
@@ -1886,21 +1994,17 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
             }
         }
         ha.act = p->d.act;
-        const HaloTile tw = mf_halo_w_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin);
-        if (p->q) {                             // the f16 + FP6 format has one kernel: the 8-wave 16 x 16 x 128-channel tile
+        if (cfg.family == MF_CONV_FAMILY_F16Q) {   // the f16 + FP6 format has one kernel: the 8-wave 16 x 16 x 128-channel tile
             MF_REQUIRE(!ha.res_from_halo, "conv (f16q): residual-from-input is not built for this format");
-            if (p->out_stats) {
-                const int cpg = p->d.cout / p->out_stats_groups;
-                if (p->d.cout % p->out_stats_groups == 0 && (cpg == 4 || cpg == 8 || cpg == 16) && !ha.ws) {   // (other group widths: k_gn_stats behind the conv)
-                    ha.gn_out = p->out_stats; ha.gn_out_cpg = cpg; ha.gn_out_groups = p->out_stats_groups;
-                    *stats_done = true;
-                }
+            if (cfg.stats == MF_CONV_STATS_EPILOGUE) {   // (other group widths: k_gn_stats behind the conv)
+                ha.gn_out = p->out_stats; ha.gn_out_cpg = p->d.cout / p->out_stats_groups; ha.gn_out_groups = p->out_stats_groups;
+                *stats_done = true;
             }
             ha.wide_store = out.coff % 8 == 0 && ob.C % 8 == 0 && p->d.cout % 32 == 0;   // 16-byte epilogue stores (lane pairs exchange halves)
             const HaloTile qtile{16, 128, 4, 2};
             // A map too small to give every CU a 16 x 16 patch (the VAE's 512-channel 32 x 32 levels at batch 8: 32 patches x 4 channel tiles): the
             // channel slices split over blockIdx.y, fp32 partial tiles combined by k_splitk_epilogue[_stats] -- as the bf16x3 256-channel tile does.
-            const int ns = mf_q_split_count(p, batch);
+            const int ns = cfg.tile.nsplit;
             if (ns > 1) {
                 const int64_t per_split = (int64_t)batch * p->out_h * p->out_w * p->d.cout;
                 const int64_t need = per_split * ns;
@@ -1929,13 +2033,13 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
             }
             return mf_halo_w_launch(ha, qtile, true, stream);
         }
-        if (tw.ph) return mf_halo_w_launch(ha, tw, x3, stream);
+        if (cfg.family == MF_CONV_FAMILY_HALO_W) return mf_halo_w_launch(ha, HaloTile{cfg.tile.bm, cfg.tile.bn, cfg.tile.wgm, cfg.tile.wgn}, x3, stream);
         // Wide layer on a map too small to give every CU a 16 x 16 patch (the VAE's 512-channel 32 x 32 levels at batch 8: 64 patches x
         // channel tiles): the 256-channel tile with the channel slices split over blockIdx.y, fp32 partials combined by
         // k_splitk_epilogue -- the same two-pass scheme as the implicit GEMM's split-K, with half its L2 -> LDS bytes.  MF_HALO_SPLIT=0: off.
         {
-            const int ns = mf_halo_split_count(p, batch);
-            if (ns) {
+            const int ns = cfg.tile.nsplit;
+            if (cfg.family == MF_CONV_FAMILY_HALO_W_SPLIT) {
                 const int64_t per_split = (int64_t)batch * p->out_h * p->out_w * p->d.cout;
                 const int64_t need = per_split * ns;
                 if (need > p->ws_cap) {
@@ -1967,17 +2071,17 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
                 return MF_OK;
             }
         }
-        if (p->alt) {                          // wide layer, too few patches for the fat tiles at this batch: implicit GEMM
+        if (cfg.family == MF_CONV_FAMILY_TWIN) {   // wide layer, too few patches for the fat tiles at this batch: implicit GEMM
             p->alt->prof_mid = p->prof_mid;
             p->alt->out_stats = p->out_stats; p->alt->out_stats_groups = p->out_stats_groups;
             const int rc = conv_launch_impl(p->alt, in, out, res, batch, stream, 0, stats_done);
             p->alt->prof_mid = nullptr;
             return rc;
         }
-        return mf_halo_launch(ha, mf_halo_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin), x3, stream);
+        return mf_halo_launch(ha, HaloTile{cfg.tile.bm, cfg.tile.bn, cfg.tile.wgm, cfg.tile.wgn}, x3, stream);
     }
 
-    if (p->up_hi && p->q) {
+    if (cfg.family == MF_CONV_FAMILY_F16Q) {
         // upsample + 3x3 in the f16 + FP6 format: four launches of the 16 x 16 x 128-channel tile, phase (py, px) writes output pixels (2i + py, 2j + px)
         MF_REQUIRE(ib.halo >= 1 && !res.buf, "conv (f16q): upsample path needs an input halo and no residual");
         HaloArgs ha{};
@@ -1989,12 +2093,9 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
         ha.yb = ob.per_batch(); ha.yi = 2 * ob.Wp() * ob.C; ha.yj = 2 * ob.C;
         ha.act = p->d.act;
         ha.wide_store = out.coff % 8 == 0 && ob.C % 8 == 0 && p->d.cout % 32 == 0;
-        if (p->out_stats) {
-            const int cpg = p->d.cout / p->out_stats_groups;
-            if (p->d.cout % p->out_stats_groups == 0 && (cpg == 4 || cpg == 8 || cpg == 16)) {
-                ha.gn_out = p->out_stats; ha.gn_out_cpg = cpg; ha.gn_out_groups = p->out_stats_groups;    // every phase adds its quarter of the pixels
-                *stats_done = true;
-            }
+        if (cfg.stats == MF_CONV_STATS_EPILOGUE) {
+            ha.gn_out = p->out_stats; ha.gn_out_cpg = p->d.cout / p->out_stats_groups; ha.gn_out_groups = p->out_stats_groups;    // every phase adds its quarter of the pixels
+            *stats_done = true;
         }
         const int64_t per_phase = (int64_t)p->n_slices * 4 * p->Npad * 32;
         for (int ph = 0; ph < 4; ++ph) {
@@ -2047,26 +2148,8 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
         goff_max = std::max(goff_max, p->ph[ph].ngroups);
     }
 
-    ConvTile tc = mf_conv_pick_tile(p, batch);
-    a.ld = -1;
-    {
-        auto it = p->tuned.find(batch);
-        if (it != p->tuned.end()) a.ld = it->second.ld;
-        static const int force_ld = [] { const char* e = getenv("MF_FORCE_LD"); return e ? atoi(e) : -1; }();   // (measurement, with MF_FORCE_TILE / MF_FORCE_SPLIT)
-        if (force_ld >= 0 && !(force_ld >= 3 && (!x3 || p->q || tc.wgm * tc.wgn != 4 || tc.bn < 64 || tc.bm < 64))) a.ld = force_ld;
-    }
-    if (tokens > 0) {
-        // the cost model priced the full sequence: re-balance the split for the rows actually computed
-        const int nt = cdiv(a.M, tc.bm) * cdiv(a.N, tc.bn);
-        int kt_min = p->ph[0].KT;
-        tc.nsplit = nt >= 256 ? 1 : std::max(1, std::min(std::min(kt_min, cdiv(512, nt)), 16));
-        if (tc.bm > 128 && a.M <= 256) { tc.bm = 64; tc.bn = 64; tc.wgm = 2; tc.wgn = 2; }
-        if (p->d.act == 5 && tc.bn < 32) tc.nsplit = 1;
-    }
-    // the split-K partials ([split][B][Ho][Wo][N], unpadded rows) are written and combined in float4 channel quads: with a cout that is not a multiple
-    // of 4 the last quad of a row would overwrite the next pixel's first channels (and run past the workspace at the last one), and the combine would
-    // drop the row's last channels.  Such a layer takes the single-pass epilogue.
-    if (a.N % 4) tc.nsplit = 1;
+    const ConvTile tc = cfg.tile;            // tile, split and operand path as mf_conv_resolve settled them
+    a.ld = cfg.ld;
     a.tiles_m = cdiv(a.M, tc.bm); a.tiles_n = cdiv(a.N, tc.bn);
     {
         // XCD tile order by which operand is heavier: weights N x K vs the input tensor M x Cin (both x planes)
@@ -2097,8 +2180,8 @@ static int conv_launch_impl(ConvPlan* p, const ActView& in, const ActView& out, 
     }
     if (p->out_stats && p->d.act != 5 && p->d.cout % p->out_stats_groups == 0 && p->out_stats_groups <= 64 && tokens == 0) {
         a.gn_out_cpg = p->d.cout / p->out_stats_groups; a.gn_out_groups = p->out_stats_groups;
-        // in the epilogue: 4-wave tiles (k_conv_igemm's ST) whose pixel tile lies inside one sample; split-K layers: in the combine pass below
-        if (tc.nsplit == 1 && tc.wgm * tc.wgn == 4 && tc.bm * tc.bn < 128 * 128 && a.HqWq % tc.bm == 0) { a.gn_out = p->out_stats; *stats_done = true; }
+        // in the epilogue (mf_conv_resolve: 4-wave tiles whose pixel tile lies inside one sample); split-K layers: in the combine pass below
+        if (cfg.stats == MF_CONV_STATS_EPILOGUE) { a.gn_out = p->out_stats; *stats_done = true; }
     }
     int rc = MF_ERR_INVALID;
 #define MF_CASE(BM, BN, WGM, WGN)                                                          \
@@ -2286,13 +2369,13 @@ std::map<std::string, ConvTuned>& tune_cache() {
         auto valid = [](const std::string& k, const ConvTuned& c) {
             if (k.rfind("g950k4:", 0) != 0) return false;
             if (c.tile.bm == 0) return true;                                          // "the cost model's pick stays"
-            static const int tiles[][4] = {{64, 64, 2, 2}, {128, 64, 2, 2}, {128, 128, 2, 2}, {256, 128, 4, 2}, {256, 256, 2, 4}, {128, 80, 4, 1}};
-            bool tile_ok = false;
-            for (const auto& t : tiles) tile_ok |= c.tile.bm == t[0] && c.tile.bn == t[1] && c.tile.wgm == t[2] && c.tile.wgn == t[3];
-            if ((c.ld == 3 || c.ld == 4) && c.tile.wgm * c.tile.wgn != 4) return false;
-            if (c.tile.bn == 80 && c.ld != 3 && c.ld != 4) return false;                // (the 128 x 80 tile: producer-wave kernels only)
-            // ld 3 / 4 (round 5's producer-wave path) are additions to generation k4: every older entry still names a kernel this library has
-            return tile_ok && c.tile.nsplit >= 1 && c.tile.nsplit <= 16 && (c.ld == -1 || c.ld == 0 || c.ld == 2 || c.ld == 3 || c.ld == 4);
+            // a compiled tile, a split of 1 .. 16, an operand path that exists and that the tile runs -- in the key's precision (the producer-wave kernels,
+            // hence ld 3 / 4 and the 128 x 80 tile, are bf16x3 only) and with the key's activation (no 128 x 80 GEGLU).  ld 3 / 4 (round 5's producer-wave path) are additions to generation k4: every older
+            // entry still names a kernel this library has
+            int f[14] = {0};   // precision, batch, cin, cout, kh, kw, stride_h, stride_w, pad_h, pad_w, transposed, output_padding, residual, act
+            if (sscanf(k.c_str() + 7, "%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d", f, f + 1, f + 2, f + 3, f + 4, f + 5, f + 6, f + 7, f + 8, f + 9, f + 10, f + 11,
+                       f + 12, f + 13) != 14) return false;
+            return mf_conv_tuned_valid(c, f[0], f[13]);
         };
         int dropped = 0;
         if (FILE* f = path.empty() ? nullptr : fopen(path.c_str(), "r")) {
@@ -2325,6 +2408,12 @@ bool tunable_layer(const ConvPlan* p, int batch) {
     const int M = batch * p->Hq * p->Wq, N = p->d.cout;
     return !(N <= 32 || (M <= 16 && p->d.act != 5 && !p->q));                         // the narrow special tiles have no alternatives
 }
+ConvTuned split_clamped(const ConvPlan* p, ConvTuned c) {
+    int kt_min = p->ph[0].KT;
+    for (int ph = 0; ph < p->nphase; ++ph) kt_min = std::min(kt_min, p->ph[ph].KT);
+    c.tile.nsplit = std::max(1, std::min(c.tile.nsplit, kt_min));                     // (a split deeper than the layer's K tiles cannot launch)
+    return c;
+}
 std::string tune_key(const ConvPlan* p, const ActView& in, int batch) {
     char keybuf[256];
     snprintf(keybuf, sizeof(keybuf), "g950k4:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d", p->precision, batch, p->d.cin, p->d.cout, p->d.kh, p->d.kw, p->d.stride_h, p->d.stride_w,
@@ -2349,14 +2438,20 @@ int mf_conv_tune_lookup(ConvPlan* p, const ActView& in, int batch) {
     if (!tunable_layer(p, batch)) return 0;
     auto it = tune_cache().find(tune_key(p, in, batch));
     if (it == tune_cache().end()) return 0;
-    if (it->second.tile.bm > 0) {
-        ConvTuned c = it->second;
-        int kt_min = p->ph[0].KT;
-        for (int ph = 0; ph < p->nphase; ++ph) kt_min = std::min(kt_min, p->ph[ph].KT);
-        c.tile.nsplit = std::max(1, std::min(c.tile.nsplit, kt_min));                 // (a split deeper than the layer's K tiles cannot launch)
-        p->tuned[batch] = c;
-    } else p->tuned.erase(batch);
+    if (it->second.tile.bm > 0) p->tuned[batch] = split_clamped(p, it->second);
+    else p->tuned.erase(batch);
     return 1;
+}
+
+int mf_conv_pin(ConvPlan* p, int batch, const ConvTuned& c) {
+    if (p->halo && p->alt && !p->q) return mf_conv_pin(p->alt, batch, c);          // (as mf_conv_tune_lookup: the wide halo layer's twin takes the entry)
+    if (c.tile.bm == 0) { p->tuned.erase(batch); return MF_OK; }
+    MF_REQUIRE(!p->halo && !p->up_hi, "conv: this layer runs on a halo-tile or thin kernel: the tuning table does not serve it");
+    MF_REQUIRE(tunable_layer(p, batch), "conv: at batch %d this layer runs a narrow special tile (cout <= 32, or <= 16 pixels; or MF_FORCE_* is set): "
+               "the tuning table does not serve it", batch);
+    if (!mf_conv_tuned_valid(c, p->precision, p->d.act)) return MF_ERR_INVALID;
+    p->tuned[batch] = split_clamped(p, c);
+    return MF_OK;
 }
 
 int mf_conv_tune(ConvPlan* p, const ActView& in, const ActView& out, const ActView& res, int batch, hipStream_t stream) {
@@ -2467,41 +2562,37 @@ int mf_conv_tune(ConvPlan* p, const ActView& in, const ActView& out, const ActVi
 
 void mf_conv_kernel_name(const ConvPlan* p, int batch, char* buf, int cap) {
     const char* x3 = p->precision != MF_PREC_BF16 ? "true" : "false";
+    ConvLaunchCfg c;
+    if (mf_conv_resolve(p, batch, 0, 0, &c)) { snprintf(buf, cap, "(no kernel: %s)", mf_last_error()); return; }
+    const ConvTile& t = c.tile;
     // (the f16 + FP6 tile: the specialised workgroup <16,128,2,2,...> -- 4 compute + 4 producer waves)
     const char* qt = "2,2";
-    if (p->q && p->up_hi) { snprintf(buf, cap, "4 x k_conv3x3_halo_w<16,128,%s,true,1,phase> f16+fp6", qt); return; }
-    if (p->q && p->halo) {
-        // (" grid N": the launch's thread count as rocprofv3 reports it, so that a counter pass can be matched to exactly these launches -- the split
-        // and unsplit launches share one kernel symbol)
-        const int ns = mf_q_split_count(p, batch);
-        const long grid = (long)batch * cdiv(p->out_h, 16) * cdiv(p->out_w, 16) * cdiv(p->d.cout, 128) * ns * 512;
-        if (ns > 1) snprintf(buf, cap, "k_conv3x3_halo_w<16,128,%s,true,1> f16+fp6 split %d grid %ld", qt, ns, grid);
-        else snprintf(buf, cap, "k_conv3x3_halo_w<16,128,%s,true,1> f16+fp6 grid %ld", qt, grid);
+    switch (c.family) {
+    case MF_CONV_FAMILY_F16Q:
+        if (p->up_hi) { snprintf(buf, cap, "4 x k_conv3x3_halo_w<16,128,%s,true,1,phase> f16+fp6", qt); return; }
+        {
+            // (" grid N": the launch's thread count as rocprofv3 reports it, so that a counter pass can be matched to exactly these launches -- the split
+            // and unsplit launches share one kernel symbol)
+            const long grid = (long)batch * cdiv(p->out_h, 16) * cdiv(p->out_w, 16) * cdiv(p->d.cout, 128) * t.nsplit * 512;
+            if (t.nsplit > 1) snprintf(buf, cap, "k_conv3x3_halo_w<16,128,%s,true,1> f16+fp6 split %d grid %ld", qt, t.nsplit, grid);
+            else snprintf(buf, cap, "k_conv3x3_halo_w<16,128,%s,true,1> f16+fp6 grid %ld", qt, grid);
+        }
         return;
-    }
-    if (p->thin) {
+    case MF_CONV_FAMILY_THIN:
         snprintf(buf, cap, "k_conv_thin<%d,%d,%d,%d,%s>", p->d.kh, p->d.stride_h, p->d.cin <= 8 ? 8 : 16, (p->d.cout + 15) / 16, x3);
         return;
-    }
-    if (p->halo) {
-        const HaloTile tw = mf_halo_w_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin);
-        if (!tw.ph && mf_halo_split_count(p, batch)) {
-            snprintf(buf, cap, "k_conv3x3_halo_w<16,256,2,4,%s,1> split %d", x3, mf_halo_split_count(p, batch));
-            return;
-        }
-        if (!tw.ph && p->alt) { mf_conv_kernel_name(p->alt, batch, buf, cap); return; }
-        const HaloTile t = tw.ph ? tw : mf_halo_pick_tile(p->out_h, p->out_w, p->d.cout, batch, p->d.cin);
+    case MF_CONV_FAMILY_HALO_W_SPLIT:
+        snprintf(buf, cap, "k_conv3x3_halo_w<16,256,2,4,%s,1> split %d", x3, t.nsplit);
+        return;
+    case MF_CONV_FAMILY_HALO_W:
+    case MF_CONV_FAMILY_HALO:
         // last template argument: halo stages (register-weights kernel) / taps per weight-ring slot (LDS-weights kernel)
-        snprintf(buf, cap, "k_conv3x3_halo%s<%d,%d,%d,%d,%s,%d>", tw.ph ? "_w" : "", t.ph, t.bn, t.wgm, t.wgn, x3, tw.ph ? (t.bn >= 128 ? 1 : 3) : 2);
-    } else {
-        const ConvTile t = mf_conv_pick_tile(p, batch);
-        // tile depth as launch_prec picks it: 64 everywhere except the 8-wave bf16x3 tiles
-        const bool x3b = p->precision == MF_PREC_BF16X3;
-        const int bk = ((x3b && t.bm + t.bn > 128 && t.wgm * t.wgn != 4) || (p->q && t.wgm * t.wgn != 4)) ? 32 : 64;
-        int ld = -1;
-        { auto it = p->tuned.find(batch); if (it != p->tuned.end()) ld = it->second.ld; }
-        if (ld >= 3) snprintf(buf, cap, "k_conv_igemm<%d,%d,%d,%d,%s,%d,pw>", t.bm, t.bn, t.wgm, t.wgn, x3, ld == 3 ? 64 : 32);   // pw: producer waves
-        else snprintf(buf, cap, "k_conv_igemm<%d,%d,%d,%d,%s,%d>%s", t.bm, t.bn, t.wgm, t.wgn, x3, bk, p->q ? " f16+fp6" : "");
+        snprintf(buf, cap, "k_conv3x3_halo%s<%d,%d,%d,%d,%s,%d>", c.family == MF_CONV_FAMILY_HALO_W ? "_w" : "", t.bm, t.bn, t.wgm, t.wgn, x3,
+                 c.family == MF_CONV_FAMILY_HALO_W ? (t.bn >= 128 ? 1 : 3) : 2);
+        return;
+    default:   // implicit GEMM, or a wide halo plan's twin
+        if (c.ld >= 3) snprintf(buf, cap, "k_conv_igemm<%d,%d,%d,%d,%s,%d,pw>", t.bm, t.bn, t.wgm, t.wgn, x3, c.bk);   // pw: producer waves
+        else snprintf(buf, cap, "k_conv_igemm<%d,%d,%d,%d,%s,%d>%s", t.bm, t.bn, t.wgm, t.wgn, x3, c.bk, p->q ? " f16+fp6" : "");
     }
 }
 

@@ -114,3 +114,19 @@ extern "C" int mf_conv2d_out_shape(const mf_conv2d* h, int* out_h, int* out_w) {
 }
 
 extern "C" void mf_conv2d_destroy(mf_conv2d* h) { delete h; }
+
+// Test seam of the launch selection: what mf_conv2d_forward[_stats] at this batch launches, resolved by mf_conv_resolve -- the function conv_launch_impl
+// itself launches from -- and the configuration pinned into the slot the tuning table fills (mf_conv_pin: the table's own rules and split clamp).
+extern "C" int mf_conv2d_launch_config(const mf_conv2d* h, int batch, int stats_groups, int* info, int n) {
+    MF_REQUIRE(h && info && n >= 11 && batch > 0 && stats_groups >= 0, "conv2d_launch_config: needs a handle, batch > 0, stats_groups >= 0 and room for 11 ints");
+    ConvLaunchCfg c;
+    if (const int rc = mf_conv_resolve(&h->plan, batch, 0, stats_groups, &c)) return rc;
+    const int v[11] = {c.family, c.tile.bm, c.tile.bn, c.tile.wgm, c.tile.wgn, c.tile.nsplit, c.ld, c.bk, c.nphase, c.stats, c.pinned ? 1 : 0};
+    std::copy(v, v + 11, info);
+    return MF_OK;
+}
+
+extern "C" int mf_conv2d_pin_config(mf_conv2d* h, int batch, int bm, int bn, int wgm, int wgn, int nsplit, int ld) {
+    MF_REQUIRE(h && batch > 0, "conv2d_pin_config: null handle or batch <= 0");
+    return mf_conv_pin(&h->plan, batch, ConvTuned{ConvTile{bm, bn, wgm, wgn, nsplit}, ld});
+}

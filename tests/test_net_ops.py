@@ -18,12 +18,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_numerics import F32, U, bf16_rne, bn_fold, exact, stored  # noqa: F401
+
 PRECS = ["bf16x3", "bf16"]
-# relative rounding of one stored value.  bf16 keeps 8 significant bits: RNE is within half a spacing, 2^-8 |x| (reached just above a
-# power of two).  hi + lo: the residual x - hi is at most half of hi's spacing, 2^(e-8) for x in [2^e, 2^(e+1)), and the lo plane rounds it
-# to 8 bits, within 2^(e-17) <= 2^-17 |x|.  test_stored_matches_the_format_rounding checks both.
-U = {"bf16x3": 2.0 ** -17, "bf16": 2.0 ** -8}
-F32 = 2.0 ** -24                      # fp32 unit roundoff: every op computes in fp32 between a load and a store
 SENT = -8192.0                        # pre-fill of output buffers (exact in both formats)
 BIG = 2.0 ** 20                       # neighbours of an input slice (exact in both formats)
 
@@ -32,30 +29,7 @@ def pad8(c):
     return (c + 7) // 8 * 8
 
 
-# ---- storage-format emulation (CPU) ----------------------------------------------------------------------------------------------------------
-def bf16_rne(x):
-    """fp32 -> bf16 -> fp32, round to nearest even: Pl::st's nfb() and the hardware conversion of k_nchw_to_act (finite inputs)"""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def stored(x, prec):
-    """what a buffer gives back for fp32 x: hi = rne(x), lo = rne(x - hi) in fp32 (bf16x3), read as hi + lo in fp32"""
-    x = np.asarray(x, np.float32)
-    hi = bf16_rne(x)
-    if prec == "bf16":
-        return hi
-    lo = bf16_rne(x - hi)
-    return hi + lo
-
-
-def exact(rng, shape, prec, scale=1.0, offset=0.0):
-    """random values the storage format holds exactly: stored() of an fp32 draw (hi + lo needs <= 17 significant bits, so it is an fp32 sum
-    without rounding, and storing it again splits it into the same value)"""
-    return stored((offset + scale * rng.standard_normal(shape)).astype(np.float32), prec)
-
-
+# ---- storage-format emulation (CPU): U, F32, bf16_rne, stored, exact, bn_fold live in conv_numerics.py, shared with test_conv_configs.py --------------
 def test_exact_inputs_survive_storage():
     rng = np.random.default_rng(0)
     for prec in PRECS:
@@ -91,12 +65,6 @@ def l2norm_ref(x, w, eps):
     x = torch.as_tensor(x, dtype=torch.float64)
     norm = x.pow(2).sum(dim=1, keepdim=True).sqrt() + eps
     return x / norm * torch.as_tensor(w, dtype=torch.float64).view(1, -1, 1, 1)
-
-
-def bn_fold(w, b, gamma, beta, mean, var, eps=1e-5):
-    """eval-mode BatchNorm2d after a conv, as one conv: (w', b')"""
-    sc = gamma / np.sqrt(var + eps)
-    return w * sc.reshape(-1, 1, 1, 1), (b - mean) * sc + beta
 
 
 def test_l2norm_ref_is_the_oracle():

@@ -20,6 +20,7 @@ KEY_FIELDS = ("precision", "batch", "cin", "cout", "kh", "kw", "stride_h", "stri
               "act", "in_h", "in_w", "upsample", "pad_hi", "in_c")
 LINE_RE = re.compile(r"(g950k4((?::-?\d+){%d})(?::s)?) (-?\d+) (-?\d+) (-?\d+) (-?\d+) (-?\d+) (-?\d+)" % len(KEY_FIELDS))
 PRECISION_NAMES = {0: "bf16", 1: "bf16x3"}                 # MF_PREC_BF16, MF_PREC_BF16X3 (include/merefusion.h)
+PRECISION_IDS = {v: k for k, v in PRECISION_NAMES.items()}
 
 # The loader's validity rules (mf_conv.hip, `valid` in tune_cache()).  KEEP IN SYNC with that lambda: a tile or operand path added there is added here.
 TILES = {(64, 64, 2, 2), (128, 64, 2, 2), (128, 128, 2, 2), (256, 128, 4, 2), (256, 256, 2, 4), (128, 80, 4, 1)}   # (bm, bn, wgm, wgn)
@@ -48,8 +49,9 @@ def parse(lines):
     return rows, problems
 
 
-def loader_rejects(cfg):
-    """The reason mf_conv.hip's loader would drop this configuration, or None.  (KEEP IN SYNC with `valid` in tune_cache().)"""
+def loader_rejects(cfg, precision=1, act=0):
+    """The reason mf_conv.hip's loader would drop this configuration of a key with this precision and activation, or None.  (KEEP IN SYNC with `valid` in
+    tune_cache() and mf_conv_tuned_valid().)"""
     bm, bn, wgm, wgn, nsplit, ld = cfg
     if bm == 0:
         return None                                          # "the cost model's pick stays"
@@ -63,11 +65,15 @@ def loader_rejects(cfg):
         return f"split {nsplit} outside 1 .. 16"
     if ld not in LD_PATHS:
         return f"operand path ld {ld} does not exist"
+    if (ld in (3, 4) or bn == 80) and precision != PRECISION_IDS["bf16x3"]:
+        return "the producer-wave kernels (ld 3 / 4, the 128 x 80 tile) are bf16x3 only"
+    if bn == 80 and act == 5:
+        return "the 128 x 80 tile cannot pair GEGLU value / gate fragments"
     return None
 
 
 def invalid_rows(rows):
-    return [f"line {n}: {k}: {why}" for n, k, _, cfg in rows if (why := loader_rejects(cfg))]
+    return [f"line {n}: {k}: {why}" for n, k, f, cfg in rows if (why := loader_rejects(cfg, f["precision"], f["act"]))]
 
 
 def duplicate_keys(rows):
@@ -187,6 +193,15 @@ def _mutate(lines, kind):
         out[tuned] = _set_cfg(out[tuned], (256, 128, 4, 2, 1, 3))
     elif kind == "80_wide_tile_off_producer_path":
         out[tuned] = _set_cfg(out[tuned], (128, 80, 4, 1, 1, 2))
+    elif kind == "producer_path_on_bf16_key":         # the bf16 library has no producer-wave kernel: the launch would fail
+        i = _first(out, lambda l: l.split(":")[1] == "0" and not l.endswith(" 0 0 0 0 0 -1"))
+        out[i] = _set_cfg(out[i], (128, 64, 2, 2, 1, 3))
+    elif kind == "80_wide_tile_on_bf16_key":
+        i = _first(out, lambda l: l.split(":")[1] == "0" and not l.endswith(" 0 0 0 0 0 -1"))
+        out[i] = _set_cfg(out[i], (128, 80, 4, 1, 1, 4))
+    elif kind == "80_wide_tile_on_geglu_key":
+        i = _first(out, lambda l: l.split(":")[1] == "1" and l.split(" ")[0].split(":")[14] == "5")
+        out[i] = _set_cfg(out[i], (128, 80, 4, 1, 1, 3))
     elif kind == "batch_outside_grid":
         out[mid] = _replace_field(out[mid], "batch", 7)
     elif kind == "grid_batch_missing":                # every row of Wav2Lip bf16 batch 128 gone
@@ -205,7 +220,8 @@ def _mutate(lines, kind):
 MUTATIONS = {                                         # mutation -> the checker that must catch it
     "truncated_line": "parse", "truncated_key": "parse", "unknown_suffix": "parse",
     "invalid_tile": "valid", "split_out_of_range": "valid", "unknown_ld": "valid", "producer_path_on_8_wave_tile": "valid",
-    "80_wide_tile_off_producer_path": "valid",
+    "80_wide_tile_off_producer_path": "valid", "producer_path_on_bf16_key": "valid", "80_wide_tile_on_bf16_key": "valid",
+    "80_wide_tile_on_geglu_key": "valid",
     "batch_outside_grid": "grid", "grid_batch_missing": "grid",
     "duplicate_key": "duplicates",
     "unknown_map_size": "classify",
@@ -231,4 +247,6 @@ def test_loader_rules_accept_the_compiled_tiles():
         for ld in lds:
             for split in (1, 16):
                 assert loader_rejects((bm, bn, wgm, wgn, split, ld)) is None, (bm, bn, wgm, wgn, split, ld)
+                if bn != 80 and ld not in (3, 4):          # bf16 keys: everything but the producer-wave kernels
+                    assert loader_rejects((bm, bn, wgm, wgn, split, ld), PRECISION_IDS["bf16"], 5) is None, (bm, bn, wgm, wgn, split, ld)
     assert loader_rejects((0, 0, 0, 0, 0, -1)) is None
