@@ -547,6 +547,24 @@ int mf_net_get_output(mf_net* h, int buf, int coff, int C, float* nchw, int batc
 int mf_net_get_output_bilinear(mf_net* h, int buf, int coff, int C, float* nchw, int H, int W, int batch, void* stream);
 /* "max-out background label" of net_s3fd.py:123-126: device fp32 [batch][4][hw] -> [batch][2][hw] = (max(c0, c1, c2), c3) */
 int mf_s3fd_maxout_bg(const float* cls4, float* cls2, int batch, int hw, void* stream);
+/* uint8 [batch][H][W][3] device frames -> an input buffer of 3 channels: channel c = (float)img[..][reverse_channels ? 2 - c : c] - mean3[c] (host floats).  The
+ * `imgs - np.array([104, 117, 123])` of sfd/detect.py:59-60 and the `images[..., ::-1]` of face_detection/api.py:65 in one pass; bit-equal to mf_net_set_input of the
+ * same values as fp32 (they are exact integers). */
+int mf_net_set_input_u8(mf_net* h, int buf, const uint8_t* u8_nhwc, const float* mean3, int reverse_channels, int batch, void* stream);
+/* S3FD's post-process on the device (sfd/detect.py:58-94 batch_detect, bbox.py:111-129 batch_decode, bbox.py:44-64 nms, sfd_detector.py:41-47): after mf_net_run,
+ * reads the six 8-channel head buffers (conf in channels 0..3, loc in 4..7; level 1's max-out background fused) in place.  Per image: candidates with softmax face
+ * probability > cand_thresh are decoded and appended (at most max_candidates <= 4096 stored; n_candidates[b] counts them all, so n_candidates[b] > max_candidates
+ * reports an overflow), sorted by (score descending, (level, row, column) ascending), greedy NMS with `ovr > nms_thresh` suppression, and the kept boxes with score >
+ * final_thresh written in keep order as boxes[b][i] = (x1, y1, x2, y2, score), i < min(counts[b], max_det); counts[b] counts every kept box.  The reference's values are
+ * 0.05 / 0.3 / 0.5; cand_thresh = final_thresh gives the identical boxes from shorter lists (mf_s3fd_detect.hip says why).  boxes: device fp32 [batch][max_det][5];
+ * counts, n_candidates: device int32 [batch].  Nothing synchronises with the host. */
+int mf_s3fd_detect(mf_net* net, const int* head_bufs, int batch, float cand_thresh, float nms_thresh, float final_thresh, int max_candidates, int max_det, float* boxes,
+                   int* counts, int* n_candidates, void* stream);
+/* The same on the twelve tensors s3fd.__call__ returns: heads[2 * l] = cls [batch][2][h][w] (level 1 already maxed out), heads[2 * l + 1] = reg [batch][4][h][w], device
+ * fp32; map_hw[2 * l], map_hw[2 * l + 1] = h, w of level l + 1 (host).  workspace: device memory of mf_s3fd_detect_workspace_bytes(batch, max_candidates) bytes. */
+int mf_s3fd_detect_tensors(const float* const* heads, const int* map_hw, int batch, float cand_thresh, float nms_thresh, float final_thresh, int max_candidates, int max_det,
+                           void* workspace, float* boxes, int* counts, int* n_candidates, void* stream);
+size_t mf_s3fd_detect_workspace_bytes(int batch, int max_candidates);
 void mf_net_destroy(mf_net* h);
 
 /* ---- measurement seam --------------------------------------------------------------------------------------------- */

@@ -84,6 +84,16 @@ class Net:
             _lib.check(_lib.lib().mf_net_set_input(self._h, buf, _p(x), Cn, B, self._stream()), "net_set_input")
         return B
 
+    def set_input_u8(self, buf, x, mean, reverse_channels=False):
+        """uint8 device frames [B, H, W, 3] -> a 3-channel input buffer: channel c = frame[..., 2 - c if reverse_channels else c] - mean[c]"""
+        x = x.to(self.device).contiguous()
+        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or tuple(x.shape[1:3]) != self.shape[buf][1:]:
+            raise ValueError(f"set_input_u8: uint8 [B, {self.shape[buf][1]}, {self.shape[buf][2]}, 3] expected, got {x.dtype} {tuple(x.shape)}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mf_net_set_input_u8(self._h, buf, _p(x), (C.c_float * 3)(*[float(m) for m in mean]), int(bool(reverse_channels)), x.shape[0],
+                                                      self._stream()), "net_set_input_u8")
+        return x.shape[0]
+
     def run(self, batch):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mf_net_run(self._h, batch, self._stream()), "net_run")

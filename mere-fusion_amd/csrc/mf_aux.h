@@ -35,3 +35,9 @@ int mf_nchw_to_act_q(const float* src, int C, const ActBuf& dst, int batch, hipS
 // (sample, group), gamma and beta (the values mf_groupnorm_affine would have written, bit for bit): no k_gn_affine launch in front
 int mf_affine_silu_to_act_q(const ActView& x, const float* scale, const float* shift, int silu, const ActBuf& dst, int batch, hipStream_t s, const float* post = nullptr,
                             const double* gn_stats = nullptr, const float* gn_gamma = nullptr, const float* gn_beta = nullptr, int gn_groups = 0, float gn_eps = 0.f);
+
+// ---- seams of the mf_net graph (mf_net.hip) for kernels that read or write its buffers in place (mf_s3fd_detect.hip) ----
+struct mf_net;
+const ActBuf* mf_net_actbuf(mf_net* h, int id);                 // null when there is no such buffer
+int mf_net_max_batch(const mf_net* h);
+int mf_net_scratch(mf_net* h, size_t bytes, void** out);        // device scratch owned by the handle (grows, never shrinks)

@@ -164,6 +164,8 @@ struct mf_net {
     hipStream_t cap_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bool use_graph = true;
+    void* scratch = nullptr;                                               // mf_net_scratch: the candidate lists of mf_s3fd_detect
+    size_t scratch_bytes = 0;
 
     ~mf_net() {
         for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
@@ -409,3 +411,19 @@ extern "C" int mf_s3fd_maxout_bg(const float* cls4, float* cls2, int batch, int 
 }
 
 extern "C" void mf_net_destroy(mf_net* h) { delete h; }
+
+// ---- seams for the kernels that read a graph's buffers in place (mf_s3fd_detect.hip) ------------------------------------------------------------------
+const ActBuf* mf_net_actbuf(mf_net* h, int id) { return h ? h->B(id) : nullptr; }
+int mf_net_max_batch(const mf_net* h) { return h ? h->cap : 0; }
+
+int mf_net_scratch(mf_net* h, size_t bytes, void** out) {
+    MF_REQUIRE(h && out && bytes > 0, "net_scratch: bad argument");
+    if (bytes > h->scratch_bytes) {                                        // grows only; the old block stays until the handle goes (a launch in flight may still read it)
+        float* p = nullptr;
+        MF_HIP(hipMalloc(&p, bytes));
+        h->dev.push_back(p);
+        h->scratch = p; h->scratch_bytes = bytes;
+    }
+    *out = h->scratch;
+    return MF_OK;
+}

@@ -1,0 +1,222 @@
+"""S3FD ending in boxes on the device: softmax / threshold / decode / NMS (csrc/mf_s3fd_detect.hip), the uint8 input, `SFDDetector` and the
+`FaceAlignment.get_detections_for_batch` counterpart (mere-fusion_amd/avatar/face_detection.py).
+
+Golden = the reference's own `batch_detect` -> `nms(., 0.3)` -> `> 0.5` (tests/golden/make_s3fd_detect_golden.py -> s3fd_detect_golden.npz): set P drives the
+post-process alone on synthetic head tensors, set E / F the whole detector on uint8 frames.  The generator asserts that the reference's numbers keep clear of every
+threshold by a margin and derives set E's bounds from the head tolerances of tests/test_avatar.py; the CPU tier re-checks those conditions on the committed file.
+
+Measured on an MI355X (bf16x3), printed by the tests:
+  set P: max coordinate error 0 ulp of the coordinate (bound 8), max score error 0 (bound 1e-6), both sizes and both threshold sequences
+  set E: max coordinate error 1.53e-5 px (derived bounds 3.46e-3 .. 3.55e-3 px), max score error 1.25e-6 (derived bound 5.01e-4)"""
+import importlib.util
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from mere_fusion_amd import weights as W
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+NEW_SYMBOLS = ["mf_net_set_input_u8", "mf_s3fd_detect", "mf_s3fd_detect_tensors", "mf_s3fd_detect_workspace_bytes"]
+LEVEL_NAMES = ["conv3_3_norm", "conv4_3_norm", "conv5_3_norm", "fc7", "conv6_2", "conv7_2"]
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(os.path.join(ROOT, "tests", "golden", "s3fd_detect_golden.npz"))
+
+
+@pytest.fixture(scope="module")
+def gen():
+    spec = importlib.util.spec_from_file_location("make_s3fd_detect_golden", os.path.join(ROOT, "tests", "golden", "make_s3fd_detect_golden.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)                      # the reference is only imported inside its main()
+    return m
+
+
+def _heads(golden, k, device="cuda"):
+    return [torch.from_numpy(golden[f"P{k}_head{i}"]).to(device) for i in range(12)]
+
+
+def _rows(boxes, counts):
+    b, c = boxes.cpu().numpy(), counts.cpu().numpy()
+    return [b[i, :c[i]] for i in range(len(c))]
+
+
+def _shifted_state_dict(golden):
+    sd = W.make_s3fd_state_dict(0)
+    for n, s in zip(LEVEL_NAMES, golden["E_bias_shift"]):
+        sd[n + "_mbox_conf.bias"] = sd[n + "_mbox_conf.bias"].clone()
+        sd[n + "_mbox_conf.bias"][-1] += float(s)
+    return sd
+
+
+# ---- CPU tier ---------------------------------------------------------------------------------------------------------------------------------------
+def test_new_symbols_in_header_exports_and_ctypes_table(lib_built):
+    import ctypes as C
+    from mere_fusion_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "merefusion.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", text))
+    lib = C.CDLL(lib_built)
+    for n in NEW_SYMBOLS:
+        assert n in declared, f"{n} is not declared in merefusion.h"
+        assert hasattr(lib, n), f"{n} is not exported"
+        assert n in _lib.SIGNATURES, f"{n} is missing from the ctypes table"
+    assert _lib.lib().mf_abi_version() == 4                                   # symbols were only added
+    assert _lib.lib().mf_s3fd_detect_workspace_bytes(3, 4096) == 3 * 4096 * 6 * 4
+    # argument checks that need no device
+    assert _lib.lib().mf_s3fd_detect(None, None, 1, 0.05, 0.3, 0.5, 64, 8, None, None, None, None) == -1
+    assert b"null" in _lib.lib().mf_last_error()
+
+
+def test_generator_conditions_hold_on_committed_golden(golden, gen):
+    assert int(golden["capacity"]) == gen.CAPACITY == 4096 and float(golden["P_m"]) == gen.P_M == 1e-5
+    assert tuple(golden["E_eps"]) == gen.E_EPS == (1e-3, 1e-3, 1e-3, 5e-3, 5e-3, 5e-3)         # the head gates of tests/test_avatar.py
+    for k in range(2):
+        cands = [golden[f"P{k}_cand{b}"] for b in range(3)]
+        gen.check_conditions(cands, golden[f"P{k}_gaps"], [gen.P_M] * 6, tag=f"P{k}")
+        assert [len(golden[f"P{k}_boxes{b}"]) for b in range(3)] == [3, 3, 0]
+        for b in range(3):                                                                        # every expected box is one of the image's candidates, above 0.5, in score order
+            bx = golden[f"P{k}_boxes{b}"]
+            assert np.all(np.isin(bx[:, 4], cands[b][:, 4])) and np.all(bx[:, 4] > 0.5) and np.all(np.diff(bx[:, 4]) < 0)
+    m_score = [e / 2 + 1e-6 for e in gen.E_EPS]
+    for tag in "EF":
+        cands = [golden[f"{tag}_cand{b}"] for b in range(4)]
+        boxes = [golden[f"{tag}_boxes{b}"] for b in range(4)]
+        gen.check_conditions(cands, golden[f"{tag}_gaps"], m_score, gen.E_EPS, tag=tag)
+        tuples, has = gen.first_box_tuples(boxes, cands, gen.E_EPS, tag)                          # asserts the int() margin
+        assert np.array_equal(tuples, golden[f"{tag}_tuples"]) and np.array_equal(has, golden[f"{tag}_has_box"])
+        assert not has[3] and has.sum() >= 2
+        for b in range(4):
+            assert len(golden[f"{tag}_coord_bound{b}"]) == len(boxes[b]) == len(golden[f"{tag}_score_bound{b}"])
+            if len(boxes[b]):
+                rows = np.concatenate([gen.match(cands[b], bx) for bx in boxes[b]])
+                np.testing.assert_array_equal(golden[f"{tag}_coord_bound{b}"], gen.coord_bound(rows, np.array([gen.E_EPS[int(l)] for l in rows[:, 5]])))
+
+
+# ---- GPU tier ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [0, 1])
+def test_postprocess_matches_reference_set_p(lib_built, golden, k):
+    from mere_fusion_amd.avatar.s3fd import check_counts, detect_from_heads
+    heads = _heads(golden, k)
+    answers = []
+    for cand_thresh in (0.05, 0.5):                                                               # the literal sequence, and candidates cut at the final threshold
+        boxes, counts, ncand = detect_from_heads(heads, cand_thresh=cand_thresh, nms_thresh=0.3, final_thresh=0.5)
+        check_counts(counts, ncand)
+        if cand_thresh == 0.05:
+            assert ncand.cpu().tolist() == [len(golden[f"P{k}_cand{b}"]) for b in range(3)]
+        got = _rows(boxes, counts)
+        ulps, serr = 0.0, 0.0
+        for b in range(3):
+            want = golden[f"P{k}_boxes{b}"]
+            assert got[b].shape == want.shape, f"image {b}: {len(got[b])} boxes, the reference has {len(want)}"
+            if len(want):
+                ulps = max(ulps, float((np.abs(got[b][:, :4].astype(np.float64) - want[:, :4]) / np.spacing(np.abs(want[:, :4]))).max()))
+                serr = max(serr, float(np.abs(got[b][:, 4].astype(np.float64) - want[:, 4]).max()))
+        print(f"[s3fd detect set P{k}, cand_thresh {cand_thresh}] max coordinate error {ulps:.1f} ulp (bound 8), max score error {serr:.2e} (bound 1e-6)")
+        assert ulps <= 8 and serr <= 1e-6
+        answers.append((boxes.cpu(), counts.cpu()))
+    assert torch.equal(answers[0][0], answers[1][0]) and torch.equal(answers[0][1], answers[1][1])   # the equivalence stated in mf_s3fd_detect.hip
+
+
+@pytest.fixture(scope="module")
+def detector(golden):
+    from mere_fusion_amd.avatar import SFDDetector
+    return SFDDetector(device="cuda", state_dict=_shifted_state_dict(golden), max_batch=4)
+
+
+@pytest.mark.gpu
+def test_detector_matches_reference_set_e(lib_built, golden, detector):
+    got = detector.detect_from_batch(golden["E_images"])
+    assert len(got) == 4
+    cerr, serr, cb, sb = 0.0, 0.0, [], []
+    for b in range(4):
+        want = golden[f"E_boxes{b}"]
+        assert len(got[b]) == len(want), f"image {b}: {len(got[b])} boxes, the reference has {len(want)}"
+        for i, row in enumerate(got[b]):
+            assert row.dtype == np.float32 and row.shape == (5,)
+            ce, se = float(np.abs(row[:4].astype(np.float64) - want[i, :4]).max()), float(abs(float(row[4]) - float(want[i, 4])))
+            cerr, serr = max(cerr, ce), max(serr, se)
+            cb.append(float(golden[f"E_coord_bound{b}"][i])); sb.append(float(golden[f"E_score_bound{b}"][i]))
+            assert ce <= cb[-1] and se <= sb[-1], (b, i, ce, se)
+    print(f"[s3fd detect set E] max coordinate error {cerr:.2e} px (derived bounds {min(cb):.2e} .. {max(cb):.2e}), max score error {serr:.2e} (derived bound {max(sb):.2e})")
+    one = detector.detect_from_image(golden["E_images"][2])
+    assert len(one) == len(got[2]) and all(np.abs(a - b).max() <= max(cb) for a, b in zip(one, got[2]))
+    assert (detector.reference_scale, detector.reference_x_shift, detector.reference_y_shift) == (195, 0, 0)
+
+
+@pytest.mark.gpu
+def test_detect_is_deterministic_and_batch_order_free(lib_built, golden):
+    from mere_fusion_amd.avatar.s3fd import detect_from_heads
+    heads = _heads(golden, 0)
+    first = [t.cpu() for t in detect_from_heads(heads)]
+    assert first[1].tolist() == [3, 3, 0]
+    for _ in range(4):
+        again = [t.cpu() for t in detect_from_heads(heads)]
+        assert all(torch.equal(a, f) for a, f in zip(again, first))
+    perm = [2, 0, 1]
+    shuffled = [t.cpu() for t in detect_from_heads([t[perm].contiguous() for t in heads])]
+    assert all(torch.equal(s, f[perm]) for s, f in zip(shuffled, first))
+
+
+@pytest.mark.gpu
+def test_candidate_overflow_raises_and_reports_the_true_count(lib_built, golden):
+    from mere_fusion_amd.avatar.s3fd import boxes_to_lists, detect_from_heads
+    heads = _heads(golden, 0, "cpu")
+    rng = np.random.default_rng(5)
+    h, w = heads[0].shape[2:]
+    heads[0][0, 0] = 0.0
+    heads[0][0, 1] = torch.from_numpy(rng.uniform(2.0, 9.0, (h, w)).astype(np.float32))          # image 0: every level-1 position is a candidate (score >= 0.88)
+    true = [int(sum((torch.softmax(heads[2 * l][b], 0)[1] > 0.05).sum() for l in range(6))) for b in range(3)]
+    assert true[0] >= h * w
+    boxes, counts, ncand = detect_from_heads([t.cuda() for t in heads], max_candidates=64, max_det=16)
+    assert ncand.cpu().tolist() == true
+    with pytest.raises(RuntimeError, match=rf"{true[0]} candidates.*max_candidates = 64"):
+        boxes_to_lists(boxes, counts, ncand, 64, 16)
+    with pytest.raises(RuntimeError, match="max_candidates 4097 outside"):                      # beyond what the kernel's workgroup can sort: refused before any launch
+        detect_from_heads([t.cuda() for t in heads], max_candidates=4097)
+    boxes, counts, ncand = detect_from_heads([t.cuda() for t in heads], max_candidates=4096, max_det=2)    # the box capacity is reported the same way
+    with pytest.raises(RuntimeError, match=r"keeps \d+ boxes.*max_det = 2"):
+        boxes_to_lists(boxes, counts, ncand, 4096, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
+def test_u8_input_bit_equal_to_float_input(lib_built, precision):
+    from mere_fusion_amd.avatar.net import Net
+    B, H, Wd = 3, 37, 51
+    img = np.random.default_rng(3).integers(0, 256, (B, H, Wd, 3), dtype=np.uint8)
+    img[0, 0, 0], img[0, 0, 1] = (0, 0, 0), (255, 255, 255)
+    mean = (104.0, 117.0, 123.0)
+    n = Net(B, precision)
+    buf = n.buffer(3, H, Wd, 1)
+    for reverse in (False, True):
+        src = img[..., ::-1] if reverse else img
+        x = torch.from_numpy((src - np.array(mean)).transpose(0, 3, 1, 2).copy()).float()
+        n.set_input(buf, x)
+        want = n.output(buf, 8, B).cpu()
+        n.set_input(buf, torch.zeros_like(x))
+        n.set_input_u8(buf, torch.from_numpy(img).cuda(), mean, reverse)
+        got = n.output(buf, 8, B).cpu()
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), f"reverse_channels={reverse}"
+        if precision == "bf16x3":
+            assert torch.equal(got[:, :3], x)                                                     # small integers: exact in the (hi, lo) planes
+        assert not got[:, 3:].any()
+
+
+@pytest.mark.gpu
+def test_get_detections_for_batch_matches_reference(lib_built, golden, detector):
+    from mere_fusion_amd.avatar import FaceAlignment, LandmarksType
+    fa = FaceAlignment.__new__(FaceAlignment)                                                     # the same detector object: one graph for the module
+    fa.face_detector = detector
+    got = fa.get_detections_for_batch(golden["E_images"])
+    assert got[3] is None                                                                         # the flat image
+    for b in range(4):
+        if golden["F_has_box"][b]:
+            assert got[b] == tuple(int(v) for v in golden["F_tuples"][b]) and all(type(v) is int for v in got[b])
+        else:
+            assert got[b] is None
+    assert LandmarksType._2D.value == 1
