@@ -565,6 +565,28 @@ int mf_s3fd_detect(mf_net* net, const int* head_bufs, int batch, float cand_thre
 int mf_s3fd_detect_tensors(const float* const* heads, const int* map_hw, int batch, float cand_thresh, float nms_thresh, float final_thresh, int max_candidates, int max_det,
                            void* workspace, float* boxes, int* counts, int* n_candidates, void* stream);
 size_t mf_s3fd_detect_workspace_bytes(int batch, int max_candidates);
+/* MuseTalk's blend masks on the device (mf_face_mask.hip): what FaceParsing.__call__ (face_parsing/__init__.py:34-51), face_seg and get_image_prepare_material
+ * (musetalk/utils/blending.py:17-24, 62-86) do on the host around the BiSeNet graph.  Nothing synchronises with the host; a geometry the kernels cannot serve is
+ * MF_ERR_INVALID with the limit named in mf_last_error (more than 64 resampling taps per pixel: for mf_face_mask_finish a crop under 34 pixels from a 512 x 512 mask, which mf_face_mask_parse still serves; a blur wider than 151 taps: a crop over 1519 pixels); there is no fallback.
+ *
+ * mf_face_mask_parse: jobs[i] = (frame index, x_s, y_s, x_e, y_e) (host int32 [n_jobs][5]): the crop box of a uint8 [n_frames][H][W][3] device frame, black outside
+ * the frame like Image.crop, channels reversed when reverse_channels (`image[:, :, ::-1]`), is resized to the input buffer's size exactly as Pillow's
+ * Image.resize(size, BILINEAR) does for 8-bit pixels and written into batch slot i of in_buf as ((float)u8 / 255.f - mean3[c]) / std3[c] (bit-equal to mf_net_set_input
+ * of those floats); the graph runs at batch n_jobs <= its capacity; masks[i] (device uint8 [n_jobs][in_h][in_w]) = 255 where the argmax over the n_classes channels of
+ * head_buf, upsampled as mf_net_get_output_bilinear does, is a class in 1..13 (first maximum wins), else 0.
+ *
+ * mf_face_mask_finish: jobs[i] = (w, h, rx0, ry0, rx1, ry1, top) (host int32 [n_jobs][7]): masks[i] (device uint8 [n_jobs][mask_h][mask_w]) is resized to w x h as
+ * Image.resize(size) does for mode L (BICUBIC), zeroed outside the rectangle [rx0, rx1) x [ry0, ry1) and above row `top` (blending.py:74-82) -> pre_blur (optional),
+ * then blurred as cv2.GaussianBlur(., (k, k), 0), k = int(0.1 * w // 2 * 2) + 1, is defined (float64 taps, fp32 passes, one rounding) -> out.  Both outputs are packed:
+ * job i starts at the sum of w * h of the jobs before it.  blur = 0 stops at pre_blur (face_seg alone: the whole crop as rectangle, top = 0).
+ *
+ * workspace: device memory of mf_face_mask_workspace_bytes(finish, box_sizes, n_jobs, mask_h, mask_w) bytes, box_sizes = host int32 [n_jobs][2] (w, h) of the crop
+ * boxes, mask_h x mask_w = the size of the parser's input; 0 for a geometry that is refused. */
+size_t mf_face_mask_workspace_bytes(int finish, const int* box_sizes, int n_jobs, int mask_h, int mask_w);
+int mf_face_mask_parse(mf_net* net, int in_buf, int head_buf, int n_classes, const uint8_t* frames, int n_frames, int H, int W, int reverse_channels, const int* jobs,
+                       int n_jobs, const float* mean3, const float* std3, void* workspace, size_t workspace_bytes, uint8_t* masks, void* stream);
+int mf_face_mask_finish(const uint8_t* masks, int mask_h, int mask_w, const int* jobs, int n_jobs, int blur, void* workspace, size_t workspace_bytes, uint8_t* pre_blur,
+                        uint8_t* out, void* stream);
 void mf_net_destroy(mf_net* h);
 
 /* ---- measurement seam --------------------------------------------------------------------------------------------- */

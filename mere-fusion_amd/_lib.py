@@ -130,6 +130,10 @@ SIGNATURES = {
     "mf_s3fd_detect_tensors": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_s3fd_detect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mf_face_mask_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),
+    "mf_face_mask_parse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mf_face_mask_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_net_destroy": (None, [C.c_void_p]),
     "mf_probe_mfma_ceiling": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "mf_unet_create": (C.c_int, [C.POINTER(MfUnetConfig), C.POINTER(MfTensor), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

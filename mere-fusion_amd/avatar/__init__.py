@@ -3,3 +3,4 @@ module classes (face_detection/detection/sfd/net_s3fd.py, musetalk/utils/face_pa
 from .s3fd import s3fd                 # noqa: F401
 from .bisenet import BiSeNet           # noqa: F401
 from .face_detection import FaceAlignment, LandmarksType, SFDDetector   # noqa: F401
+from .face_parsing import FaceParsing, finish_masks   # noqa: F401

@@ -10,6 +10,7 @@
 // The op list is replayed as a hipGraph per batch size like the other stages.
 #include "mf_nn.h"
 #include "mf_aux.h"
+#include "mf_net_planes.h"
 #include <cfloat>
 #include <cmath>
 #include <functional>
@@ -19,20 +20,6 @@
 #include <vector>
 
 namespace {
-
-__device__ __forceinline__ float nbf(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t nfb(float f) {
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-struct Pl {   // one buffer's geometry for the elementwise kernels
-    bf16_t* hi; bf16_t* lo; int C, H, W, halo;
-    __device__ int64_t at(int b, int y, int x) const { return (((int64_t)b * (H + 2 * halo) + y + halo) * (W + 2 * halo) + x + halo) * C; }
-    __device__ float ld(int64_t o) const { float v = nbf(hi[o]); if (lo) v += nbf(lo[o]); return v; }
-    __device__ void st(int64_t o, float v) const { const uint32_t h = nfb(v); hi[o] = (bf16_t)h; if (lo) lo[o] = (bf16_t)nfb(v - nbf(h)); }
-};
-Pl pl_of(const ActBuf& b) { return Pl{b.hi, b.lo, b.C, b.H, b.W, b.halo}; }
 
 // F.max_pool2d(x, k, s, p): taps outside the image are skipped (== -inf padding)
 __global__ __launch_bounds__(256) void k_maxpool(Pl X, Pl Y, int k, int s, int p, int64_t total) {
@@ -127,13 +114,7 @@ __global__ __launch_bounds__(256) void k_bilinear_ac(Pl X, int coff, int C, floa
     const int y = t % H; t /= H;
     const int c = t % C;
     const int b = t / C;
-    const float fy = sh * y, fx = sw * x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < X.H - 1 ? 1 : 0), x1 = x0 + (x0 < X.W - 1 ? 1 : 0);
-    const float ly = fy - y0, lx = fx - x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float v00 = X.ld(X.at(b, y0, x0) + coff + c), v01 = X.ld(X.at(b, y0, x1) + coff + c);
-    const float v10 = X.ld(X.at(b, y1, x0) + coff + c), v11 = X.ld(X.at(b, y1, x1) + coff + c);
-    dst[idx] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    dst[idx] = bilinear_ac_sample(X, bilinear_ac_corners(X, y, x, sh, sw), b, coff + c);
 }
 
 // net_s3fd.py:123-126 "max-out background label": [B, 4, h, w] -> [B, 2, h, w] = (max(c0, c1, c2), c3)
