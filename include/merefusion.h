@@ -182,6 +182,45 @@ int mf_melspec_frames(int n);
 int mf_attention_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk,
                          int heads, int head_dim, int precision, void* stream);
 
+/* ---- token-sequence ops one at a time (test seams of LayerNorm, row softmax, GroupNorm, the plane conversions, the device-packed GEMM, the VAE's
+ * uint8 tail and the five-launch composite attention) ------------------------------------------------------------------------------------------ */
+/* A view of an activation buffer: channels [coff, coff + c) of a padded NHWC buffer [batch][h + 2*halo][w + 2*halo][cbuf]; token t of the view is
+ * pixel (t / w, t % w).  Tensors cross this ABI as device fp32 [batch][h*w][c]. */
+typedef struct mf_rows_geom { int cbuf, coff, c, h, w, halo; } mf_rows_geom;
+/* Every buffer these calls own is filled with a poison value before the input view is loaded over it: MF_NN_POISON_X3 where the (hi, lo) planes both
+ * exist (bf16x3), MF_NN_POISON_BF16 for the hi plane alone.  A non-null `y_full` receives the whole padded OUTPUT buffer [batch][h + 2*halo][w +
+ * 2*halo][cbuf] as fp32 (hi + lo): everything outside the written view must still read as the poison.  All calls synchronise the stream. */
+#define MF_NN_POISON_X3 (-1231.375f)
+#define MF_NN_POISON_BF16 (-1232.0f)
+/* fp32 -> planes (+ optional addend [h*w][c], broadcast over the batch) -> fp32.  y (optional): [batch][h*w][c].  y_layered (optional): the first
+ * `tokens` tokens into layer `layer` of a caller-initialised [batch][tokens][n_layers][c] tensor (Whisper's embedding gather). */
+int mf_rows_roundtrip(const float* x, const float* addend, float* y, float* y_layered, const mf_rows_geom* g, int batch, int tokens, int layer,
+                      int n_layers, int precision, float* y_full, void* stream);
+/* y = act((x - mean) / sqrt(var + eps) * gamma + beta) per token; tokens > 0: only that prefix of every batch item; act 0 none, 3 GELU (erf).
+ * gamma, beta: device fp32 [c].  At most 2048 channels. */
+int mf_layernorm_forward(const float* x, const float* gamma, const float* beta, float* y, const mf_rows_geom* gx, const mf_rows_geom* gy, int batch,
+                         float eps, int tokens, int act, int precision, float* y_full, void* stream);
+/* probs[t][j] = softmax_j(scale * scores[t][j]) over j < n_keys; columns n_keys .. gp->c - 1 are written as zero.  Rows of at most 2048 columns. */
+int mf_softmax_rows_forward(const float* scores, float* probs, const mf_rows_geom* gs, const mf_rows_geom* gp, int batch, int n_keys, float scale,
+                            int precision, float* y_full, void* stream);
+/* GroupNorm [+ SiLU] over (h*w x c/groups) per (batch, group); at most 64 groups and 4096 channels.  stats: device fp64 [batch][groups][2] (sum, sum of
+ * squares) -- read when have_stats (the apply kernel alone runs), else optional and filled by the statistics kernel.  scale, shift (optional, together):
+ * device fp32 [batch][c], the per-channel affine mf_groupnorm_affine derives (y = x * scale + shift before the SiLU). */
+int mf_groupnorm_forward(const float* x, const float* gamma, const float* beta, float* y, const mf_rows_geom* gx, const mf_rows_geom* gy, int batch,
+                         int groups, float eps, int silu, int have_stats, double* stats, float* scale, float* shift, int precision, float* y_full,
+                         void* stream);
+/* out[i][j] = sum_{l < pack_k} a[i][l] * B[j][l] for j < pack_n, 0 for pack_n <= j < n, with B[j][l] = b[j * stride_n + l * stride_k] packed on the device
+ * out of the planes of the fp32 matrix b [b_rows][b_cols].  a: [t][k], out: [t][n]; k % 8 == 0.  When pack_n < n or pack_k < k the plan is first packed
+ * with the whole n x k operand, so the smaller pack has stale entries to clear.  y_full: [1][3][t + 2][n rounded up to 8]; the GEMM's epilogue stores
+ * channel quads, so columns n .. (n rounded up to 4) - 1 of the interior are written too, as zero. */
+int mf_gemm_bt_forward(const float* a, const float* b, float* out, int t, int n, int k, int b_rows, int b_cols, int64_t stride_n, int64_t stride_k,
+                       int pack_n, int pack_k, int precision, float* y_full, void* stream);
+/* (x / 2 + 0.5).clamp(0, 1) * 255, rounded half to even -> dst device uint8 [batch][h][w][3] with the channel order reversed; gx->c == 3. */
+int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_rows_geom* gx, int batch, int precision, void* stream);
+/* mf_attention_forward's contract on the five-launch path (pack K, GEMM, row softmax, pack V^T, GEMM) the VAE mid-block runs: any head_dim % 8 == 0. */
+int mf_attention_composite_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk, int heads, int head_dim,
+                                   int precision, float* y_full, void* stream);
+
 /* ---- MuseTalk Whisper audio features (H3) -------------------------------------------------- */
 typedef struct mf_whisper mf_whisper;
 

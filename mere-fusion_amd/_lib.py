@@ -56,6 +56,10 @@ class MfWav2Vec2Config(C.Structure):
                 ("do_normalize", C.c_int), ("out_hidden", C.c_int)]
 
 
+class MfRowsGeom(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("cbuf", "coff", "c", "h", "w", "halo")]
+
+
 class MfPasteJob(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("frame_index", "x1", "y1", "x2", "y2", "cx1", "cy1", "cx2", "cy2")] + [("mask", C.c_void_p)]
 
@@ -157,6 +161,14 @@ SIGNATURES = {
     "mf_melspec": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_melspec_frames": (C.c_int, [C.c_int]),
     "mf_attention_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "mf_rows_roundtrip": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "mf_layernorm_forward": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] * 2 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 2),
+    "mf_softmax_rows_forward": (C.c_int, [C.c_void_p] * 2 + [C.POINTER(MfRowsGeom)] * 2 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 2),
+    "mf_groupnorm_forward": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] * 2 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
+                             + [C.c_int] + [C.c_void_p] * 2),
+    "mf_gemm_bt_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_int64] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2),
+    "mf_vae_post_u8_forward": (C.c_int, [C.c_void_p] * 2 + [C.POINTER(MfRowsGeom), C.c_int, C.c_int, C.c_void_p]),
+    "mf_attention_composite_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 2),
     "mf_near_far_from_aabb": (C.c_int, [C.c_void_p] * 3 + [C.c_uint32, C.c_float] + [C.c_void_p] * 3),
     "mf_march_rays": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32]
                       + [C.c_void_p] * 8),

@@ -18,6 +18,7 @@
 #include "mf_nn.h"
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -357,6 +358,57 @@ int mf_attention(const ActView& q, const ActView& k, const ActView& v, const Act
         case 160: return launch_qb<160, 32>(a, groups, x3, s);
     }
     return MF_ERR_INVALID;
+}
+
+// ---- the five-launch composite: pack K, scores GEMM, row softmax, pack V^T, weights x V GEMM ----
+// For head dims the fused kernel has no instance of (the VAE mid-block's dh 512).  ps / pv are grouped GEMM shells (mf_gemm_plan_create_grouped) for
+// `groups_cap` = batch capacity x heads operands; their rows are linear, so the k-group table is just cg * 8.
+int mf_attention_composite_plans(ConvPlan* ps, ConvPlan* pv, int dh, int Tq, int Tk, int groups_cap, int precision) {
+    MF_REQUIRE(dh > 0 && dh % 8 == 0, "attention: the composite needs a head dim that is a multiple of 8 (got %d)", dh);
+    const int Tk64 = (Tk + 63) / 64 * 64;
+    int rc;
+    if ((rc = mf_gemm_plan_create_grouped(ps, dh, Tk, Tq, groups_cap, precision))) return rc;
+    if ((rc = mf_gemm_plan_create_grouped(pv, Tk64, dh, Tq, groups_cap, precision))) return rc;
+    for (ConvPlan* p : {ps, pv}) {
+        std::vector<int> goff(p->goff_total);
+        for (int g = 0; g < p->goff_total; ++g) goff[g] = (g < p->cin_pad / 8 ? g : 0) * 8;
+        MF_HIP(hipMemcpy(p->goff, goff.data(), goff.size() * sizeof(int), hipMemcpyHostToDevice));
+        p->bound_in_ld = 1; p->bound_in_wp = 1;
+    }
+    return MF_OK;
+}
+
+// sc: scratch {C = Tk rounded up to 8, H = heads, W = Tq, halo 0}; pm: scratch {C = Tk rounded up to 64, H = heads, W = Tq, halo 0}; q / k / v / out: views of
+// contiguous (halo 0) token buffers with heads * dh channels
+int mf_attention_composite(ConvPlan* ps, ConvPlan* pv, const ActBuf* sc, const ActBuf* pm, const ActView& q, const ActView& k, const ActView& v,
+                           const ActView& out, int heads, int batch, int precision, hipStream_t s) {
+    const int C = q.C, dh = C / heads;
+    const int Tq = q.buf->H * q.buf->W, Tk = k.buf->H * k.buf->W;
+    MF_REQUIRE(!q.buf->halo && !k.buf->halo && !v.buf->halo && !out.buf->halo && dh * heads == C && dh % 8 == 0 && k.C == C && v.C == C && out.C == C,
+               "attention: needs contiguous token buffers and a head dim that is a multiple of 8");
+    MF_REQUIRE(v.buf->H * v.buf->W == Tk && out.buf->H * out.buf->W == Tq, "attention: token count mismatch");
+    MF_REQUIRE(sc->C >= Tk && sc->H * sc->W == heads * Tq && pm->C == pv->cin_pad && pm->C >= Tk && pm->H * pm->W == heads * Tq && !sc->halo && !pm->halo,
+               "attention: scratch buffers do not fit %d heads x %d queries x %d keys", heads, Tq, Tk);
+    const float scale = 1.0f / std::sqrt((float)dh);
+    const bool x3 = precision == MF_PREC_BF16X3;
+    int rc;
+    if ((rc = mf_pack_b_grouped(ps, k.buf->hi + k.coff, x3 ? k.buf->lo + k.coff : nullptr, k.buf->per_batch(), dh,
+                                k.buf->C, 1, Tk, dh, batch * heads, heads, s))) return rc;
+    GroupedGemm g{};
+    g.x_hi = q.buf->hi + q.coff; g.x_lo = x3 ? q.buf->lo + q.coff : nullptr;
+    g.zx_b = q.buf->per_batch(); g.zx_h = dh; g.x_row = q.buf->C;
+    g.y_hi = sc->hi; g.y_lo = sc->lo; g.zy_b = sc->per_batch(); g.zy_h = (int64_t)Tq * sc->C; g.y_row = sc->C;
+    g.M = Tq; g.groups = batch * heads; g.heads = heads;
+    if ((rc = mf_gemm_grouped_launch(ps, g, s))) return rc;
+    if ((rc = mf_softmax_rows(ActView{sc, 0, Tk}, ActView{pm, 0, pm->C}, Tk, scale, batch, s))) return rc;
+    if ((rc = mf_pack_b_grouped(pv, v.buf->hi + v.coff, x3 ? v.buf->lo + v.coff : nullptr, v.buf->per_batch(), dh,
+                                1, v.buf->C, dh, Tk, batch * heads, heads, s))) return rc;
+    GroupedGemm o{};
+    o.x_hi = pm->hi; o.x_lo = pm->lo; o.zx_b = pm->per_batch(); o.zx_h = (int64_t)Tq * pm->C; o.x_row = pm->C;
+    o.y_hi = out.buf->hi + out.coff; o.y_lo = x3 ? out.buf->lo + out.coff : nullptr;
+    o.zy_b = out.buf->per_batch(); o.zy_h = dh; o.y_row = out.buf->C;
+    o.M = Tq; o.groups = batch * heads; o.heads = heads;
+    return mf_gemm_grouped_launch(pv, o, s);
 }
 
 // ---- C ABI: the fused attention on fp32 [B][T][heads*dh] device tensors (test seam, like mf_conv2d_*) ----

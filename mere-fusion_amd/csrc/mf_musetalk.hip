@@ -457,16 +457,8 @@ struct Net {
         if (!attn_plans.count(key)) {
             ConvPlan* ps = new_plan();
             ConvPlan* pv = new_plan();
-            int rc;
-            if ((rc = mf_gemm_plan_create_grouped(ps, dh, Tk, Tq, cap * heads, precision))) return rc;
-            if ((rc = mf_gemm_plan_create_grouped(pv, Tk64, dh, Tq, cap * heads, precision))) return rc;
-            // linear rows: the k-group table is just cg*8
-            for (ConvPlan* p : {ps, pv}) {
-                std::vector<int> goff(p->goff_total);
-                for (int g = 0; g < p->goff_total; ++g) goff[g] = (g < p->cin_pad / 8 ? g : 0) * 8;
-                MF_HIP(hipMemcpy(p->goff, goff.data(), goff.size() * sizeof(int), hipMemcpyHostToDevice));
-                p->bound_in_ld = 1; p->bound_in_wp = 1;
-            }
+            const int rc = mf_attention_composite_plans(ps, pv, dh, Tq, Tk, cap * heads, precision);
+            if (rc) return rc;
             attn_plans[key] = {ps, pv};
         }
         ConvPlan* ps = attn_plans[key].first;
@@ -474,29 +466,10 @@ struct Net {
         ActBuf* sc = tmp("attn.scores", Tk8, heads, Tq, 0);
         ActBuf* pm = tmp("attn.probs", Tk64, heads, Tq, 0);
         if (!sc || !pm) return MF_ERR_HIP;
-        const float scale = 1.0f / std::sqrt((float)dh);
-        const bool x3 = precision == MF_PREC_BF16X3;
+        const int prec = precision;
         push("attention " + std::to_string(Tq) + "x" + std::to_string(Tk) + " heads " + std::to_string(heads) + " dh " + std::to_string(dh),
-             "pack+gemm+softmax+pack+gemm", 4.0 * Tq * Tk * C, [=](int B, hipStream_t s) {
-            int rc;
-            if ((rc = mf_pack_b_grouped(ps, k.buf->hi + k.coff, x3 ? k.buf->lo + k.coff : nullptr, k.buf->per_batch(), dh,
-                                        k.buf->C, 1, Tk, dh, B * heads, heads, s))) return rc;
-            GroupedGemm g{};
-            g.x_hi = q.buf->hi + q.coff; g.x_lo = x3 ? q.buf->lo + q.coff : nullptr;
-            g.zx_b = q.buf->per_batch(); g.zx_h = dh; g.x_row = q.buf->C;
-            g.y_hi = sc->hi; g.y_lo = sc->lo; g.zy_b = sc->per_batch(); g.zy_h = (int64_t)Tq * sc->C; g.y_row = sc->C;
-            g.M = Tq; g.groups = B * heads; g.heads = heads;
-            if ((rc = mf_gemm_grouped_launch(ps, g, s))) return rc;
-            if ((rc = mf_softmax_rows(ActView{sc, 0, Tk}, ActView{pm, 0, pm->C}, Tk, scale, B, s))) return rc;
-            if ((rc = mf_pack_b_grouped(pv, v.buf->hi + v.coff, x3 ? v.buf->lo + v.coff : nullptr, v.buf->per_batch(), dh,
-                                        1, v.buf->C, dh, Tk, B * heads, heads, s))) return rc;
-            GroupedGemm o{};
-            o.x_hi = pm->hi; o.x_lo = pm->lo; o.zx_b = pm->per_batch(); o.zx_h = (int64_t)Tq * pm->C; o.x_row = pm->C;
-            o.y_hi = out.buf->hi + out.coff; o.y_lo = x3 ? out.buf->lo + out.coff : nullptr;
-            o.zy_b = out.buf->per_batch(); o.zy_h = dh; o.y_row = out.buf->C;
-            o.M = Tq; o.groups = B * heads; o.heads = heads;
-            return mf_gemm_grouped_launch(pv, o, s);
-        });
+             "pack+gemm+softmax+pack+gemm", 4.0 * Tq * Tk * C,
+             [=](int B, hipStream_t s) { return mf_attention_composite(ps, pv, sc, pm, q, k, v, out, heads, B, prec, s); });
         return MF_OK;
     }
 

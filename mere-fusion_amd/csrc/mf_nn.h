@@ -52,9 +52,6 @@ void mf_tail_conv_destroy(TailConv* p);
 int mf_gn_conv3_tail(const TailConv& p, const ActView& x, const float* gamma, const float* beta, int groups, float eps, bool silu, double* stats,
                      bool have_stats, const ActView& out, int batch, hipStream_t s);
 
-// GEGLU (diffusers): y[t][c] = x[t][c] * gelu(x[t][C + c]) for c < C = x.C / 2
-int mf_geglu(const ActView& x, const ActView& y, int batch, hipStream_t s);
-
 // Packs `groups` = batch*heads B operands at once (see mf_pack_b): group z = (b, h) reads
 // src[b*sb + h*sh + n*stride_n + k*stride_k] into plan weights + z * (KT*Npad*64).
 int mf_pack_b_grouped(ConvPlan* plan, const bf16_t* src_hi, const bf16_t* src_lo, int64_t sb, int64_t sh, int64_t stride_n,
@@ -71,5 +68,12 @@ bool mf_attention_supported(int dh);
 // tq / tk > 0: only the first tq queries attend to only the first tk keys of every batch item (sequence prefixes)
 int mf_attention(const ActView& q, const ActView& k, const ActView& v, const ActView& out, int heads, int batch, int precision,
                  hipStream_t s, int tq = 0, int tk = 0);
+
+// The same attention as five launches (pack K, scores GEMM, mf_softmax_rows, pack V^T, weights x V GEMM) for any head dim that is a multiple of 8: the
+// VAE mid-block's single 512-wide head.  mf_attention_composite_plans fills two fresh ConvPlans (grouped GEMM shells for `groups_cap` = batch capacity x
+// heads operands); sc / pm are caller-owned halo-0 scratch buffers {C = Tk rounded up to 8 / to 64, H = heads, W = Tq}.
+int mf_attention_composite_plans(ConvPlan* ps, ConvPlan* pv, int dh, int Tq, int Tk, int groups_cap, int precision);
+int mf_attention_composite(ConvPlan* ps, ConvPlan* pv, const ActBuf* sc, const ActBuf* pm, const ActView& q, const ActView& k, const ActView& v,
+                           const ActView& out, int heads, int batch, int precision, hipStream_t s);
 
 inline int64_t mf_interior(const ActBuf& b) { return ((int64_t)b.halo * b.Wp() + b.halo) * b.C; }

@@ -381,17 +381,6 @@ __global__ __launch_bounds__(256) void k_gn_apply(Rows X, Rows Y, const float* _
     (void)TS;
 }
 
-__global__ __launch_bounds__(256) void k_geglu(Rows X, Rows Y, int C, int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c = (int)(idx % C);
-    const int64_t r = idx / C;
-    const int t = (int)(r % X.T), b = (int)(r / X.T);
-    const int64_t xo = X.off(b, t);
-    const float a = ld(X.hi, X.lo, xo + c), g = ld(X.hi, X.lo, xo + C + c);
-    st(const_cast<bf16_t*>(Y.hi), const_cast<bf16_t*>(Y.lo), Y.off(b, t) + c, a * (0.5f * g * (1.f + erff(g * 0.70710678118654752f))));
-}
-
 __global__ __launch_bounds__(256) void k_pack_b_grouped(const bf16_t* sh, const bf16_t* sl, int64_t sb, int64_t shd,
                                                         int64_t stride_n, int64_t stride_k, int N, int K, int Npad, int heads,
                                                         int64_t per_group, bf16_t* dh, bf16_t* dl, int64_t total) {
@@ -547,15 +536,6 @@ int mf_groupnorm(const ActView& x, const ActView& y, const float* gamma, const f
         else
             hipLaunchKernelGGL(k_gn_apply<1>, grid, dim3(256), 0, s, xr, yr, gamma, beta, stats, 1.0 / ((double)xr.T * cpg), eps, groups, cpg, x.C, silu ? 1 : 0, 0);
     }
-    MF_HIP(hipGetLastError());
-    return MF_OK;
-}
-
-int mf_geglu(const ActView& x, const ActView& y, int batch, hipStream_t s) {
-    MF_REQUIRE(x.C == 2 * y.C, "geglu: input must have twice the output channels");
-    const Rows xr = rows_of(x), yr = rows_of(y);
-    const int64_t total = (int64_t)batch * xr.T * y.C;
-    hipLaunchKernelGGL(k_geglu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, xr, yr, y.C, total);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

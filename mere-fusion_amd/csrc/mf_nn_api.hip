@@ -1,0 +1,208 @@
+// C ABI test seams of the token-sequence ops (mf_nn.hip) and of the composite attention, like mf_attention_forward: fp32 [batch][T][C] device
+// tensors in and out, every op launched exactly as the model builders launch it.  Each call owns its buffers: they are filled with a fixed finite
+// poison value first (MF_NN_POISON_*), the input view is loaded over it, and `y_full` hands the whole padded output buffer back, so a test sees
+// every element an op wrote outside its view (halo ring, neighbouring channels of a wider buffer, tokens past a prefix).
+#include "mf_nn.h"
+#include <cmath>
+
+namespace {
+
+constexpr bf16_t POISON_HI = 0xC49A;   // -1232
+constexpr bf16_t POISON_LO = 0x3F20;   // 0.625: hi + lo = -1231.375 is exact in fp32, and a write to either plane alone changes it
+
+__global__ __launch_bounds__(256) void k_fill_planes(bf16_t* hi, bf16_t* lo, int64_t n, bf16_t vh, bf16_t vl) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    hi[i] = vh;
+    if (lo) lo[i] = vl;
+}
+
+__global__ __launch_bounds__(256) void k_planes_to_f32(const bf16_t* hi, const bf16_t* lo, float* dst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = __uint_as_float((uint32_t)hi[i] << 16);
+    if (lo) v += __uint_as_float((uint32_t)lo[i] << 16);
+    dst[i] = v;
+}
+
+bool geom_ok(const mf_rows_geom* g) {
+    return g && g->c > 0 && g->coff >= 0 && g->coff + g->c <= g->cbuf && g->h > 0 && g->w > 0 && g->halo >= 0;
+}
+
+// a poisoned activation buffer of `batch` items
+struct PBuf {
+    ActBuf b;
+    int64_t n = 0;     // elements of the batch (without the tail pad every buffer of the library carries)
+    ~PBuf() {
+        if (b.hi) (void)hipFree(b.hi);
+        if (b.lo) (void)hipFree(b.lo);
+    }
+    int alloc(int C, int H, int W, int halo, int batch, bool x3, hipStream_t s) {
+        b.C = C; b.H = H; b.W = W; b.halo = halo;
+        n = (int64_t)batch * b.per_batch();
+        const int64_t total = n + 64;
+        MF_HIP(hipMalloc(&b.hi, total * sizeof(bf16_t)));
+        if (x3) MF_HIP(hipMalloc(&b.lo, total * sizeof(bf16_t)));
+        hipLaunchKernelGGL(k_fill_planes, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, b.hi, b.lo, total, POISON_HI, POISON_LO);
+        MF_HIP(hipGetLastError());
+        return MF_OK;
+    }
+    int alloc(const mf_rows_geom& g, int batch, bool x3, hipStream_t s) { return alloc(g.cbuf, g.h, g.w, g.halo, batch, x3, s); }
+    ActView view(const mf_rows_geom& g) const { return ActView{&b, g.coff, g.c}; }
+    ActView all() const { return ActView{&b, 0, b.C}; }
+    int full(float* dst, hipStream_t s) const {      // [batch][Hp][Wp][C] as fp32 (hi + lo), or nothing
+        if (!dst) return MF_OK;
+        hipLaunchKernelGGL(k_planes_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.hi, b.lo, dst, n);
+        MF_HIP(hipGetLastError());
+        return MF_OK;
+    }
+};
+
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { MF_HIP(hipMalloc(&p, bytes)); return MF_OK; }
+};
+
+struct PlanGuard {
+    ConvPlan p;
+    ~PlanGuard() { mf_conv_plan_destroy(&p); }
+};
+
+#define API_PREC(name)                                                                                                                    \
+    MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, name ": unknown precision %d", precision);                       \
+    const bool x3 = precision == MF_PREC_BF16X3;                                                                                          \
+    hipStream_t s = (hipStream_t)stream;                                                                                                  \
+    int rc
+
+}  // namespace
+
+extern "C" int mf_rows_roundtrip(const float* x, const float* addend, float* y, float* y_layered, const mf_rows_geom* g, int batch, int tokens,
+                                 int layer, int n_layers, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(x && geom_ok(g) && batch > 0, "rows_roundtrip: null argument or bad geometry");
+    API_PREC("rows_roundtrip");
+    PBuf b;
+    if ((rc = b.alloc(*g, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, addend, b.view(*g), batch, s))) return rc;
+    if (y && (rc = mf_rows_to_f32(b.view(*g), y, batch, s))) return rc;
+    if (y_layered && (rc = mf_rows_to_f32_layered(b.view(*g), y_layered, batch, tokens, layer, n_layers, s))) return rc;
+    if ((rc = b.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_layernorm_forward(const float* x, const float* gamma, const float* beta, float* y, const mf_rows_geom* gx, const mf_rows_geom* gy,
+                                    int batch, float eps, int tokens, int act, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(x && gamma && beta && y && geom_ok(gx) && geom_ok(gy) && batch > 0, "layernorm_forward: null argument or bad geometry");
+    API_PREC("layernorm_forward");
+    PBuf bx, by;
+    if ((rc = bx.alloc(*gx, batch, x3, s)) || (rc = by.alloc(*gy, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*gx), batch, s))) return rc;
+    if ((rc = mf_layernorm(bx.view(*gx), by.view(*gy), gamma, beta, eps, batch, s, tokens, act))) return rc;
+    if ((rc = mf_rows_to_f32(by.view(*gy), y, batch, s))) return rc;
+    if ((rc = by.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_softmax_rows_forward(const float* scores, float* probs, const mf_rows_geom* gs, const mf_rows_geom* gp, int batch, int n_keys,
+                                       float scale, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(scores && probs && geom_ok(gs) && geom_ok(gp) && batch > 0, "softmax_rows_forward: null argument or bad geometry");
+    API_PREC("softmax_rows_forward");
+    PBuf bs, bp;
+    if ((rc = bs.alloc(*gs, batch, x3, s)) || (rc = bp.alloc(*gp, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(scores, nullptr, bs.view(*gs), batch, s))) return rc;
+    if ((rc = mf_softmax_rows(bs.view(*gs), bp.view(*gp), n_keys, scale, batch, s))) return rc;
+    if ((rc = mf_rows_to_f32(bp.view(*gp), probs, batch, s))) return rc;
+    if ((rc = bp.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_groupnorm_forward(const float* x, const float* gamma, const float* beta, float* y, const mf_rows_geom* gx, const mf_rows_geom* gy,
+                                    int batch, int groups, float eps, int silu, int have_stats, double* stats, float* scale, float* shift,
+                                    int precision, float* y_full, void* stream) {
+    MF_REQUIRE(x && gamma && beta && y && geom_ok(gx) && geom_ok(gy) && batch > 0 && groups > 0, "groupnorm_forward: null argument or bad geometry");
+    MF_REQUIRE(!have_stats || stats, "groupnorm_forward: have_stats needs the statistics");
+    MF_REQUIRE((scale == nullptr) == (shift == nullptr), "groupnorm_forward: scale and shift come together");
+    API_PREC("groupnorm_forward");
+    PBuf bx, by;
+    DevMem own;
+    const int ns = batch * groups * 2;
+    if ((rc = own.alloc((size_t)ns * 2 * sizeof(double)))) return rc;
+    double* st = stats ? stats : (double*)own.p;
+    double* st2 = (double*)own.p + ns;           // mf_groupnorm_affine's own statistics
+    if ((rc = bx.alloc(*gx, batch, x3, s)) || (rc = by.alloc(*gy, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*gx), batch, s))) return rc;
+    if (!have_stats && (rc = mf_zero_f64(st, ns, s))) return rc;
+    if ((rc = mf_groupnorm(bx.view(*gx), by.view(*gy), gamma, beta, groups, eps, silu != 0, st, batch, s, have_stats != 0))) return rc;
+    if (scale) {
+        if (have_stats) MF_HIP(hipMemcpyAsync(st2, st, (size_t)ns * sizeof(double), hipMemcpyDeviceToDevice, s));
+        else if ((rc = mf_zero_f64(st2, ns, s))) return rc;
+        if ((rc = mf_groupnorm_affine(bx.view(*gx), gamma, beta, groups, eps, st2, scale, shift, batch, s, have_stats != 0))) return rc;
+    }
+    if ((rc = mf_rows_to_f32(by.view(*gy), y, batch, s))) return rc;
+    if ((rc = by.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_gemm_bt_forward(const float* a, const float* b, float* out, int t, int n, int k, int b_rows, int b_cols, int64_t stride_n,
+                                  int64_t stride_k, int pack_n, int pack_k, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(a && b && out && t > 0 && n > 0 && k > 0 && b_rows > 0 && b_cols > 0, "gemm_bt_forward: null argument or empty shape");
+    MF_REQUIRE(pack_n > 0 && pack_n <= n && pack_k > 0 && pack_k <= k, "gemm_bt_forward: packs %d x %d of a %d x %d operand", pack_n, pack_k, n, k);
+    MF_REQUIRE(stride_n >= 0 && stride_k >= 0 && (int64_t)(pack_n - 1) * stride_n + (int64_t)(pack_k - 1) * stride_k < (int64_t)b_rows * b_cols,
+               "gemm_bt_forward: the strides leave the %d x %d source", b_rows, b_cols);
+    API_PREC("gemm_bt_forward");
+    // token sequences as the Whisper encoder holds them: one row, halo 1
+    PBuf ba, bb, bo;
+    const int n8 = (n + 7) / 8 * 8;
+    if ((rc = ba.alloc(k, 1, t, 1, 1, x3, s)) || (rc = bb.alloc(b_cols, 1, b_rows, 0, 1, x3, s)) || (rc = bo.alloc(n8, 1, t, 1, 1, x3, s))) return rc;
+    PlanGuard pg;
+    if ((rc = mf_gemm_plan_create(&pg.p, k, n, t, precision))) return rc;
+    if ((rc = mf_conv_bind(&pg.p, ba.b))) return rc;
+    if ((rc = mf_rows_from_f32(a, nullptr, ba.all(), 1, s))) return rc;
+    if ((rc = mf_rows_from_f32(b, nullptr, bb.all(), 1, s))) return rc;
+    // a first pack of the whole operand when the call asks for a smaller one: the entries the second pack leaves out must come back zero
+    if ((pack_n < n || pack_k < k) && (rc = mf_pack_b(&pg.p, bb.b.hi, bb.b.lo, stride_n, stride_k, n, k, s))) return rc;
+    if ((rc = mf_pack_b(&pg.p, bb.b.hi, bb.b.lo, stride_n, stride_k, pack_n, pack_k, s))) return rc;
+    if ((rc = mf_conv_launch(&pg.p, ba.all(), ActView{&bo.b, 0, n}, ActView{}, 1, s))) return rc;
+    if ((rc = mf_rows_to_f32(ActView{&bo.b, 0, n}, out, 1, s))) return rc;
+    if ((rc = bo.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_rows_geom* gx, int batch, int precision, void* stream) {
+    MF_REQUIRE(x && dst && geom_ok(gx) && batch > 0, "vae_post_u8_forward: null argument or bad geometry");
+    API_PREC("vae_post_u8_forward");
+    PBuf bx;
+    if ((rc = bx.alloc(*gx, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*gx), batch, s))) return rc;
+    if ((rc = mf_vae_post_u8(bx.view(*gx), dst, batch, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_attention_composite_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk, int heads,
+                                              int head_dim, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(q && k && v && out, "attention_composite_forward: null argument");
+    MF_REQUIRE(batch > 0 && tq > 0 && tk > 0 && heads > 0, "attention_composite_forward: batch=%d tq=%d tk=%d heads=%d", batch, tq, tk, heads);
+    MF_REQUIRE(head_dim > 0 && head_dim % 8 == 0, "attention_composite_forward: head_dim %d is not a multiple of 8", head_dim);
+    API_PREC("attention_composite_forward");
+    const int C = heads * head_dim, tk8 = (tk + 7) / 8 * 8, tk64 = (tk + 63) / 64 * 64;
+    PBuf bq, bk, bv, bo, sc, pm;
+    if ((rc = bq.alloc(C, 1, tq, 0, batch, x3, s)) || (rc = bk.alloc(C, 1, tk, 0, batch, x3, s)) || (rc = bv.alloc(C, 1, tk, 0, batch, x3, s)) ||
+        (rc = bo.alloc(C, 1, tq, 0, batch, x3, s)) || (rc = sc.alloc(tk8, heads, tq, 0, batch, x3, s)) || (rc = pm.alloc(tk64, heads, tq, 0, batch, x3, s)))
+        return rc;
+    PlanGuard ps, pv;
+    if ((rc = mf_attention_composite_plans(&ps.p, &pv.p, head_dim, tq, tk, batch * heads, precision))) return rc;
+    if ((rc = mf_rows_from_f32(q, nullptr, bq.all(), batch, s))) return rc;
+    if ((rc = mf_rows_from_f32(k, nullptr, bk.all(), batch, s))) return rc;
+    if ((rc = mf_rows_from_f32(v, nullptr, bv.all(), batch, s))) return rc;
+    if ((rc = mf_attention_composite(&ps.p, &pv.p, &sc.b, &pm.b, bq.all(), bk.all(), bv.all(), bo.all(), heads, batch, precision, s))) return rc;
+    if ((rc = mf_rows_to_f32(bo.all(), out, batch, s))) return rc;
+    if ((rc = bo.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}

@@ -161,8 +161,8 @@ struct mf_whisper {
     unsigned* gmax = nullptr;   // [cap]
     int cap = 1;                // windows one call can encode (mf_whisper_set_batch)
     std::vector<float> pos_host;   // sinusoids as NCHW [1][C][1][T], re-uploaded into every batch slot of `pos` when the workspace grows
-    bool fused_attn = true;     // one k_attention launch per layer; false (MF_ATTN=composite or an unsupported head dim):
-                                // per-head pack + GEMM + softmax + pack + GEMM
+    bool fused_attn = true;     // one k_attention launch per layer; false (set by mf_whisper_create for a head dim mf_attention_supported declines,
+                                // nothing else switches it): per-head pack + GEMM + softmax + pack + GEMM
 
     ~mf_whisper() {
         for (auto& p : plans) mf_conv_plan_destroy(p.get());

@@ -8,18 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from nn_numerics import _one_hot_qkv, _qkv
 from oracle import musetalk_ref as R
-
-
-def _qkv(b, tq, tk, heads, dh, seed):
-    g = torch.Generator().manual_seed(seed)
-    c = heads * dh
-    # non-symmetric, per-channel scaled inputs: an operand transpose or a head / channel mix-up changes the answer
-    ramp = torch.linspace(0.5, 1.5, c)
-    q = torch.randn(b, tq, c, generator=g) * ramp
-    k = torch.randn(b, tk, c, generator=g) * ramp.flip(0)
-    v = torch.randn(b, tk, c, generator=g) + torch.arange(c) * 0.01
-    return q, k, v
 
 
 def test_oracle_attention_core_matches_dense_softmax():
@@ -82,27 +72,6 @@ def test_hip_attention_rejects_unsupported_head_dim(lib_built):
 KT = {40: 64, 64: 64, 80: 64, 160: 32}
 REPR = {"bf16x3": 2.0 ** -16, "bf16": 2.0 ** -8}
 EDGE_CASES = [(dh, tk) for dh in (40, 64, 80, 160) for tk in (KT[dh] - 1, KT[dh], KT[dh] + 1, 2 * KT[dh] + 1)]
-
-
-def _one_hot_qkv(b, tq, tk, heads, dh, hot_keys, seed, margin=200.0):
-    """q, k, v and, per (batch, query, head), the key whose logit (q.k / sqrt(dh)) sits >= `margin` - ~10 above every other key's.  Hot key i of `hot_keys` is
-    A e_i in its head; the other keys are N(0, 1) in the head dims >= len(hot_keys) (orthogonal to every hot key); query r of head h points at hot key
-    (r + h) % len(hot_keys), with N(0, 1) noise in the same dims as the ordinary keys."""
-    g = torch.Generator().manual_seed(seed)
-    n = len(hot_keys)
-    amp = (margin * dh ** 0.5) ** 0.5
-    k = torch.randn(b, tk, heads, dh, generator=g)
-    k[..., :n] = 0
-    q = torch.randn(b, tq, heads, dh, generator=g)
-    q[..., :n] = 0
-    pick = (torch.arange(tq)[:, None] + torch.arange(heads)[None, :]) % n            # [tq, heads]
-    for i, key in enumerate(hot_keys):
-        k[:, key] = 0
-        k[:, key, :, i] = amp
-    q.scatter_(-1, pick[None, :, :, None].expand(b, tq, heads, 1), amp)
-    v = torch.randn(b, tk, heads, dh, generator=g) * 2 + torch.linspace(-1, 1, dh)
-    want = torch.stack([v[:, hot_keys[int(pick[r, h])], h] for r in range(tq) for h in range(heads)], 1).reshape(b, tq, heads, dh)
-    return q.reshape(b, tq, -1), k.reshape(b, tk, -1), v.reshape(b, tk, -1), want.reshape(b, tq, -1)
 
 
 @pytest.mark.gpu
