@@ -351,6 +351,20 @@ int mf_sh_encode_forward(const float* inputs, float* outputs, uint32_t B, uint32
  * freqencoder.cu:30-58); outputs [B, D + 2*D*degree]. */
 int mf_freq_encode_forward(const float* inputs, uint32_t B, uint32_t D, uint32_t degree, uint32_t C, float* outputs, void* stream);
 
+/* `_backend.morton3D(coords, N, indices)` (raymarching.py:98 -> kernel_morton3D, raymarching.cu:214-226): coords int32 [N,3] ->
+ * indices int32 [N], 10 bits per axis interleaved (x in bit 0, y in bit 1, z in bit 2). */
+int mf_morton3d(const int* coords, uint32_t n, int* indices, void* stream);
+/* `_backend.morton3D_invert(indices, N, coords)` (raymarching.py:120 -> kernel_morton3D_invert, raymarching.cu:237-254):
+ * indices int32 [N] -> coords int32 [N,3]. */
+int mf_morton3d_invert(const int* indices, uint32_t n, int* coords, void* stream);
+/* `_backend.packbits(grid, N, density_thresh, bitfield)` (raymarching.py:149 -> kernel_packbits, raymarching.cu:268-289):
+ * grid fp32 [N*8] -> bitfield uint8 [N]; bit i of byte n is (grid[8n + i] > density_thresh), a strict comparison. */
+int mf_packbits(const float* grid, uint32_t n_bytes, float density_thresh, uint8_t* bitfield, void* stream);
+/* `_backend.morton3D_dilation(grid, C, H, grid_dilation)` (raymarching.py:175 -> kernel_morton3D_dilation, raymarching.cu:304-335):
+ * grid fp32 [C, H^3] in Morton order -> out [C, H^3], fmaxf over a cell and its six neighbours, clipped at the borders.
+ * H <= 1024, C * H^3 < 2^32; out must not alias grid. */
+int mf_morton3d_dilation(const float* grid, uint32_t cascades, uint32_t grid_size, float* out, void* stream);
+
 /* Tail of `run_cuda` (renderer.py:275-280) and the uint8 conversion of nerfreal.py:111, in place:
  * image[N,3] = clamp(image + (1 - weights_sum) * bg, 0, 1); depth[N] = clamp(depth - near, 0) / (far - near);
  * frame_u8 (optional, may be NULL) = uint8(image * 255), truncating like ndarray.astype.  bg_color: device fp32 [N,3]
@@ -384,6 +398,23 @@ int mf_nerf_field_create(const mf_nerf_field_config* cfg, const mf_tensor* weigh
 int mf_nerf_field_forward(mf_nerf_field* h, const float* xyzs, const float* dirs, const float* enc_a, const float* ind_code,
                           float eye, int n_samples, float* sigmas, float* rgbs, float* amb_aud, float* amb_eye,
                           float* uncertainty, void* stream);
+/* Replaces the head branch of `NeRFRenderer.update_extra_state` (renderer.py:437-485) as three launches, no host
+ * synchronisation: (a) the density half of the field (network.py:280-308) swept over the cascades x grid_size^3 cell
+ * centres of :458-467 -- bound_c = min(2^cas, bound), half = bound_c / grid_size, position = (2 c / (H - 1) - 1) *
+ * (bound_c - half) + (2 u - 1) * half in the reference's float32 statement order -- sigma * density_scale written to
+ * tmp_grid in Morton order; (b) six-neighbour max of tmp_grid and, where grid >= 0 and the max >= 0, grid =
+ * fmaxf(grid * decay, max) (:475-479), cells marked -1 kept; (c) mean_density = mean of max(grid, 0) as an fp64 sum in a
+ * fixed order, density_bitfield = packbits(grid, min((float)mean_density, density_thresh)) (:480-485).
+ * density_grid: device fp32 [cascades, grid_size^3], in/out; density_bitfield: uint8 [cascades * grid_size^3 / 8], out;
+ * enc_a: device fp32 [32]; eye: the scalar of opt.exp_eye, used when use_eye (the field must have been created with
+ * exp_eye; without use_eye such a field sees e = 0); noise: device fp32 [cascades, grid_size^3, 3], the torch.rand values
+ * of :467 in meshgrid order ((x H + y) H + z), or NULL for cell centres; tmp_grid: fp32 [cascades, grid_size^3], holds
+ * the sweep's (undilated) values afterwards; xyzs_out: fp32 [cascades, grid_size^3, 3] in Morton order, or NULL;
+ * mean_density: device fp64, 1 value.  grid_size 32, 64 or 128, cascades 1..8, else MF_ERR_INVALID with the limit named in
+ * mf_last_error.  Needs the fused field kernel and runs in the field's precision mode. */
+int mf_nerf_density_grid_update(mf_nerf_field* field, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound,
+                                const float* enc_a, float eye, int use_eye, float density_scale, float decay, float density_thresh,
+                                const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density, void* stream);
 void mf_nerf_field_destroy(mf_nerf_field* h);
 
 /* a24, `Trainer.test_gui_with_data` utils.py:1208-1216 + nerfreal.py:111: the [h,w] render resized to the GUI's [H,W].

@@ -39,6 +39,13 @@ int mf_nerf_tail_launch(const bf16_t* packed, bool x3, const float* const emb[3]
                         const uint8_t* bitfield, float* xyzs, float* dirs, float* deltas, float* wsum, float* depth, float* image, float* aasum, float* aesum,
                         float* unsum, hipStream_t s);
 
+// mf_nerf_occupancy.hip: the occupancy-grid rebuild over the fused field's weight fragments (sweep, dilate + EMA, reduce + pack)
+int mf_nerf_occupancy_shape(int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked
+int mf_nerf_occupancy_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float field_bound,
+                             int has_eye, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound, const float* enc_a, float eye,
+                             float density_scale, float decay, float density_thresh, const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density,
+                             double* partials, hipStream_t s);
+
 // mf_nerf_torso.hip: the whole torso branch as one fp32 kernel (default); the GEMM chain below stays for A/B (MF_TORSO=gemm)
 int mf_nerf_torso_fused_weight_count();
 int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls,
@@ -203,6 +210,8 @@ struct mf_nerf_field : TokenNet {
     float* emb[3] = {nullptr, nullptr, nullptr};
     float *coords = nullptr, *enc = nullptr, *d_enc_a = nullptr, *d_ind = nullptr;
     bf16_t* fused_w = nullptr;      // weight fragments of k_nerf_field_fused, or null (MF_NERF_FIELD=gemm)
+    double* occ_partials = nullptr; // per-workgroup sums of mf_nerf_density_grid_update, allocated at its first call
+    size_t occ_cap = 0;
 };
 
 static const mf_tensor* nf_find(const std::map<std::string, const mf_tensor*>& sd, const std::string& k, int64_t r, int64_t c) {
@@ -304,6 +313,28 @@ extern "C" int mf_nerf_field_create(const mf_nerf_field_config* cfg, const mf_te
     MF_HIP(hipDeviceSynchronize());
     *out = h.release();
     return MF_OK;
+}
+
+extern "C" int mf_nerf_density_grid_update(mf_nerf_field* h, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound,
+                                           const float* enc_a, float eye, int use_eye, float density_scale, float decay, float density_thresh, const float* noise,
+                                           float* tmp_grid, float* xyzs_out, double* mean_density, void* stream) {
+    MF_REQUIRE(h && density_grid && density_bitfield && enc_a && tmp_grid && mean_density, "nerf_density_grid_update: null argument");
+    MF_REQUIRE(h->fused_w, "nerf_density_grid_update: needs the fused field kernel (the field was created under MF_NERF_FIELD=gemm)");
+    MF_REQUIRE(!use_eye || h->cfg.exp_eye, "nerf_density_grid_update: use_eye on a field created without exp_eye");
+    size_t need = 0;
+    int rc;
+    if ((rc = mf_nerf_occupancy_shape(cascades, grid_size, &need))) return rc;
+    if (need > h->occ_cap) {
+        // (first call for this size: the only allocation; a grown buffer leaves the old one to mf_nerf_field_destroy, which frees h->dev -- a launch may still read it)
+        double* p = nullptr;
+        MF_HIP(hipMalloc(&p, need * sizeof(double)));
+        h->dev.push_back(p);
+        h->occ_partials = p; h->occ_cap = need;
+    }
+    const mf_nerf_field_config& c = h->cfg;
+    return mf_nerf_occupancy_launch(h->fused_w, h->precision == MF_PREC_BF16X3, h->emb, c.offsets, c.log2_per_level_scale, c.base_resolution, c.bound,
+                                    use_eye ? 1 : 0, density_grid, density_bitfield, cascades, grid_size, bound, enc_a, eye, density_scale, decay, density_thresh,
+                                    noise, tmp_grid, xyzs_out, mean_density, h->occ_partials, (hipStream_t)stream);
 }
 
 extern "C" int mf_nerf_field_forward(mf_nerf_field* h, const float* xyzs, const float* dirs, const float* enc_a, const float* ind_code,

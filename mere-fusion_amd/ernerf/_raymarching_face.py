@@ -26,6 +26,26 @@ def composite_rays_triplane(n_alive, n_step, T_thresh, rays_alive, rays_t, sigma
            B.f32(amb_aud_sum, "amb_aud_sum"), B.f32(amb_eye_sum, "amb_eye_sum"), B.f32(uncertainty_sum, "uncertainty_sum"), B.stream())
 
 
+def morton3D(coords, N, indices):
+    """raymarching.py:98 -> raymarching.cu:229-232."""
+    B.call("mf_morton3d", B.i32(coords, "coords"), int(N), B.i32(indices, "indices"), B.stream())
+
+
+def morton3D_invert(indices, N, coords):
+    """raymarching.py:120 -> raymarching.cu:257-260."""
+    B.call("mf_morton3d_invert", B.i32(indices, "indices"), int(N), B.i32(coords, "coords"), B.stream())
+
+
+def packbits(grid, N, density_thresh, bitfield):
+    """raymarching.py:149 -> raymarching.cu:292-300 (N bytes of bitfield, eight cells each)."""
+    B.call("mf_packbits", B.f32(grid, "grid"), int(N), float(density_thresh), B.u8(bitfield, "bitfield"), B.stream())
+
+
+def morton3D_dilation(grid, C, H, grid_dilation):
+    """raymarching.py:175 -> raymarching.cu:337-340."""
+    B.call("mf_morton3d_dilation", B.f32(grid, "grid"), int(C), int(H), B.f32(grid_dilation, "grid_dilation"), B.stream())
+
+
 def _training_only(name):
     def f(*a, **k):
         raise RuntimeError(f"_raymarching_face.{name}: training / occupancy-grid maintenance is outside the MI355X inference path")
@@ -33,7 +53,7 @@ def _training_only(name):
     return f
 
 
-for _n in ("sph_from_ray", "morton3D", "morton3D_invert", "packbits", "morton3D_dilation", "march_rays_train", "march_rays_train_backward",
+for _n in ("sph_from_ray", "march_rays_train", "march_rays_train_backward",
            "composite_rays_train_forward", "composite_rays_train_backward", "composite_rays", "composite_rays_ambient",
            "composite_rays_train_sigma_forward", "composite_rays_train_sigma_backward", "composite_rays_ambient_sigma",
            "composite_rays_train_uncertainty_forward", "composite_rays_train_uncertainty_backward", "composite_rays_uncertainty",

@@ -18,6 +18,8 @@ The device objects are built from `self.state_dict()` at the first frame AFTER t
 camera optimisation at test time, `perturb`, a missing audio window or eye feature, CPU tensors: the reference's own `run_cuda` runs, over the extension
 shims (`dropin/_raymarching_face.py` ...), exactly as before."""
 import os
+import random
+import sys
 
 import torch
 
@@ -51,6 +53,7 @@ class HipRenderMixin:
     _mf = None
     _mf_frame_id = 0
     mf_frames = 0                      # frames rendered by the device loop (tests assert the fast route ran)
+    mf_grid_updates = 0                # occupancy grids rebuilt by the device route
 
     def __init__(self, *args, **kwargs):
         # on a multi-GPU node the process takes its GPU here, before the reference's Trainer says `.to('cuda')` (placement.py)
@@ -144,6 +147,62 @@ class HipRenderMixin:
         res["image"] = out["image"].view(*prefix, 3)
         res["weights_sum"] = out["weights_sum"]
         return res
+
+
+    # ---- occupancy-grid maintenance (renderer.py:421-539) ---------------------------------------------------------------------------
+    def _mf_grid_fast_path(self):
+        if os.environ.get("MF_NERF_DROPIN", "1") == "0" or not self.cuda_ray or self.torso:
+            return False
+        # what mf_nerf_density_grid_update does not serve goes the reference's way too: another grid size, a field without the fused kernel
+        if self.grid_size not in (32, 64, 128) or not 1 <= self.cascade <= 8 or os.environ.get("MF_NERF_FIELD") == "gemm":
+            return False
+        return torch.is_tensor(self.density_grid) and self.density_grid.is_cuda and self.density_bitfield.is_cuda
+
+    def update_extra_state(self, decay=0.95, S=128):
+        """`NeRFRenderer.update_extra_state` with the head grid rebuilt on the device (mf_nerf_density_grid_update: sweep, dilate + EMA, reduce + pack: three
+        kernels, after the jitter's `torch.rand` draws).  The selection statements are the reference's own and consume the same Python / torch random streams, so both routes rebuild from the same
+        audio window, eye value and jitter.  Torso training, CPU tensors, MF_NERF_DROPIN=0: the reference's method runs, over the extension shims
+        (`morton3D`, `morton3D_dilation`, `packbits`), the torso grid branch of :488-528 included.  `mark_untrained_grid` and `reset_extra_state` need no
+        override: they are torch statements over the same shims and buffers."""
+        if not self._mf_grid_fast_path():
+            return super().update_extra_state(decay=decay, S=S)
+        dev = self.density_bitfield.device
+        # the reference's helper (ernerf/nerf_triplane/utils.py:43), as the module that defines the method this one stands in front of imported it (renderer.py:11)
+        mro = type(self).__mro__
+        owner = next(c for c in mro[mro.index(HipRenderMixin) + 1:] if "update_extra_state" in vars(c))
+        get_audio_features = getattr(sys.modules[owner.__module__], "get_audio_features")
+        with torch.no_grad():
+            rand_idx = random.randint(0, self.aud_features.shape[0] - 1)                              # renderer.py:428-432
+            auds = get_audio_features(self.aud_features, self.att, rand_idx).to(dev)
+            enc_a = self.encode_audio(auds)
+            eye = float(self.eye_area[[rand_idx]].reshape(-1)[0]) if self.exp_eye else None           # :440-443 (eye_area lives on the host)
+            # the jitter of :467, drawn block by block and cascade by cascade as the reference's loops draw it
+            H, Cn = self.grid_size, self.cascade
+            steps = [(i, min(i + S, H)) for i in range(0, H, S)]
+            noise = torch.empty(Cn, H, H, H, 3, device=dev)
+            if len(steps) == 1:                                                                       # S >= grid_size (the reference's default): one draw per cascade, in place
+                for cas in range(Cn):
+                    torch.rand(H ** 3, 3, out=noise[cas].view(H ** 3, 3))
+            else:
+                for x0, x1 in steps:
+                    for y0, y1 in steps:
+                        for z0, z1 in steps:
+                            for cas in range(Cn):
+                                noise[cas, x0:x1, y0:y1, z0:z1] = torch.rand((x1 - x0) * (y1 - y0) * (z1 - z0), 3, device=dev).view(x1 - x0, y1 - y0, z1 - z0, 3)
+            st = self._mf
+            if st is None or st["device"] != dev or st["bitfield_ptr"] != self.density_bitfield.data_ptr():
+                st = self._mf_build(st["cap"] if st is not None else 1, dev)
+            r = st["renderer"]
+            r.bitfield, r.density_scale = self.density_bitfield, float(self.density_scale)
+            mean = r.update_density_grid(self.density_grid, enc_a, eye=eye, decay=decay, density_thresh=float(self.density_thresh), noise=noise.view(Cn, H ** 3, 3),
+                                         cascades=Cn)
+        self.mean_density = mean.item()                                                               # :480, the one sync the reference has too
+        self.iter_density += 1
+        total_step = min(16, self.local_step)                                                         # :533-537
+        if total_step > 0:
+            self.mean_count = int(self.step_counter[:total_step, 0].sum().item() / total_step)
+        self.local_step = 0
+        self.__dict__["mf_grid_updates"] = self.mf_grid_updates + 1
 
 
 def load_reference_module(shadow_name, shadow_file, package):

@@ -163,6 +163,56 @@ class HipHeadRenderer:
         hit[0].replay()
         return hit[1]
 
+    GRID_SIZES = (32, 64, 128)          # what mf_nerf_density_grid_update serves (the reference always uses 128)
+
+    @torch.no_grad()
+    def update_density_grid(self, density_grid, enc_a, eye=None, decay=0.95, density_thresh=10.0, noise=None, cascades=None, tmp_grid=None, xyzs_out=None):
+        """The head branch of `NeRFRenderer.update_extra_state` (renderer.py:437-485) on the device, three launches and no host sync
+        (mf_nerf_density_grid_update): the density field swept over the cascades x grid_size^3 cell centres, six-neighbour dilation, the
+        masked EMA with `decay`, mean density, bit pack with min(mean, density_thresh) (opt.density_thresh, default 10).
+
+        density_grid [cascades, grid_size^3] fp32 is updated in place and so is `self.bitfield` (same tensor, same data_ptr: a captured
+        graph stays valid).  enc_a: [1, 32] / [32] device tensor; eye: the scalar eye feature (a host number or tensor; a device tensor
+        is read back, which syncs) or None; noise: [cascades, grid_size^3, 3] uniform numbers in the reference's meshgrid order (what its
+        `torch.rand_like` calls draw, :467), None samples the cell centres.  tmp_grid / xyzs_out: optional [cascades, grid_size^3] /
+        [cascades, grid_size^3, 3] fp32 buffers that keep the sweep's raw values and positions (Morton order).
+        Returns mean_density as a 0-d float64 device tensor."""
+        H = self.grid_size
+        if H not in self.GRID_SIZES:
+            raise RuntimeError(f"HipHeadRenderer.update_density_grid: grid_size {H} is not served (32, 64 or 128)")
+        cascades = self.cascade if cascades is None else int(cascades)
+        if not 1 <= cascades <= 8:
+            raise RuntimeError(f"HipHeadRenderer.update_density_grid: cascades {cascades} outside 1..8")
+        cells = cascades * H ** 3
+
+        def dev_f32(t, name, numel):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise RuntimeError(f"HipHeadRenderer.update_density_grid: {name} must be a CUDA tensor (there is no CPU path)")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+                raise RuntimeError(f"HipHeadRenderer.update_density_grid: {name} must be contiguous float32 with {numel} elements "
+                                   f"(got {t.dtype}, {tuple(t.shape)})")
+            return t
+        dev_f32(density_grid, "density_grid", cells)
+        if not (torch.is_tensor(enc_a) and enc_a.is_cuda):
+            raise RuntimeError("HipHeadRenderer.update_density_grid: enc_a must be a CUDA tensor (there is no CPU path)")
+        if not self.bitfield.is_cuda or self.bitfield.dtype != torch.uint8 or self.bitfield.numel() != cells // 8:
+            raise RuntimeError(f"HipHeadRenderer.update_density_grid: the bitfield must be a CUDA uint8 tensor of {cells // 8} bytes")
+        dev = density_grid.device
+        ea = dev_f32(enc_a.float().reshape(-1).contiguous(), "enc_a", 32)
+        if noise is not None:
+            dev_f32(noise, "noise", cells * 3)
+        tmp_grid = torch.empty(cascades, H ** 3, device=dev) if tmp_grid is None else dev_f32(tmp_grid, "tmp_grid", cells)
+        if xyzs_out is not None:
+            dev_f32(xyzs_out, "xyzs_out", cells * 3)
+        use_eye = eye is not None and self.field.exp_eye
+        ev = float(eye.reshape(-1)[0]) if torch.is_tensor(eye) else (float(eye) if eye is not None else 0.0)
+        mean = torch.empty((), dtype=torch.float64, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.mf_nerf_density_grid_update(self.field._h, p(density_grid), p(self.bitfield), cascades, H, self.bound, p(ea), ev, int(use_eye),
+                                                         self.density_scale, float(decay), float(density_thresh), p(noise), p(tmp_grid), p(xyzs_out), p(mean),
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_density_grid_update")
+        return mean
+
     @torch.no_grad()
     def run_cuda(self, rays_o, rays_d, enc_a, ind_code, eye, bg_color=None, dt_gamma=1 / 256, max_steps=16, T_thresh=1e-4, perturb=False,
                  want_u8=False):
