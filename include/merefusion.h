@@ -415,6 +415,15 @@ int mf_nerf_field_forward(mf_nerf_field* h, const float* xyzs, const float* dirs
 int mf_nerf_density_grid_update(mf_nerf_field* field, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound,
                                 const float* enc_a, float eye, int use_eye, float density_scale, float decay, float density_thresh,
                                 const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density, void* stream);
+/* Replaces `NeRFRenderer.mark_untrained_grid` (renderer.py:356-416) as one launch: one lane per (cascade, Morton index) forms
+ * the cell centre world = (2 c / (H - 1) - 1) * (bound_c - bound_c / H) (:387-394, float32 statement order) and walks the poses
+ * (camera-to-world, device fp32 [n_poses, 4, 4]): cam = (world - t) @ R; the cell is covered when cam.z > 0 and
+ * |cam.x| < (cx / fx) cam.z + 2 bound_c / H and |cam.y| < (cy / fy) cam.z + 2 bound_c / H (:402-408; the Python scalars are formed in
+ * double and rounded to fp32 where they meet the tensor).  A cell no pose covers gets -1 (:416); every other cell keeps its bits.
+ * density_grid: device fp32 [cascades, grid_size^3] in Morton order, in/out.  grid_size 32, 64 or 128, cascades 1..8,
+ * n_poses >= 1, else MF_ERR_INVALID with the limit named in mf_last_error. */
+int mf_nerf_mark_untrained(const float* poses, int n_poses, double fx, double fy, double cx, double cy, float bound, int cascades,
+                           int grid_size, float* density_grid, void* stream);
 void mf_nerf_field_destroy(mf_nerf_field* h);
 
 /* a24, `Trainer.test_gui_with_data` utils.py:1208-1216 + nerfreal.py:111: the [h,w] render resized to the GUI's [H,W].
@@ -489,6 +498,24 @@ int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_tensor* weigh
 int mf_nerf_torso_forward(mf_nerf_torso* h, const float* bg_coords, const float* frame_consts_host, const float* bg_color,
                           int bg_per_ray, float bg_const, float density_thresh, int n_pixels, float* bg_out, float* torso_alpha,
                           float* deform, void* stream);
+/* The occupancy grid mf_nerf_torso_forward samples: `density_grid` (device fp32 [grid_size^2], row y, column x) is BORROWED, as
+ * mf_nerf_head_render borrows the bitfield -- the reference rebinds `self.density_grid_torso` at every torso update
+ * (renderer.py:527), so the caller hands over the tensor of the frame.  It must stay valid until the forwards that use it have
+ * finished.  NULL: back to the copy of "density_grid_torso" taken at creation. */
+int mf_nerf_torso_set_grid(mf_nerf_torso* h, const float* density_grid);
+/* Replaces the torso branch of `NeRFRenderer.update_extra_state` (renderer.py:488-528) as three launches, no host
+ * synchronisation: (a) one lane per cell (x, y): position = (2 c / (G - 1) - 1) * (1 - 1/G) + (2 u - 1) * (1/G) in the
+ * reference's float32 statement order (:511-514), through the per-point arithmetic of mf_nerf_torso_forward (no occupancy mask,
+ * no colour mix), alpha written to raw_grid[y G + x] (the reference transposes, :510); (b) 5 x 5 max of raw_grid (stride 1, the
+ * border padded with -inf as max_pool2d pads) and grid = fmaxf(grid * decay, max) (:522-527); (c) mean = mean of grid (:528) as an
+ * fp64 sum in a fixed order, rounded to fp32.
+ * frame_consts_host as in mf_nerf_torso_forward (the pose and code row of :492-499); noise: device fp32 [G^2, 2], the
+ * torch.rand values of :514 in meshgrid order (row x G + y), or NULL for cell centres; density_grid: device fp32 [G^2], in/out,
+ * and the grid later forwards sample (as mf_nerf_torso_set_grid); raw_grid: fp32 [G^2], holds the sweep's (undilated) alpha
+ * afterwards; xys_out: fp32 [G^2, 2] in meshgrid order, or NULL; mean: device fp32, 1 value.  G = the handle's grid_size: 32, 64 or
+ * 128, else MF_ERR_INVALID with the limit named in mf_last_error.  Needs the fused torso kernel (not MF_TORSO=gemm). */
+int mf_nerf_torso_grid_update(mf_nerf_torso* h, const float* frame_consts_host, const float* noise, float decay, float* density_grid,
+                              float* raw_grid, float* xys_out, float* mean, void* stream);
 void mf_nerf_torso_destroy(mf_nerf_torso* h);
 
 /* ---- ER-NeRF audio features ------------------------------------------------------------------- */

@@ -200,6 +200,9 @@ SIGNATURES = {
     "mf_nerf_head_destroy": (None, [C.c_void_p]),
     "mf_nerf_torso_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mf_nerf_torso_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 4),
+    "mf_nerf_torso_set_grid": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mf_nerf_torso_grid_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5),
+    "mf_nerf_mark_untrained": (C.c_int, [C.c_void_p, C.c_int] + [C.c_double] * 4 + [C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mf_nerf_torso_destroy": (None, [C.c_void_p]),
     "mf_audio_encoder_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mf_audio_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

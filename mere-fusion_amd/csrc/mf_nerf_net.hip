@@ -40,7 +40,7 @@ int mf_nerf_tail_launch(const bf16_t* packed, bool x3, const float* const emb[3]
                         float* unsum, hipStream_t s);
 
 // mf_nerf_occupancy.hip: the occupancy-grid rebuild over the fused field's weight fragments (sweep, dilate + EMA, reduce + pack)
-int mf_nerf_occupancy_shape(int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked
+int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked
 int mf_nerf_occupancy_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float field_bound,
                              int has_eye, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound, const float* enc_a, float eye,
                              float density_scale, float decay, float density_thresh, const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density,
@@ -51,6 +51,10 @@ int mf_nerf_torso_fused_weight_count();
 int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls,
                                int base_res, const float* density, int G, const float* bg_coords, float shrink, float thresh, const float* bg,
                                int bg_per_ray, float bg_const, int N, float* out, float* alpha_out, float* deform, hipStream_t s);
+// ... and the torso grid's rebuild through the same per-point code: sweep, 5 x 5 dilate + EMA, mean
+int mf_nerf_torso_grid_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
+                              float shrink, int G, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out, float* mean,
+                              double* partials, hipStream_t s);
 
 namespace {
 
@@ -323,7 +327,7 @@ extern "C" int mf_nerf_density_grid_update(mf_nerf_field* h, float* density_grid
     MF_REQUIRE(!use_eye || h->cfg.exp_eye, "nerf_density_grid_update: use_eye on a field created without exp_eye");
     size_t need = 0;
     int rc;
-    if ((rc = mf_nerf_occupancy_shape(cascades, grid_size, &need))) return rc;
+    if ((rc = mf_nerf_occupancy_shape("nerf_density_grid_update", cascades, grid_size, &need))) return rc;
     if (need > h->occ_cap) {
         // (first call for this size: the only allocation; a grown buffer leaves the old one to mf_nerf_field_destroy, which frees h->dev -- a launch may still read it)
         double* p = nullptr;
@@ -479,6 +483,10 @@ struct mf_nerf_torso : TokenNet {
     std::vector<float> wd_const, wt_const;     // [32][50]: the constant-input columns of the two first layers
     float* wf = nullptr;                       // fp32 [out][in] tables of the six layers for the fused kernel (mf_nerf_torso.hip)
     bool fused = true;
+    const float* grid = nullptr;               // mf_nerf_torso_set_grid / _grid_update: the caller's density_grid_torso, borrowed; null = `density`, the copy of creation
+    double* grid_partials = nullptr;           // per-workgroup sums of mf_nerf_torso_grid_update (grid_size^2 / 256 <= 64 at the sizes served)
+    const float* sampled() const { return grid ? grid : density; }
+    void frame_bias(const float* frame_consts_host, float* bd, float* bt) const;
 };
 
 extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_tensor* weights, int n_weights, int precision, int max_pixels,
@@ -519,6 +527,8 @@ extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_te
         MF_REQUIRE(n == (int64_t)cfg->grid_size * cfg->grid_size, "nerf_torso_create: density_grid_torso has %lld entries, expected %d^2", (long long)n, cfg->grid_size);
         if ((rc = dmalloc(&h->density, (size_t)n))) return rc;
         MF_HIP(hipMemcpy(h->density, it->second->data, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        MF_HIP(hipMalloc(&h->grid_partials, 64 * sizeof(double)));
+        h->dev.push_back(h->grid_partials);
     }
     auto first_layer = [&](const char* name, int cin_ref, int var_cols, int cin_buf, const std::vector<int>& col_of, std::vector<float>& w,
                            std::vector<float>& wconst) -> int {
@@ -577,6 +587,19 @@ extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_te
     return MF_OK;
 }
 
+// per-frame biases of the two first layers: W[:, constant columns] . [freq(wrapped anchors) | individual code]
+void mf_nerf_torso::frame_bias(const float* frame_consts_host, float* bd, float* bt) const {
+    const int ncst = 42 + cfg.individual_dim;
+    for (int o = 0; o < 32; ++o) {
+        double a = 0, b = 0;
+        for (int i = 0; i < ncst; ++i) {
+            a += (double)wd_const[(size_t)o * NCONST + i] * frame_consts_host[i];
+            b += (double)wt_const[(size_t)o * NCONST + i] * frame_consts_host[i];
+        }
+        bd[o] = (float)a; bt[o] = (float)b;
+    }
+}
+
 namespace {
 struct FrameBias { float v[64]; };
 __global__ void k_torso_bias(FrameBias fb, float* bd, float* bt) {
@@ -593,20 +616,11 @@ extern "C" int mf_nerf_torso_forward(mf_nerf_torso* h, const float* bg_coords, c
     if (n_pixels == 0) return MF_OK;
     hipStream_t s = (hipStream_t)stream;
     const int N = n_pixels, nb = (N + TW - 1) / TW, gb = (N + 255) / 256;
-    const int ncst = 42 + h->cfg.individual_dim;
-    // per-frame biases of the two first layers: W[:, constant columns] . [freq(wrapped anchors) | individual code]
     FrameBias fb;
     float *bd = fb.v, *bt = fb.v + 32;
-    for (int o = 0; o < 32; ++o) {
-        double a = 0, b = 0;
-        for (int i = 0; i < ncst; ++i) {
-            a += (double)h->wd_const[(size_t)o * NCONST + i] * frame_consts_host[i];
-            b += (double)h->wt_const[(size_t)o * NCONST + i] * frame_consts_host[i];
-        }
-        bd[o] = (float)a; bt[o] = (float)b;
-    }
+    h->frame_bias(frame_consts_host, bd, bt);
     if (h->fused)
-        return mf_nerf_torso_fused_launch(h->wf, bd, bt, h->emb, h->cfg.offsets, h->cfg.log2_per_level_scale, h->cfg.base_resolution, h->density,
+        return mf_nerf_torso_fused_launch(h->wf, bd, bt, h->emb, h->cfg.offsets, h->cfg.log2_per_level_scale, h->cfg.base_resolution, h->sampled(),
                                           h->cfg.grid_size, bg_coords, h->cfg.torso_shrink, density_thresh, bg_color, bg_per_ray, bg_const, N, bg_out,
                                           torso_alpha, deform, s);
     hipLaunchKernelGGL(k_torso_bias, dim3(1), dim3(64), 0, s, fb, h->d1->bias, h->t1->bias);   // by value: no staging copy, no host sync
@@ -628,9 +642,32 @@ extern "C" int mf_nerf_torso_forward(mf_nerf_torso* h, const float* bg_coords, c
     if ((rc = mf_conv_launch(h->t1, V(h->TH, TH_C), V(h->U1, 32), ActView{}, nb, s))) return rc;
     if ((rc = mf_conv_launch(h->t2, V(h->U1, 32), V(h->U2, 32), ActView{}, nb, s))) return rc;
     if ((rc = mf_conv_launch(h->t3, V(h->U2, 32), V(h->OUT, 4), ActView{}, nb, s))) return rc;
-    hipLaunchKernelGGL(k_torso_mix, dim3(gb), dim3(256), 0, s, bg_coords, h->density, h->cfg.grid_size, density_thresh, h->OUT->hi, h->OUT->lo, bg_color,
+    hipLaunchKernelGGL(k_torso_mix, dim3(gb), dim3(256), 0, s, bg_coords, h->sampled(), h->cfg.grid_size, density_thresh, h->OUT->hi, h->OUT->lo, bg_color,
                        bg_per_ray, bg_const, N, bg_out, torso_alpha);
     MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_torso_set_grid(mf_nerf_torso* h, const float* density_grid) {
+    MF_REQUIRE(h, "nerf_torso_set_grid: null handle");
+    h->grid = density_grid;
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_torso_grid_update(mf_nerf_torso* h, const float* frame_consts_host, const float* noise, float decay, float* density_grid, float* raw_grid,
+                                         float* xys_out, float* mean, void* stream) {
+    MF_REQUIRE(h && frame_consts_host && density_grid && raw_grid && mean, "nerf_torso_grid_update: null argument");
+    MF_REQUIRE(density_grid != raw_grid, "nerf_torso_grid_update: density_grid and raw_grid are the same buffer");
+    MF_REQUIRE(h->fused, "nerf_torso_grid_update: needs the fused torso kernel (unset MF_TORSO=gemm)");
+    size_t unused = 0;
+    int rc;
+    if ((rc = mf_nerf_occupancy_shape("nerf_torso_grid_update", 1, h->cfg.grid_size, &unused))) return rc;
+    float bd[32], bt[32];
+    h->frame_bias(frame_consts_host, bd, bt);
+    if ((rc = mf_nerf_torso_grid_launch(h->wf, bd, bt, h->emb, h->cfg.offsets, h->cfg.log2_per_level_scale, h->cfg.base_resolution, h->cfg.torso_shrink,
+                                        h->cfg.grid_size, noise, decay, density_grid, raw_grid, xys_out, mean, h->grid_partials, (hipStream_t)stream)))
+        return rc;
+    h->grid = density_grid;
     return MF_OK;
 }
 

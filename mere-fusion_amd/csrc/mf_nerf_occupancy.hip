@@ -196,6 +196,53 @@ __global__ __launch_bounds__(OCC_T) void k_reduce_pack(const float* __restrict__
     bitfield[byte] = (uint8_t)pack8(g, thresh);
 }
 
+// ---- mark_untrained_grid (renderer.py:356-416) -------------------------------------------------------------------------------------------------------
+constexpr int MARK_T = 256;             // one cell per lane; 256 | H^3, so a workgroup lies in one cascade
+constexpr int MARK_POSES = 64;          // poses staged per round: 12 floats each (R row-major, then t)
+
+struct MarkArgs {
+    uint32_t H, log2_H3;
+    int n_poses;
+    float inv_hm1, kx, ky;               // float32(cx / fx), float32(cy / fy): Python scalars, rounded when they meet the tensor (:407-408)
+    float scale[MAX_CASCADES];           // float32(bound_c - half_grid_size) (:394)
+    float slack[MAX_CASCADES];           // float32(half_grid_size * 2)
+};
+
+// A cell is covered when some camera sees its centre inside the frustum widened by a cell (:402-409); the reference counts the cameras and reads only
+// `count == 0` (:416), so the walk over the poses ends for a wave once each of its lanes has found one.
+__global__ __launch_bounds__(MARK_T) void k_mark_untrained(const float* __restrict__ poses, float* __restrict__ grid, const MarkArgs a) {
+#pragma clang fp contract(off)
+    __shared__ float sp[MARK_POSES * 12];
+    __shared__ float s_scale[MAX_CASCADES], s_slack[MAX_CASCADES];
+    if (threadIdx.x < MAX_CASCADES) { s_scale[threadIdx.x] = a.scale[threadIdx.x]; s_slack[threadIdx.x] = a.slack[threadIdx.x]; }
+    __syncthreads();
+    const uint32_t n = blockIdx.x * MARK_T + threadIdx.x;
+    const uint32_t cas = n >> a.log2_H3, ind = n & ((1u << a.log2_H3) - 1u);
+    const float sc = s_scale[cas], h2 = s_slack[cas];
+    const float px = cell_position(compact_bits(ind), a.inv_hm1, sc, 0.f, false, 0.f);
+    const float py = cell_position(compact_bits(ind >> 1), a.inv_hm1, sc, 0.f, false, 0.f);
+    const float pz = cell_position(compact_bits(ind >> 2), a.inv_hm1, sc, 0.f, false, 0.f);
+    bool covered = false;
+    for (int p0 = 0; p0 < a.n_poses; p0 += MARK_POSES) {
+        const int np = min(MARK_POSES, a.n_poses - p0);
+        for (int i = threadIdx.x; i < np * 12; i += MARK_T) {
+            const int p = i / 12, k = i - p * 12;                                      // k < 9: R[k / 3][k % 3], else t[k - 9]
+            sp[i] = poses[(size_t)(p0 + p) * 16 + (k < 9 ? (k / 3) * 4 + k % 3 : (k - 9) * 4 + 3)];
+        }
+        __syncthreads();
+        for (int p = 0; p < np && !__all(covered); ++p) {
+            const float* q = sp + p * 12;
+            const float dx = px - q[9], dy = py - q[10], dz = pz - q[11];             // cas_world_xyzs - poses[:, :3, 3]
+            const float cx = dx * q[0] + dy * q[3] + dz * q[6];                        // @ poses[:, :3, :3]
+            const float cy = dx * q[1] + dy * q[4] + dz * q[7];
+            const float cz = dx * q[2] + dy * q[5] + dz * q[8];
+            covered = covered || (cz > 0.f && fabsf(cx) < a.kx * cz + h2 && fabsf(cy) < a.ky * cz + h2);
+        }
+        if (!__syncthreads_or(!covered)) break;                                        // (also the barrier in front of the next round's staging)
+    }
+    if (!covered) grid[n] = -1.0f;
+}
+
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + NT - 1) / NT); }
 
 }  // namespace
@@ -234,10 +281,11 @@ extern "C" int mf_morton3d_dilation(const float* grid, uint32_t C, uint32_t H, f
 }
 
 // ---- the rebuild: called by mf_nerf_density_grid_update (mf_nerf_net.hip, where the field handle is defined) after mf_nerf_occupancy_shape accepted the sizes ----------------------------------------------
-// the sizes served (checked here once, for the launch below too) and the number of per-workgroup partial sums they need
-int mf_nerf_occupancy_shape(int cascades, int grid_size, size_t* n_partials) {
-    MF_REQUIRE(grid_size == 32 || grid_size == 64 || grid_size == 128, "nerf_density_grid_update: grid_size %d is not served (32, 64 or 128)", grid_size);
-    MF_REQUIRE(cascades >= 1 && cascades <= MAX_CASCADES, "nerf_density_grid_update: cascades %d outside 1..%d", cascades, MAX_CASCADES);
+// the sizes served (checked here once: for the launch below, for mf_nerf_mark_untrained and for the torso grid of mf_nerf_torso_grid_update) and the number of
+// per-workgroup partial sums the head grid needs
+int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_t* n_partials) {
+    MF_REQUIRE(grid_size == 32 || grid_size == 64 || grid_size == 128, "%s: grid_size %d is not served (32, 64 or 128)", what, grid_size);
+    MF_REQUIRE(cascades >= 1 && cascades <= MAX_CASCADES, "%s: cascades %d outside 1..%d", what, cascades, MAX_CASCADES);
     *n_partials = (size_t)cascades * grid_size * grid_size * grid_size / OCC_CELLS;
     return MF_OK;
 }
@@ -272,6 +320,30 @@ int mf_nerf_occupancy_launch(const bf16_t* packed, bool x3, const float* const e
     hipLaunchKernelGGL(k_dilate_ema, dim3(nwg), dim3(OCC_T), 0, s, tmp_grid, density_grid, H, log2_H3, decay, partials);
     MF_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_reduce_pack, dim3(nwg), dim3(OCC_T), 0, s, density_grid, partials, nwg, (double)cells, density_thresh, density_bitfield, mean_density);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_mark_untrained(const float* poses, int n_poses, double fx, double fy, double cx, double cy, float bound, int cascades, int grid_size,
+                                      float* density_grid, void* stream) {
+    MF_REQUIRE(poses && density_grid, "nerf_mark_untrained: null argument");
+    MF_REQUIRE(n_poses >= 1, "nerf_mark_untrained: n_poses %d: at least one pose is needed (with none every cell would be marked untrained)", n_poses);
+    MF_REQUIRE(bound > 0.f && fx != 0.0 && fy != 0.0, "nerf_mark_untrained: bound and the focal lengths must be non-zero");
+    size_t unused = 0;
+    int rc;
+    if ((rc = mf_nerf_occupancy_shape("nerf_mark_untrained", cascades, grid_size, &unused))) return rc;
+    MarkArgs a{};
+    a.H = (uint32_t)grid_size; a.log2_H3 = grid_size == 32 ? 15u : (grid_size == 64 ? 18u : 21u);
+    a.n_poses = n_poses; a.inv_hm1 = 1.0f / (float)(grid_size - 1);
+    a.kx = (float)(cx / fx); a.ky = (float)(cy / fy);
+    for (int c = 0; c < cascades; ++c) {
+        // `bound = min(2 ** cas, self.bound)`, `half_grid_size = bound / self.grid_size`: Python floats (doubles)
+        const double bc = std::min((double)(1 << c), (double)bound), half = bc / (double)grid_size;
+        a.scale[c] = (float)(bc - half);
+        a.slack[c] = (float)(half * 2);
+    }
+    const unsigned nwg = (unsigned)(((size_t)cascades << a.log2_H3) / MARK_T);
+    hipLaunchKernelGGL(k_mark_untrained, dim3(nwg), dim3(MARK_T), 0, (hipStream_t)stream, poses, density_grid, a);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

@@ -32,6 +32,11 @@ struct TorsoFusedArgs {
     float shrink, thresh, bg_const;
     int bg_per_ray, G, N;
     float *out, *alpha_out, *deform;
+    // the grid sweep (k_torso_fused<true>): the jitter [G^2, 2] in meshgrid order (row x G + y) or null, the positions out (same order) or null, and the
+    // Python scalars of renderer.py:511-514 as the float32 values they take when they meet the tensor
+    const float* noise;
+    float* xys_out;
+    float inv_gm1, cell_scale, cell_half;
 };
 
 // the frequency features' sine is the reference's own: freqencoder.cu:56 calls __sinf -- the hardware sine of x / 2 pi -- and so does k_freq_encode (mf_nerf.hip);
@@ -104,10 +109,43 @@ __device__ __forceinline__ void from_lds(const float* col, f32x2 (&x)[HID / 2]) 
     for (int j = 0; j < HID / 2; ++j) x[j] = f32x2{col[2 * j * 256], col[(2 * j + 1) * 256]};
 }
 
+// renderer.py:511-514 for one coordinate of a torso grid cell: every operation rounded to fp32 as written (contraction is off in this file)
+__device__ __forceinline__ float torso_cell_position(int c, float inv_gm1, float scale, float half, bool noisy, float u) {
+    float v = 2.0f * (float)c;           // 2 * coords.float()
+    v = v * inv_gm1;                     // / (grid_size - 1): a tensor over a Python scalar is a product with the scalar's fp32 reciprocal
+    v = v - 1.0f;                        // - 1
+    v = v * scale;                       // * (1 - half_grid_size)
+    if (noisy) {
+        float r = u * 2.0f;              // torch.rand_like(xys) * 2
+        r = r - 1.0f;                    // - 1
+        r = r * half;                    // * half_grid_size
+        v = v + r;                       // xys += ...
+    }
+    return v;
+}
+
+// SWEEP off: one frame of `run_torso`, a lane per pixel of bg_coords.  SWEEP on: the torso branch of `update_extra_state` (renderer.py:506-519), a lane per
+// cell of the G x G occupancy grid -- lane n is cell (x, y) = (n % G, n / G), its point formed by torso_cell_position, the same per-point arithmetic, and the
+// raw alpha stored at alpha_out[y G + x] = alpha_out[n] (the reference's transposed index, :510) with no occupancy mask and no colour mix.
+template <bool SWEEP>
 __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= a.N) return;
-    const float2 bc = *reinterpret_cast<const float2*>(a.bg_coords + 2 * (size_t)n);
+    float2 bc;
+    int sweep_row = 0;
+    if constexpr (SWEEP) {
+        const int cx = n % a.G, cy = n / a.G;
+        sweep_row = cx * a.G + cy;
+        float u0 = 0.f, u1 = 0.f;
+        if (a.noise) {
+            const float2 u = *reinterpret_cast<const float2*>(a.noise + 2 * (size_t)sweep_row);
+            u0 = u.x; u1 = u.y;
+        }
+        bc.x = torso_cell_position(cx, a.inv_gm1, a.cell_scale, a.cell_half, a.noise != nullptr, u0);
+        bc.y = torso_cell_position(cy, a.inv_gm1, a.cell_scale, a.cell_half, a.noise != nullptr, u1);
+    } else {
+        bc = *reinterpret_cast<const float2*>(a.bg_coords + 2 * (size_t)n);
+    }
     // TH / TX: [grid 32 | x 2 | sin, cos of 2^f x, f = 0..7 (freqencoder.cu:30-58: sinf(scalbnf(x, f) + phase)) ]
     f32x2 in[(TG + FQ) / 2];                      // pairs 0..15: grid features, 16..32: frequency features
     float fq[FQ];
@@ -196,6 +234,12 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) o4[k] = col[k * 256];
     }
+    if constexpr (SWEEP) {
+        // alpha = sigmoid(.) * 1.002 - 0.001 (network.py:198) at every cell: `forward_torso` itself has no mask
+        if (a.xys_out) *reinterpret_cast<float2*>(a.xys_out + 2 * (size_t)sweep_row) = bc;
+        a.alpha_out[n] = (1.f / (1.f + __expf(-o4[0]))) * 1.002f - 0.001f;
+        return;
+    }
     // occupancy = grid_sample(density_grid_torso, bg_coords, align_corners=True) (renderer.py:326), mask = occupancy > thresh;
     // alpha / colour = sigmoid(.) * 1.002 - 0.001 (network.py:198-199); bg = colour * alpha + bg * (1 - alpha) (renderer.py:343)
     const int G = a.G;
@@ -219,6 +263,53 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
     }
 }
 
+// ---- after the sweep: renderer.py:522-528 ------------------------------------------------------------------------------------------------------------
+constexpr int TG_T = 256;                 // threads per workgroup of k_torso_dilate_ema: one cell per lane (256 | G^2 for every size served)
+
+// F.max_pool2d(raw, kernel_size=5, stride=1, padding=2) (the padding is -inf: it never wins, and alpha can be -0.001), grid = max(grid * decay, pooled), and the
+// workgroup's fp64 sum of the new cells, added over LDS in a fixed tree (no floating-point atomics: the same bits on every run)
+__global__ __launch_bounds__(TG_T) void k_torso_dilate_ema(const float* __restrict__ raw, float* __restrict__ grid, int G, float decay, double* __restrict__ partials) {
+    __shared__ double s[TG_T];
+    const int n = blockIdx.x * TG_T + threadIdx.x, x = n % G, y = n / G;
+    float m = -INFINITY;
+    for (int dy = -2; dy <= 2; ++dy)
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            if (yy >= 0 && yy < G && xx >= 0 && xx < G) m = fmaxf(m, raw[yy * G + xx]);
+        }
+    const float g = fmaxf(grid[n] * decay, m);
+    grid[n] = g;
+    s[threadIdx.x] = (double)g;
+    __syncthreads();
+    for (int d = TG_T / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
+}
+
+// torch.mean(density_grid_torso) (renderer.py:528): the <= 64 partial sums added in index order by one lane
+__global__ void k_torso_grid_mean(const double* __restrict__ partials, int n_partials, double cells, float* __restrict__ mean_out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double acc = 0.0;
+    for (int i = 0; i < n_partials; ++i) acc += partials[i];
+    *mean_out = (float)(acc / cells);
+}
+
+void torso_args(TorsoFusedArgs& a, const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
+                float shrink, int G, int N) {
+    a.w = w; a.emb = emb;
+    for (int i = 0; i < HID; ++i) { a.bias_d[i] = bias_d[i]; a.bias_t[i] = bias_t[i]; }
+    for (int l = 0; l < NLEV; ++l) {
+        const float scale = exp2f((float)l * log2_pls) * (float)base_res - 1.0f;              // gridencoder.cu:123
+        a.scale[l] = scale;
+        a.resolution[l] = (uint32_t)std::ceil(scale) + 1;                                     // gridencoder.cu:124
+        a.offset[l] = (uint32_t)offsets_host[l];
+        a.hashmap_size[l] = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
+    }
+    a.shrink = shrink; a.G = G; a.N = N;
+}
+
 }  // namespace
 
 int mf_nerf_torso_fused_weight_count() { return W_TOTAL; }
@@ -228,18 +319,33 @@ int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float*
                                int base_res, const float* density, int G, const float* bg_coords, float shrink, float thresh, const float* bg,
                                int bg_per_ray, float bg_const, int N, float* out, float* alpha_out, float* deform, hipStream_t s) {
     TorsoFusedArgs a{};
-    a.bg_coords = bg_coords; a.w = w; a.emb = emb; a.density = density; a.bg = bg;
-    for (int i = 0; i < HID; ++i) { a.bias_d[i] = bias_d[i]; a.bias_t[i] = bias_t[i]; }
-    for (int l = 0; l < NLEV; ++l) {
-        const float scale = exp2f((float)l * log2_pls) * (float)base_res - 1.0f;              // gridencoder.cu:123
-        a.scale[l] = scale;
-        a.resolution[l] = (uint32_t)std::ceil(scale) + 1;                                     // gridencoder.cu:124
-        a.offset[l] = (uint32_t)offsets_host[l];
-        a.hashmap_size[l] = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
-    }
-    a.shrink = shrink; a.thresh = thresh; a.bg_const = bg_const; a.bg_per_ray = bg_per_ray; a.G = G; a.N = N;
+    torso_args(a, w, bias_d, bias_t, emb, offsets_host, log2_pls, base_res, shrink, G, N);
+    a.bg_coords = bg_coords; a.density = density; a.bg = bg;
+    a.thresh = thresh; a.bg_const = bg_const; a.bg_per_ray = bg_per_ray;
     a.out = out; a.alpha_out = alpha_out; a.deform = deform;
-    hipLaunchKernelGGL(k_torso_fused, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_torso_fused<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+// The torso grid's rebuild (mf_nerf_torso_grid_update, mf_nerf_net.hip, where the handle is defined): sweep, dilate + EMA, mean.  The served sizes were accepted by
+// mf_nerf_occupancy_shape; partials: G^2 / 256 doubles.
+int mf_nerf_torso_grid_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
+                              float shrink, int G, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out, float* mean,
+                              double* partials, hipStream_t s) {
+    const int cells = G * G;
+    TorsoFusedArgs a{};
+    torso_args(a, w, bias_d, bias_t, emb, offsets_host, log2_pls, base_res, shrink, G, cells);
+    a.alpha_out = raw_grid; a.noise = noise; a.xys_out = xys_out;
+    // `half_grid_size = 1 / self.grid_size` and `1 - half_grid_size` are Python floats (doubles), rounded when they meet the float32 tensor
+    const double half = 1.0 / (double)G;
+    a.inv_gm1 = 1.0f / (float)(G - 1); a.cell_scale = (float)(1.0 - half); a.cell_half = (float)half;
+    const int nwg = cells / TG_T;
+    hipLaunchKernelGGL(k_torso_fused<true>, dim3((unsigned)nwg), dim3(256), 0, s, a);
+    MF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_torso_dilate_ema, dim3((unsigned)nwg), dim3(TG_T), 0, s, raw_grid, density_grid, G, decay, partials);
+    MF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_torso_grid_mean, dim3(1), dim3(64), 0, s, partials, nwg, (double)cells, mean);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

@@ -54,6 +54,8 @@ class HipRenderMixin:
     _mf_frame_id = 0
     mf_frames = 0                      # frames rendered by the device loop (tests assert the fast route ran)
     mf_grid_updates = 0                # occupancy grids rebuilt by the device route
+    mf_torso_grid_updates = 0          # torso occupancy grids rebuilt by the device route
+    mf_marks = 0                       # mark_untrained_grid calls served by the device route
 
     def __init__(self, *args, **kwargs):
         # on a multi-GPU node the process takes its GPU here, before the reference's Trainer says `.to('cuda')` (placement.py)
@@ -125,6 +127,11 @@ class HipRenderMixin:
         r.ind_code = self.individual_codes[0].detach() if self.individual_dim > 0 else None
         if r.torso is not None:
             r.torso.thresh = float(min(self.density_thresh_torso, self.mean_density_torso))
+            # the grid too: the reference's torso update rebinds `self.density_grid_torso` (renderer.py:527), so the frame samples the tensor of the frame.  A module
+            # that carries the grid only in its state dict keeps the one the torso was built from
+            g = getattr(self, "density_grid_torso", None)
+            if torch.is_tensor(g):
+                r.torso.density_grid = g if r.torso._is_grid(g) else g.detach().to(dev, torch.float32).contiguous()
         with torch.no_grad():
             if self.emb:                                                # network.py:229-230: an embedding lookup in front of the audio net -- the reference's modules run it
                 enc_a = super().encode_audio(auds)
@@ -149,21 +156,56 @@ class HipRenderMixin:
         return res
 
 
-    # ---- occupancy-grid maintenance (renderer.py:421-539) ---------------------------------------------------------------------------
+    # ---- occupancy-grid maintenance (renderer.py:355-539) ---------------------------------------------------------------------------
+    def _mf_sizes_served(self):
+        from .renderer import HipHeadRenderer
+        return self.grid_size in HipHeadRenderer.GRID_SIZES and 1 <= self.cascade <= 8      # (the library checks the same rule: mf_nerf_occupancy_shape)
+
     def _mf_grid_fast_path(self):
-        if os.environ.get("MF_NERF_DROPIN", "1") == "0" or not self.cuda_ray or self.torso:
+        if os.environ.get("MF_NERF_DROPIN", "1") == "0" or not self.cuda_ray or not self._mf_sizes_served():
             return False
-        # what mf_nerf_density_grid_update does not serve goes the reference's way too: another grid size, a field without the fused kernel
-        if self.grid_size not in (32, 64, 128) or not 1 <= self.cascade <= 8 or os.environ.get("MF_NERF_FIELD") == "gemm":
+        if not (torch.is_tensor(self.density_grid) and self.density_grid.is_cuda and self.density_bitfield.is_cuda):
             return False
-        return torch.is_tensor(self.density_grid) and self.density_grid.is_cuda and self.density_bitfield.is_cuda
+        # what the two rebuilds do not serve goes the reference's way too: a field / torso without the fused kernel
+        if self.torso:
+            g = getattr(self, "density_grid_torso", None)
+            return os.environ.get("MF_TORSO") != "gemm" and torch.is_tensor(g) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()
+        return os.environ.get("MF_NERF_FIELD") != "gemm"
+
+    def _mf_state(self, dev):
+        st = self._mf
+        if st is None or st["device"] != dev or st["bitfield_ptr"] != self.density_bitfield.data_ptr():
+            st = self._mf_build(st["cap"] if st is not None else 1, dev)
+        return st
+
+    def mark_untrained_grid(self, poses, intrinsic, S=64):
+        """`NeRFRenderer.mark_untrained_grid` (renderer.py:356-416) as one launch (mf_nerf_mark_untrained) instead of the reference's five nested loops of batched
+        matmuls: cells no training camera sees become -1 in `self.density_grid`, in place.  Another grid size, CPU tensors, MF_NERF_DROPIN=0: the reference's method."""
+        if not self.cuda_ray:
+            return
+        import numpy as np
+        from .renderer import HipHeadRenderer
+        served = (os.environ.get("MF_NERF_DROPIN", "1") != "0" and self._mf_sizes_served() and torch.is_tensor(self.density_grid) and self.density_grid.is_cuda
+                  and self.density_grid.dtype == torch.float32 and self.density_grid.is_contiguous())
+        if not served:
+            return super().mark_untrained_grid(poses, intrinsic, S=S)
+        if isinstance(poses, np.ndarray):
+            poses = torch.from_numpy(poses)
+        with torch.no_grad():
+            dev = self.density_grid.device
+            # (no device objects are needed: the renderer is a holder of bound / grid_size here, as cheap as the call)
+            r = HipHeadRenderer(None, self.density_bitfield, bound=self.bound, grid_size=self.grid_size)
+            r.mark_untrained(self.density_grid, poses.to(dev, torch.float32), intrinsic, cascades=self.cascade)
+        self.__dict__["mf_marks"] = self.mf_marks + 1
 
     def update_extra_state(self, decay=0.95, S=128):
-        """`NeRFRenderer.update_extra_state` with the head grid rebuilt on the device (mf_nerf_density_grid_update: sweep, dilate + EMA, reduce + pack: three
-        kernels, after the jitter's `torch.rand` draws).  The selection statements are the reference's own and consume the same Python / torch random streams, so both routes rebuild from the same
-        audio window, eye value and jitter.  Torso training, CPU tensors, MF_NERF_DROPIN=0: the reference's method runs, over the extension shims
-        (`morton3D`, `morton3D_dilation`, `packbits`), the torso grid branch of :488-528 included.  `mark_untrained_grid` and `reset_extra_state` need no
-        override: they are torch statements over the same shims and buffers."""
+        """`NeRFRenderer.update_extra_state` with the grid rebuilt on the device: the head grid (mf_nerf_density_grid_update: sweep, dilate + EMA, reduce + pack) or,
+        for a torso model, the torso grid (mf_nerf_torso_grid_update: sweep, 5 x 5 dilate + EMA, mean) -- three kernels each, after the jitter's `torch.rand` draws.
+        The selection statements are the reference's own and consume the same Python / torch random streams, so both routes rebuild from the same audio window, eye
+        value, pose, code row and jitter.  CPU tensors, another grid size, MF_TORSO=gemm / MF_NERF_FIELD=gemm, MF_NERF_DROPIN=0: the reference's method runs, over
+        the extension shims (`morton3D`, `morton3D_dilation`, `packbits`)."""
+        if not self.cuda_ray:
+            return
         if not self._mf_grid_fast_path():
             return super().update_extra_state(decay=decay, S=S)
         dev = self.density_bitfield.device
@@ -171,38 +213,54 @@ class HipRenderMixin:
         mro = type(self).__mro__
         owner = next(c for c in mro[mro.index(HipRenderMixin) + 1:] if "update_extra_state" in vars(c))
         get_audio_features = getattr(sys.modules[owner.__module__], "get_audio_features")
+        H, Cn = self.grid_size, self.cascade
+        steps = [(i, min(i + S, H)) for i in range(0, H, S)]
         with torch.no_grad():
             rand_idx = random.randint(0, self.aud_features.shape[0] - 1)                              # renderer.py:428-432
             auds = get_audio_features(self.aud_features, self.att, rand_idx).to(dev)
             enc_a = self.encode_audio(auds)
-            eye = float(self.eye_area[[rand_idx]].reshape(-1)[0]) if self.exp_eye else None           # :440-443 (eye_area lives on the host)
-            # the jitter of :467, drawn block by block and cascade by cascade as the reference's loops draw it
-            H, Cn = self.grid_size, self.cascade
-            steps = [(i, min(i + S, H)) for i in range(0, H, S)]
-            noise = torch.empty(Cn, H, H, H, 3, device=dev)
-            if len(steps) == 1:                                                                       # S >= grid_size (the reference's default): one draw per cascade, in place
-                for cas in range(Cn):
-                    torch.rand(H ** 3, 3, out=noise[cas].view(H ** 3, 3))
+            if self.torso:
+                rand_idx = random.randint(0, self.poses.shape[0] - 1)                                 # :492-499
+                pose = self.poses[[rand_idx]]
+                ind_code = self.individual_codes_torso[[rand_idx]].detach() if self.opt.ind_dim_torso > 0 else None
+                # the jitter of :514, drawn block by block as the reference's two loops draw it
+                noise = torch.empty(H, H, 2, device=dev)
+                if len(steps) == 1:                                                                   # S >= grid_size (the reference's default): one draw, in place
+                    torch.rand(H ** 2, 2, out=noise.view(H ** 2, 2))
+                else:
+                    for x0, x1 in steps:
+                        for y0, y1 in steps:
+                            noise[x0:x1, y0:y1] = torch.rand((x1 - x0) * (y1 - y0), 2, device=dev).view(x1 - x0, y1 - y0, 2)
+                torso = self._mf_state(dev)["renderer"].torso
+                mean = torso.update_density_grid(self.density_grid_torso, pose, ind_code, noise.view(H ** 2, 2), decay=decay)
             else:
-                for x0, x1 in steps:
-                    for y0, y1 in steps:
-                        for z0, z1 in steps:
-                            for cas in range(Cn):
-                                noise[cas, x0:x1, y0:y1, z0:z1] = torch.rand((x1 - x0) * (y1 - y0) * (z1 - z0), 3, device=dev).view(x1 - x0, y1 - y0, z1 - z0, 3)
-            st = self._mf
-            if st is None or st["device"] != dev or st["bitfield_ptr"] != self.density_bitfield.data_ptr():
-                st = self._mf_build(st["cap"] if st is not None else 1, dev)
-            r = st["renderer"]
-            r.bitfield, r.density_scale = self.density_bitfield, float(self.density_scale)
-            mean = r.update_density_grid(self.density_grid, enc_a, eye=eye, decay=decay, density_thresh=float(self.density_thresh), noise=noise.view(Cn, H ** 3, 3),
-                                         cascades=Cn)
-        self.mean_density = mean.item()                                                               # :480, the one sync the reference has too
-        self.iter_density += 1
+                eye = float(self.eye_area[[rand_idx]].reshape(-1)[0]) if self.exp_eye else None       # :440-443 (eye_area lives on the host)
+                # the jitter of :467, drawn block by block and cascade by cascade as the reference's loops draw it
+                noise = torch.empty(Cn, H, H, H, 3, device=dev)
+                if len(steps) == 1:                                                                   # S >= grid_size (the reference's default): one draw per cascade, in place
+                    for cas in range(Cn):
+                        torch.rand(H ** 3, 3, out=noise[cas].view(H ** 3, 3))
+                else:
+                    for x0, x1 in steps:
+                        for y0, y1 in steps:
+                            for z0, z1 in steps:
+                                for cas in range(Cn):
+                                    noise[cas, x0:x1, y0:y1, z0:z1] = torch.rand((x1 - x0) * (y1 - y0) * (z1 - z0), 3, device=dev).view(x1 - x0, y1 - y0, z1 - z0, 3)
+                r = self._mf_state(dev)["renderer"]
+                r.bitfield, r.density_scale = self.density_bitfield, float(self.density_scale)
+                mean = r.update_density_grid(self.density_grid, enc_a, eye=eye, decay=decay, density_thresh=float(self.density_thresh), noise=noise.view(Cn, H ** 3, 3),
+                                             cascades=Cn)
+        if self.torso:
+            self.mean_density_torso = mean.item()                                                     # :528, the one sync the reference has too
+            self.__dict__["mf_torso_grid_updates"] = self.mf_torso_grid_updates + 1
+        else:
+            self.mean_density = mean.item()                                                           # :480, the one sync the reference has too
+            self.iter_density += 1
+            self.__dict__["mf_grid_updates"] = self.mf_grid_updates + 1
         total_step = min(16, self.local_step)                                                         # :533-537
         if total_step > 0:
             self.mean_count = int(self.step_counter[:total_step, 0].sum().item() / total_step)
         self.local_step = 0
-        self.__dict__["mf_grid_updates"] = self.mf_grid_updates + 1
 
 
 def load_reference_module(shadow_name, shadow_file, package):

@@ -163,7 +163,13 @@ class HipHeadRenderer:
         hit[0].replay()
         return hit[1]
 
-    GRID_SIZES = (32, 64, 128)          # what mf_nerf_density_grid_update serves (the reference always uses 128)
+    GRID_SIZES = (32, 64, 128)          # what the grid-maintenance entry points serve (the reference always uses 128); the library's rule: mf_nerf_occupancy_shape
+
+    @classmethod
+    def check_grid_size(cls, grid_size, who):
+        """The one statement of the served sizes on the Python side: head rebuild, torso rebuild and mark_untrained all ask here."""
+        if grid_size not in cls.GRID_SIZES:
+            raise RuntimeError(f"{who}: grid_size {grid_size} is not served (32, 64 or 128)")
 
     @torch.no_grad()
     def update_density_grid(self, density_grid, enc_a, eye=None, decay=0.95, density_thresh=10.0, noise=None, cascades=None, tmp_grid=None, xyzs_out=None):
@@ -178,8 +184,7 @@ class HipHeadRenderer:
         [cascades, grid_size^3, 3] fp32 buffers that keep the sweep's raw values and positions (Morton order).
         Returns mean_density as a 0-d float64 device tensor."""
         H = self.grid_size
-        if H not in self.GRID_SIZES:
-            raise RuntimeError(f"HipHeadRenderer.update_density_grid: grid_size {H} is not served (32, 64 or 128)")
+        self.check_grid_size(H, "HipHeadRenderer.update_density_grid")
         cascades = self.cascade if cascades is None else int(cascades)
         if not 1 <= cascades <= 8:
             raise RuntimeError(f"HipHeadRenderer.update_density_grid: cascades {cascades} outside 1..8")
@@ -212,6 +217,30 @@ class HipHeadRenderer:
                                                          self.density_scale, float(decay), float(density_thresh), p(noise), p(tmp_grid), p(xyzs_out), p(mean),
                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_density_grid_update")
         return mean
+
+    @torch.no_grad()
+    def mark_untrained(self, density_grid, poses, intrinsic, cascades=None):
+        """`NeRFRenderer.mark_untrained_grid` (renderer.py:356-416) as one launch (mf_nerf_mark_untrained): a cell of the Morton-ordered
+        density_grid [cascades, grid_size^3] (CUDA fp32, in place) whose centre no camera sees inside its frustum, widened by a cell, becomes -1;
+        every other cell keeps its bits.  poses: [B, 4, 4] camera-to-world CUDA fp32, B >= 1; intrinsic: (fx, fy, cx, cy)."""
+        H = self.grid_size
+        self.check_grid_size(H, "HipHeadRenderer.mark_untrained")
+        cascades = self.cascade if cascades is None else int(cascades)
+        if not 1 <= cascades <= 8:
+            raise RuntimeError(f"HipHeadRenderer.mark_untrained: cascades {cascades} outside 1..8")
+        cells = cascades * H ** 3
+        if not (torch.is_tensor(density_grid) and density_grid.is_cuda and density_grid.dtype == torch.float32 and density_grid.is_contiguous()
+                and density_grid.numel() == cells):
+            raise RuntimeError(f"HipHeadRenderer.mark_untrained: density_grid must be a contiguous float32 CUDA tensor with {cells} elements (there is no CPU path)")
+        if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float32 and poses.dim() == 3 and tuple(poses.shape[1:]) == (4, 4)):
+            raise RuntimeError("HipHeadRenderer.mark_untrained: poses must be a float32 CUDA tensor [B, 4, 4] (there is no CPU path)")
+        if poses.shape[0] < 1:
+            raise RuntimeError("HipHeadRenderer.mark_untrained: no poses: with none every cell would be marked untrained")
+        poses = poses.contiguous()
+        fx, fy, cx, cy = (float(v) for v in intrinsic)
+        _lib.check(self._lib.mf_nerf_mark_untrained(C.c_void_p(poses.data_ptr()), int(poses.shape[0]), fx, fy, cx, cy, self.bound, cascades, H,
+                                                    C.c_void_p(density_grid.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "mf_nerf_mark_untrained")
 
     @torch.no_grad()
     def run_cuda(self, rays_o, rays_d, enc_a, ind_code, eye, bg_color=None, dt_gamma=1 / 256, max_steps=16, T_thresh=1e-4, perturb=False,

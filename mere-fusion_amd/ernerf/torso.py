@@ -5,7 +5,11 @@
     bg = torso.run_torso(bg_coords, poses, bg_color)["bg_color"]         # what run_cuda mixes the head over, renderer.py:272-275
 
 Every pixel runs through the two small MLPs and the occupancy mask is applied in the final mix (no boolean-mask gather/scatter, no
-host sync); the frequency-encoded wrapped anchors and the individual code are per-frame constants folded into first-layer biases."""
+host sync); the frequency-encoded wrapped anchors and the individual code are per-frame constants folded into first-layer biases.
+
+The occupancy grid `density_grid_torso` is not copied: `run_torso` samples the device tensor it is handed for the frame (`self.density_grid`
+by default), because the reference rebinds that attribute at every torso `update_extra_state` (renderer.py:527).  `update_density_grid`
+is that update on the device (mf_nerf_torso_grid_update)."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +17,7 @@ import torch
 
 from .. import _lib
 from .field import grid_geometry
+from .renderer import HipHeadRenderer
 
 
 def freq_encode_host(x, degree):
@@ -57,6 +62,19 @@ class HipTorso:
         codes = state_dict.get("individual_codes_torso")
         self.ind_code = codes[0].detach().float().cpu() if (codes is not None and individual_dim > 0) else None      # renderer.py:318-319
         self.thresh = float(min(density_thresh_torso, mean_density_torso))                                           # renderer.py:325
+        self.grid_size = int(grid_size)
+        # the grid the frames sample: the caller's own tensor when it already lives on the device (borrowed, never copied), an upload of it otherwise
+        g = state_dict["density_grid_torso"].detach()
+        self.density_grid = g if self._is_grid(g) else g.to(self.device, torch.float32).contiguous()
+
+    def _is_grid(self, g):
+        return torch.is_tensor(g) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == self.grid_size ** 2
+
+    def _grid(self, g, who):
+        if not self._is_grid(g):
+            raise RuntimeError(f"HipTorso.{who}: density_grid must be a contiguous float32 CUDA tensor with {self.grid_size ** 2} elements "
+                               f"(got {getattr(g, 'dtype', type(g))}, {tuple(getattr(g, 'shape', ()))}, {getattr(g, 'device', None)}); there is no CPU path")
+        return g
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -65,8 +83,9 @@ class HipTorso:
             self._h = None
 
     @torch.no_grad()
-    def run_torso(self, bg_coords, poses, bg_color=None):
-        """bg_coords: [N, 2] (or [1, N, 2]) CUDA fp32 in [-1, 1]; poses: [1, 4, 4]; bg_color: [N, 3] / [3] tensor, scalar or None (= 1)."""
+    def run_torso(self, bg_coords, poses, bg_color=None, density_grid=None):
+        """bg_coords: [N, 2] (or [1, N, 2]) CUDA fp32 in [-1, 1]; poses: [1, 4, 4]; bg_color: [N, 3] / [3] tensor, scalar or None (= 1);
+        density_grid: the [grid_size^2] CUDA fp32 occupancy grid this frame samples (renderer.py:326), None = self.density_grid."""
         if not (torch.is_tensor(bg_coords) and bg_coords.is_cuda):
             raise RuntimeError("HipTorso.run_torso: bg_coords must be a CUDA tensor (there is no CPU path)")
         xy = bg_coords.contiguous().view(-1, 2).float()
@@ -79,7 +98,45 @@ class HipTorso:
         bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
         per_ray = bg is not None and bg.numel() == 3 * N
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        grid = self._grid(self.density_grid if density_grid is None else density_grid, "run_torso")
+        _lib.check(self._lib.mf_nerf_torso_set_grid(self._h, p(grid)), "mf_nerf_torso_set_grid")
         _lib.check(self._lib.mf_nerf_torso_forward(self._h, p(xy), cbuf, p(bg), int(per_ray), float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color)),
                                                    self.thresh, N, p(out), p(alpha), p(deform), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                    "mf_nerf_torso_forward")
         return {"bg_color": out, "torso_alpha": alpha.view(N, 1), "deform": deform}
+
+    @torch.no_grad()
+    def update_density_grid(self, grid, poses, ind_code, noise, decay=0.95, raw_out=None, xys_out=None):
+        """The torso branch of `NeRFRenderer.update_extra_state` (renderer.py:488-528) on the device, three launches and no host sync
+        (mf_nerf_torso_grid_update): `forward_torso`'s alpha swept over the grid_size^2 jittered cell centres of :511-514, the 5 x 5 max pool,
+        grid = max(grid * decay, pooled), the mean.
+
+        grid: `density_grid_torso`, [grid_size^2] CUDA fp32, updated in place; it is also the grid later `run_torso` calls sample.  poses: the
+        [1, 4, 4] pose of :494; ind_code: the [1, ind_dim_torso] row of :497 (None without a code); noise: [grid_size^2, 2] uniform numbers in
+        the reference's meshgrid order (row x * grid_size + y: what its `torch.rand_like` draws, :514), None samples the cell centres.
+        raw_out / xys_out: optional [grid_size^2] / [grid_size^2, 2] fp32 buffers that keep the sweep's raw alpha (row y * grid_size + x, as the
+        grid) and its positions (meshgrid order).  Returns mean_density_torso as a 0-d float32 device tensor."""
+        G = self.grid_size
+        HipHeadRenderer.check_grid_size(G, "HipTorso.update_density_grid")
+        self._grid(grid, "update_density_grid")
+
+        def dev_f32(t, name, numel):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+                raise RuntimeError(f"HipTorso.update_density_grid: {name} must be a contiguous float32 CUDA tensor with {numel} elements")
+            return t
+        if noise is not None:
+            dev_f32(noise, "noise", 2 * G * G)
+        raw = torch.empty(G * G, device=grid.device) if raw_out is None else dev_f32(raw_out, "raw_out", G * G)
+        if xys_out is not None:
+            dev_f32(xys_out, "xys_out", 2 * G * G)
+        code = ind_code if self.ind_code is not None else None
+        if self.ind_code is not None and (code is None or torch.as_tensor(code).numel() != self.ind_code.numel()):
+            raise RuntimeError(f"HipTorso.update_density_grid: ind_code must have {self.ind_code.numel()} elements (the torso nets were built with a code)")
+        consts = wrapped_anchor_code(self.anchor_points, poses, code)
+        cbuf = (C.c_float * len(consts))(*consts.tolist())
+        mean = torch.empty((), dtype=torch.float32, device=grid.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.mf_nerf_torso_grid_update(self._h, cbuf, p(noise), float(decay), p(grid), p(raw), p(xys_out), p(mean),
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_torso_grid_update")
+        self.density_grid = grid
+        return mean
