@@ -433,6 +433,27 @@ void mf_nerf_field_destroy(mf_nerf_field* h);
 int mf_nerf_resize_frame(const float* image, const float* depth, int h, int w, int H, int W, float* out_image, float* out_depth,
                          uint8_t* frame_u8, void* stream);
 
+/* `NeRFDataset_Test.collate`, provider.py:316-330 (the default deployment: --torso_imgs with a head-only model, app.py:368-369): the frame's torso image
+ * over the background, bg_color = rgb * a + bg * (1 - a) (provider.py:323), as one launch.  torso_rgba: device uint8 [H,W,4] RGBA (4-byte aligned);
+ * bg_image: device fp32 [H,W,3], or NULL for the constant bg_const in every channel (`--bg_img white` / `black`, provider.py:203-206);
+ * bg_color: device fp32 [H*W,3].  The bits are those of the torch expression: half_mode == 0 (preload 0 / 1) t = float(u8) / 255 as
+ * `astype(np.float32) / 255` gives (provider.py:186, 321), then product, 1 - a, product, sum, each rounded to fp32; half_mode != 0 (preload 2: torso_img
+ * and bg_img are half tensors, provider.py:198, 238) t = half(float(u8) / 255), bg = half(bg), each of the four operations computed in fp32 and
+ * rounded to half, the result widened to fp32. */
+int mf_nerf_frame_background(const uint8_t* torso_rgba, const float* bg_image, float bg_const, int H, int W, int half_mode, float* bg_color,
+                             void* stream);
+/* The rest of one `nerfreal.py` frame behind the render, as one launch that ends in the uint8 RGB frame a VideoFrame takes: the resize of
+ * `Trainer.test_gui_with_data` (utils.py:1208-1212; linear_to_srgb != 0 applies utils.py:78-81 to the render first, as :1208-1209 orders it),
+ * `(image * 255).astype(np.uint8)` (nerfreal.py:110) and, with a body frame, the --fullbody paste and its cvtColor (nerfreal.py:117-122).
+ * render: device fp32 [h,w,3] or NULL; (H, W): the GUI size; body_bgr: device uint8 BGR [FH,FW,3] or NULL; (x0, y0): opt.fullbody_offset_x / _y.
+ * frame_rgb: device uint8 RGB [FH,FW,3], or [H,W,3] without a body frame (FH, FW, x0, y0 are then ignored and must leave the offset at 0).
+ * Inside the [H,W] rectangle at (x0, y0) a pixel is mf_nerf_resize_frame's frame_u8 of the same render, bit for bit (one device function serves both); outside
+ * it the body pixel with its channels reversed.  render NULL: the whole output is the channel-reversed body_bgr -- the custom-video frame of
+ * nerfreal.py:98-107.  A rectangle that leaves the body frame is MF_ERR_INVALID with both sizes in mf_last_error, as the reference's slice assignment
+ * raises; nothing is clipped. */
+int mf_nerf_frame_out(const float* render, int h, int w, int H, int W, const uint8_t* body_bgr, int FH, int FW, int x0, int y0, int linear_to_srgb,
+                      uint8_t* frame_rgb, void* stream);
+
 /* ---- ER-NeRF head frame without host round trips ----------------------------------------------- */
 typedef struct mf_nerf_head mf_nerf_head;
 /* Scratch for up to max_rays rays over `field` (which must outlive the head and use the fused field kernel). */
@@ -461,6 +482,10 @@ int mf_nerf_head_finish(mf_nerf_head* h, int n_rays, const float* bg_color, int 
  * later mf_nerf_head_render on `h` instead of its by-value `eye` argument: no host copy of a value that lives on the device, and a captured graph follows a changing
  * value.  NULL: back to the by-value argument.  The float must stay valid until the renders that use it have finished. */
 int mf_nerf_head_set_eye(mf_nerf_head* h, const float* eye_dev);
+/* `self.aabb_infer` (renderer.py:86-89, a persistent buffer a checkpoint may carry) read from DEVICE memory by every later mf_nerf_head_render on `h`
+ * (near / far, raymarching.py:44) instead of the box the head derives from the field's bound: aabb_dev is device fp32 [6] (xmin, ymin, zmin, xmax, ymax,
+ * zmax) and must stay valid until the renders that use it have finished.  NULL, or never called: the box from `bound`, as before. */
+int mf_nerf_head_set_aabb(mf_nerf_head* h, const float* aabb_dev);
 /* Rounds of a frame enqueued as (march, field, composite) launches before the tail launch.  _plan_rounds returns what the next mf_nerf_head_render would
  * choose from the round counts earlier frames posted (device -> pinned host word, read without a sync); _set_rounds(r >= 0) pins the count -- a caller that
  * captures the enqueue in a hipGraph pins what it keyed the graph on -- and _set_rounds(-1) returns to following the feedback.  _last_rounds: the round count

@@ -187,11 +187,14 @@ SIGNATURES = {
     "mf_nerf_density_grid_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_int, C.c_float,
                                               C.c_float, C.c_float] + [C.c_void_p] * 5),
     "mf_nerf_resize_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_nerf_frame_background": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mf_nerf_frame_out": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "mf_nerf_head_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mf_nerf_head_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 5),
     "mf_nerf_head_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 5),
     "mf_nerf_head_set_eye": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mf_nerf_head_set_aabb": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mf_nerf_head_sums": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "mf_nerf_head_plan_rounds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "mf_nerf_head_set_rounds": (C.c_int, [C.c_void_p, C.c_int]),

@@ -13,6 +13,7 @@
 #include "mf_common.h"
 #include "mf_nerf_grid.h"
 #include "mf_nerf_march.h"
+#include "mf_nerf_frame.h"
 #include <cstdlib>
 #include <cstring>
 #include <cfloat>
@@ -335,21 +336,18 @@ __global__ __launch_bounds__(NT) void k_nerf_resize(const float* __restrict__ im
     const int i = threadIdx.x + blockIdx.x * NT;
     if (i >= H * W) return;
     const int oy = i / W, ox = i - oy * W;
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    float fy = fmaf(sy, (float)oy + 0.5f, -0.5f), fx = fmaf(sx, (float)ox + 0.5f, -0.5f);     // fused, as aten's builds contract it
-    fy = fy < 0.f ? 0.f : fy; fx = fx < 0.f ? 0.f : fx;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly1 = fy - (float)y0, ly0 = 1.f - ly1, lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+    const NerfBilinearTaps t = nerf_bilinear_taps(oy, ox, h, w, H, W);                        // mf_nerf_frame.h, shared with k_nerf_frame_out
+    const int y0 = t.y0, x0 = t.x0, y1 = t.y1, x1 = t.x1;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float p00 = image[((size_t)y0 * w + x0) * 3 + k], p01 = image[((size_t)y0 * w + x1) * 3 + k];
         const float p10 = image[((size_t)y1 * w + x0) * 3 + k], p11 = image[((size_t)y1 * w + x1) * 3 + k];
-        const float v = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+        const float v = nerf_bilinear_blend(t, p00, p01, p10, p11);
         if (out_image) out_image[(size_t)i * 3 + k] = v;
-        if (frame) frame[(size_t)i * 3 + k] = (uint8_t)(v * 255.f);
+        if (frame) frame[(size_t)i * 3 + k] = nerf_frame_u8(v);
     }
     if (out_depth) {
+        const float sy = (float)h / (float)H, sx = (float)w / (float)W;
         int ny = (int)floorf((float)oy * sy), nx = (int)floorf((float)ox * sx);
         ny = ny < h - 1 ? ny : h - 1; nx = nx < w - 1 ? nx : w - 1;
         out_depth[i] = depth[(size_t)ny * w + nx];

@@ -701,6 +701,7 @@ struct mf_nerf_head {
     float *aabb, *nears, *fars, *rays_t, *xyzs, *dirs, *deltas, *sig, *rgb, *aa, *ae, *un, *wsum, *aasum, *aesum, *unsum;
     int *alive[2], *ctl;
     const float* eye_dev = nullptr;      // mf_nerf_head_set_eye: the eye feature stays on the device
+    const float* aabb_user = nullptr;    // mf_nerf_head_set_aabb: the caller's aabb_infer (device), read instead of `aabb` below
     // round-count feedback: two words of pinned host memory the device posts to when a frame's loop ends ([0] rounds the frame ran, [1] the tail's error flag);
     // read without a sync, so it tells about a frame that finished some calls ago
     volatile int* fb = nullptr;
@@ -784,8 +785,8 @@ extern "C" int mf_nerf_head_render(mf_nerf_head* h, const float* rays_o, const f
     float* ws = weights_sum ? weights_sum : h->wsum;
     int rc;
     // near / far (raymarching.cu:92-145) inside the loop's init launch
-    if ((rc = mf_nerf_loop_init(h->ctl, N, max_steps, h->alive[0], h->rays_t, h->nears, ws, depth, image, h->aasum, h->aesum, h->unsum, s, rays_o, rays_d, h->aabb, min_near,
-                                h->fars)))
+    if ((rc = mf_nerf_loop_init(h->ctl, N, max_steps, h->alive[0], h->rays_t, h->nears, ws, depth, image, h->aasum, h->aesum, h->unsum, s, rays_o, rays_d,
+                                h->aabb_user ? h->aabb_user : h->aabb, min_near, h->fars)))
         return rc;
     const bool x3 = f->precision == MF_PREC_BF16X3;
     // at least one sample per alive ray and round, so max_steps rounds always suffice (step += n_step >= 1, renderer.py:270)
@@ -829,6 +830,12 @@ extern "C" int mf_nerf_head_finish(mf_nerf_head* h, int n_rays, const float* bg_
 extern "C" int mf_nerf_head_set_eye(mf_nerf_head* h, const float* eye_dev) {
     MF_REQUIRE(h, "nerf_head_set_eye: null handle");
     h->eye_dev = eye_dev;
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_set_aabb(mf_nerf_head* h, const float* aabb_dev) {
+    MF_REQUIRE(h, "nerf_head_set_aabb: null handle");
+    h->aabb_user = aabb_dev;
     return MF_OK;
 }
 

@@ -125,6 +125,18 @@ class HipRenderMixin:
         # assigns mean_density_torso, the GUI density_scale)
         r.bitfield, r.density_scale = self.density_bitfield, float(self.density_scale)
         r.ind_code = self.individual_codes[0].detach() if self.individual_dim > 0 else None
+        # the box of near / far is a persistent buffer a checkpoint may carry (renderer.py:86-89, read at :226): the head reads the module's own tensor
+        ab = getattr(self, "aabb_infer", None)
+        if torch.is_tensor(ab):
+            ab = ab.detach()
+            if not (ab.dtype == torch.float32 and ab.device == dev and ab.is_contiguous()):
+                # (a `.half()`ed module, a host buffer) the values of the frame go into ONE fp32 copy kept with the device objects: its address does not change from
+                # frame to frame, so a captured graph keyed on it stays one graph
+                if st.get("aabb") is None:
+                    st["aabb"] = torch.empty(6, dtype=torch.float32, device=dev)
+                st["aabb"].copy_(ab.reshape(6))
+                ab = st["aabb"]
+            r.aabb_infer = ab
         if r.torso is not None:
             r.torso.thresh = float(min(self.density_thresh_torso, self.mean_density_torso))
             # the grid too: the reference's torso update rebinds `self.density_grid_torso` (renderer.py:527), so the frame samples the tensor of the frame.  A module

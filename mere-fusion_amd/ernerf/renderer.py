@@ -25,6 +25,7 @@ class HipHeadRenderer:
         self.bitfield = density_bitfield.contiguous()
         b = self.bound
         self.aabb_infer = torch.tensor([-b, -b / 2, -b, b, b / 2, b], dtype=torch.float32, device=density_bitfield.device)   # renderer.py:86-89
+        self._aabb_default = self.aabb_infer        # rebinding `aabb_infer` (a checkpoint's buffer: HipRenderMixin does, and NerfSession for a bare renderer) makes the device loop read it too
         self._lib = _lib.lib()
         self._head, self._side = None, None
 
@@ -118,6 +119,12 @@ class HipHeadRenderer:
         ev = 0.0 if (eye is None or eye_dev is not None) else float(eye.reshape(-1)[0])
         self._eye_keep = eye_dev
         _lib.check(self._lib.mf_nerf_head_set_eye(self._head, p(eye_dev)), "mf_nerf_head_set_eye")
+        # the box of near / far: the reference reads its persistent buffer `self.aabb_infer` every frame (renderer.py:226); the head reads a rebound one where it
+        # lives (mf_nerf_head_set_aabb).  Never rebound: the head's own box from `bound`, as before
+        aabb = None if self.aabb_infer is self._aabb_default else self.aabb_infer
+        if aabb is not None and not (torch.is_tensor(aabb) and aabb.is_cuda and aabb.dtype == torch.float32 and aabb.is_contiguous() and aabb.numel() == 6):
+            raise RuntimeError("HipHeadRenderer: aabb_infer must be a contiguous float32 CUDA tensor of 6 values (there is no CPU path)")
+        _lib.check(self._lib.mf_nerf_head_set_aabb(self._head, p(aabb)), "mf_nerf_head_set_aabb")
 
         def enqueue(out):
             _lib.check(self._lib.mf_nerf_head_render(self._head, p(rays_o), p(rays_d), N, p(self.bitfield), self.cascade, self.grid_size, self.min_near,
@@ -137,7 +144,7 @@ class HipHeadRenderer:
         planned = C.c_int(0)
         _lib.check(self._lib.mf_nerf_head_plan_rounds(self._head, int(max_steps), C.byref(planned)), "mf_nerf_head_plan_rounds")
         key = (N, ev, eye_dev is not None, bool(want_u8), bgc, bool(finish), None if bg is None else bg.numel(), float(dt_gamma), int(max_steps), float(T_thresh),
-               planned.value)
+               None if aabb is None else aabb.data_ptr(), planned.value)
         hit = self._graphs.get(key)
         live = (rays_o, rays_d, ea, ic, bg, eye_dev)
         if hit is None:
