@@ -14,6 +14,8 @@
 #include <vector>
 #include <utility>
 
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
 struct ActBuf {
     int C = 0, H = 0, W = 0, halo = 0;
     bf16_t* hi = nullptr;
@@ -129,6 +131,18 @@ int mf_halo_w_launch(const HaloArgs& a, const HaloTile& t, bool x3, hipStream_t 
 struct ConvTile { int bm, bn, wgm, wgn, nsplit; };
 struct ConvTuned { ConvTile tile; int ld; };   // a measured launch configuration (mf_conv_tune)
 
+// The tiles k_conv_igemm is compiled for, listed ONCE: mf_igemm_launch dispatches over exactly these rows.  The tunable rows, in this order, are what the tuning
+// table may name (mf_conv_tuned_valid), what the cost model prices (mf_conv_pick_tile) and what mf_conv_tune measures; the others are the narrow tiles that
+// mf_conv_pick_tile and mf_gemm_grouped_launch take by shape (cout <= 16, cout <= 32, <= 16 pixels).  resident: workgroups per CU as the cost model counts them
+// (0: never priced).  128 x 80 is the producer-wave tile (launch_pw_only).
+struct IgemmTile { int bm, bn, wgm, wgn, resident; bool tunable; };
+constexpr IgemmTile MF_IGEMM_TILES[] = {{64, 64, 2, 2, 2, true},   {128, 64, 2, 2, 2, true},  {128, 128, 2, 2, 2, true}, {256, 128, 4, 2, 1, true}, {256, 256, 2, 4, 1, true},
+                                        {128, 80, 4, 1, 1, true},  {128, 16, 4, 1, 0, false}, {128, 32, 4, 1, 0, false}, {16, 64, 1, 4, 0, false}};
+// ... and once more as literals, which template arguments need: X(row, BM, BN, WGM, WGN).  mf_conv.hip checks every row and the count against the table at compile time.
+#define MF_IGEMM_TILE_LIST(X) X(0, 64, 64, 2, 2) X(1, 128, 64, 2, 2) X(2, 128, 128, 2, 2) X(3, 256, 128, 4, 2) X(4, 256, 256, 2, 4) X(5, 128, 80, 4, 1) X(6, 128, 16, 4, 1) X(7, 128, 32, 4, 1) X(8, 16, 64, 1, 4)
+// split-K depths the cost model prices and mf_conv_tune measures
+constexpr int MF_CONV_SPLITS[] = {1, 2, 3, 4, 6, 8, 12, 16};
+
 struct ConvPlan {
     mf_conv2d_desc d{};
     int precision = 0;
@@ -185,6 +199,28 @@ struct ConvPlan {
     std::map<int, ConvTuned> tuned;           // batch -> configuration measured on this device (mf_conv_tune); empty: the cost model decides
 };
 
+// the shortest phase's K tiles: a split deeper than this cannot launch
+inline int kt_min(const ConvPlan* p) {
+    int k = p->ph[0].KT;
+    for (int ph = 1; ph < p->nphase; ++ph) k = p->ph[ph].KT < k ? p->ph[ph].KT : k;
+    return k;
+}
+
+// element offset of a view's first interior pixel (halo ring skipped, channel offset applied) in its buffer
+inline int64_t view_origin(const ActView& v) { return ((int64_t)v.buf->halo * v.buf->Wp() + v.buf->halo) * v.buf->C + v.coff; }
+// residual pointers and unit-grid strides of a ConvArgs / HaloArgs
+template <class Args>
+void set_residual(Args& a, const ActView& res, bool x3) {
+    const ActBuf& b = *res.buf;
+    a.r_hi = b.hi + view_origin(res); a.r_lo = x3 ? b.lo + view_origin(res) : nullptr;
+    a.rb = b.per_batch(); a.ri = b.Wp() * b.C; a.rj = b.C;
+}
+
+// MF_FORCE_TILE=128x64, MF_FORCE_SPLIT=4, MF_FORCE_LD=2 (exploration, tools/unet_shape_sweep.py), read once.  any: one of them is set -- the tuning table then serves
+// no layer; tile = bm * 1000 + bn, split: 0 = not set; ld: -1 = not set
+struct ConvForce { bool any; int tile, split, ld; };
+const ConvForce& mf_conv_force();
+
 // Folds BN, packs weights, uploads.  Returns mf_status.
 int mf_conv_plan_create(ConvPlan* p, const mf_conv2d_desc& d, const float* weight, const float* bias,
                         const float* bn_gamma, const float* bn_beta, const float* bn_mean,
@@ -195,7 +231,7 @@ void mf_conv_plan_destroy(ConvPlan* p);
 // row stride = Wp*C).  Must be called once before launch; rebinding to another geometry is allowed.
 int mf_conv_bind(ConvPlan* p, const ActBuf& in);
 
-// The launch configuration mf_conv_launch runs at a batch, resolved in ONE place: conv_launch_impl launches what this returns, and mf_conv_kernel_name /
+// The launch configuration mf_conv_launch runs at a batch, resolved in ONE place (mf_conv_launch.hip): conv_launch_impl launches what this returns, and mf_conv_kernel_name /
 // mf_conv2d_launch_config report it.  family: MF_CONV_FAMILY_* (include/merefusion.h); tile: implicit GEMM bm, bn, wgm, wgn and the split that launches
 // (after every clamp), halo families patch rows, channels, waves and the channel split; ld: the operand path that runs (-1 resolved; -1 outside the implicit
 // GEMM); bk: K depth of one stage (halo families: the channel slice); stats: where the GroupNorm statistics of a launch with `stats_groups` > 0 come from
@@ -210,8 +246,10 @@ bool mf_conv_tuned_valid(const ConvTuned& c, int precision, int act);
 int mf_conv_pin(ConvPlan* p, int batch, const ConvTuned& c);
 // rocprofv3-style name of the kernel mf_conv_launch will use at this batch size
 void mf_conv_kernel_name(const ConvPlan* p, int batch, char* buf, int cap);
-// Workgroup tile the launch will use for this batch size (kernel = k_conv_igemm<bm,bn,wgm,wgn,x3>).
+// Workgroup tile the launch will use for this batch size (kernel = k_conv_igemm<bm,bn,wgm,wgn,x3>): the tuned entry, else the cost model (mf_conv_tune.hip).
 ConvTile mf_conv_pick_tile(const ConvPlan* p, int batch);
+// layers the 128 x 80 producer-wave tile can run: bf16x3, channel count a multiple of 80, no GEGLU pairing (its 5 channel fragments do not pair)
+inline bool mf_tile80_ok(const ConvPlan* p) { return p->precision == MF_PREC_BF16X3 && !p->q && p->d.act != 5 && p->d.cout % 80 == 0; }
 // Measures the implicit-GEMM launch configurations (tile x split-K x operand path) of this layer at this batch ON the bound buffers and keeps the
 // fastest in p->tuned (layers that run on the halo kernels are left alone).  Eager only: call between two uncaptured forwards.  The cost model
 // behind mf_conv_pick_tile was fitted to one kernel generation; on the UNet's small GEMMs its pick is 0-15 % off per layer in either direction.
@@ -238,6 +276,21 @@ int mf_gemm_grouped_launch(ConvPlan* p, const GroupedGemm& g, hipStream_t stream
 
 // channel-slice split the f16 + FP6 kernel runs a layer with at this batch (1 = none): maps with fewer 16 x 16 x 128-channel tiles than CUs
 int mf_q_split_count(const ConvPlan* p, int batch);
+// channel-slice split of the fat 256-channel halo tile for a wide layer whose map gives too few patches at this batch (0 = none)
+int mf_halo_split_count(const ConvPlan* p, int batch);
+// The two launchers that share k_conv_igemm's translation unit (mf_conv.hip).  mf_igemm_launch: THE tile dispatch -- k_conv_igemm<t.bm, t.bn, ...> in the precision
+// and on the operand path a.ld names, a.tiles_m x a.tiles_n tiles x t.nsplit x (a.zgroups or nphase); MF_ERR_INVALID for a tile that is no row of MF_IGEMM_TILES.
+int mf_igemm_launch(const ConvArgs& a, const ConvTile& t, int nphase, int goff_max, bool x3, bool q, hipStream_t s);
+// mf_splitk_combine: the pass behind nsplit fp32 partial sets e.ws [split][batch][Ho][Wo][e.N].  With gn_out set (the consumer GroupNorm's statistics, gn_groups groups)
+// and a layer k_splitk_epilogue_stats serves (no GEGLU, e.N a multiple of 4 and of gn_groups <= 64) that kernel runs and leaves them, *with_stats = true; else
+// k_splitk_epilogue, *with_stats = false.
+int mf_splitk_combine(const ConvArgs& e, int nsplit, int batch, int Ho, int Wo, double* gn_out, int gn_groups, bool* with_stats, hipStream_t s);
+// Development probes (mf_conv_debug.hip), called by the launch path only when their MF_DEBUG word is set.  copies: after an eager launch on a batch of IDENTICAL
+// items, reports a layer whose input, output or statistics of an item differ from item 0's (MF_DEBUG_DUMP=<prefix>: and dumps the first such layer).
+// times: the buffer k_conv_igemm's workgroups stamp (null where the launch has more workgroups than it holds), and the report read back from it.
+int mf_conv_debug_copies(const ConvPlan* p, const ActView& in, const ActView& out, int batch, hipStream_t stream);
+unsigned long long* mf_conv_debug_times_buffer(int64_t workgroups);
+int mf_conv_debug_times_report(const ConvArgs& a, const ConvTile& t, int nphase, hipStream_t stream);
 // GroupNorm statistics pass alone (mf_nn.hip): (sum, sum of squares) per (sample, group) of view x ADDED to stats[2 * (b * groups + g)]
 int mf_groupnorm_stats(const ActView& x, int groups, double* stats, int batch, hipStream_t s);
 // Enqueues the layer.  res may have buf == nullptr.

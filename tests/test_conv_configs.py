@@ -1,4 +1,4 @@
-"""Every launch configuration of the convolution engine (mf_conv.hip, mf_conv_halo.hip, mf_conv_halo2.hip, mf_conv_thin.hip) against float64, at a derived
+"""Every launch configuration of the convolution engine (mf_conv.hip, mf_conv_launch.hip, mf_conv_tune.hip, mf_conv_halo.hip, mf_conv_halo2.hip, mf_conv_thin.hip) against float64, at a derived
 per-element bound, on the shapes where tiled kernels go wrong -- and proof, through mf_conv2d_launch_config, that each configuration actually ran.
 
 Seam.  mf_conv2d_launch_config reports what a forward at a batch launches (family, tile, the split after every clamp, the operand path ld that runs, BK,
@@ -386,6 +386,7 @@ SHAPE_PATHS = [
     ("halo_w 16x128 4x2", _c(32, 128, 3, 1, 1, 96, 96, act=1), 8, "halo_w", (16, 128), None),
     ("halo_w 16x256", _c(40, 256, 3, 1, 1, 96, 96, act=0), 8, "halo_w", (16, 256), None),
     ("halo_w split", _c(512, 256, 3, 1, 1, 32, 32, act=1), 16, "halo_w_split", (16, 256), ">1"),
+    ("halo_w split, residual is the input", _c(512, 512, 3, 1, 1, 32, 32, act=1, residual=1), 8, "halo_w_split", (16, 256), ">1"),
     ("twin", _c(512, 256, 3, 1, 1, 32, 32, act=2), 2, "twin", None, None),
     ("thin k7 s1", _c(6, 16, 7, 1, 3, 32, 32, act=1), 2, "thin", None, None),
     ("thin k3 s1", _c(12, 28, 3, 1, 1, 24, 24, act=2), 2, "thin", None, None),

@@ -1,4 +1,4 @@
-"""The tuning table shipped beside the library (mere-fusion_amd/tune/gfx950.txt), read the way the loader reads it (mf_conv.hip, tune_cache()).
+"""The tuning table shipped beside the library (mere-fusion_amd/tune/gfx950.txt), read the way the loader reads it (mf_conv_tune.hip, tune_cache()).
 
 The loader reads `key bm bn wgm wgn nsplit ld` with `while (fscanf(...) == 7)`: one malformed line ends the read and every row after it is lost; a row its
 validity check rejects is dropped with one line on stderr.  Either way the affected layers fall back to the cost model's pick and the output bits change from
@@ -15,14 +15,14 @@ from mere_fusion_amd.tune_grid import GRID
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 TABLE = os.path.join(ROOT, "mere-fusion_amd", "tune", "gfx950.txt")
 
-# tune_key() in mf_conv.hip: the kernel generation, then 19 integers, then ':s' when the layer also leaves GroupNorm statistics
+# tune_key() in mf_conv_tune.hip: the kernel generation, then 19 integers, then ':s' when the layer also leaves GroupNorm statistics
 KEY_FIELDS = ("precision", "batch", "cin", "cout", "kh", "kw", "stride_h", "stride_w", "pad_h", "pad_w", "transposed", "output_padding", "residual",
               "act", "in_h", "in_w", "upsample", "pad_hi", "in_c")
 LINE_RE = re.compile(r"(g950k4((?::-?\d+){%d})(?::s)?) (-?\d+) (-?\d+) (-?\d+) (-?\d+) (-?\d+) (-?\d+)" % len(KEY_FIELDS))
 PRECISION_NAMES = {0: "bf16", 1: "bf16x3"}                 # MF_PREC_BF16, MF_PREC_BF16X3 (include/merefusion.h)
 PRECISION_IDS = {v: k for k, v in PRECISION_NAMES.items()}
 
-# The loader's validity rules (mf_conv.hip, `valid` in tune_cache()).  KEEP IN SYNC with that lambda: a tile or operand path added there is added here.
+# The loader's validity rules (mf_conv_tune.hip, `valid` in tune_cache() and mf_conv_tuned_valid).  KEEP IN SYNC with that lambda: a tile or operand path added there is added here.
 TILES = {(64, 64, 2, 2), (128, 64, 2, 2), (128, 128, 2, 2), (256, 128, 4, 2), (256, 256, 2, 4), (128, 80, 4, 1)}   # (bm, bn, wgm, wgn)
 LD_PATHS = {-1, 0, 2, 3, 4}
 
@@ -50,7 +50,7 @@ def parse(lines):
 
 
 def loader_rejects(cfg, precision=1, act=0):
-    """The reason mf_conv.hip's loader would drop this configuration of a key with this precision and activation, or None.  (KEEP IN SYNC with `valid` in
+    """The reason mf_conv_tune.hip's loader would drop this configuration of a key with this precision and activation, or None.  (KEEP IN SYNC with `valid` in
     tune_cache() and mf_conv_tuned_valid().)"""
     bm, bn, wgm, wgn, nsplit, ld = cfg
     if bm == 0:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reads a MF_DEBUG=copies MF_DEBUG_DUMP=<prefix> dump (mf_conv.hip: the first layer whose copies of one frame disagree although their inputs agree) and says WHAT is wrong
+"""Reads a MF_DEBUG=copies MF_DEBUG_DUMP=<prefix> dump (mf_conv_debug.hip: the first layer whose copies of one frame disagree although their inputs agree) and says WHAT is wrong
 in the disagreeing item -- the decisive question of the packed-FMA study: is a wrong value an FMA result, a column sum, a bias, a row statistic?
 
 For a LayerNorm-folded layer  y = rs_m * (acc_mn - mu_m * cs_n) + b_n.  Item 0 is taken as right, so acc_mn follows from it; for every wrong element of item k the
