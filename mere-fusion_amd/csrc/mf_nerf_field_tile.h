@@ -122,7 +122,9 @@ __device__ __forceinline__ void field_tile(const FusedArgs& a, const char* smem,
         const bool has = mq < M && a.deltas[2 * (size_t)mq] != 0.f;
         if (!__any(has)) return;
     }
-    const float inv2b = 1.f / (2.f * a.bound);
+    // (x + bound) / (2 bound), grid.py:144, as a DIVISION: a product with fl(1 / (2 bound)) is the same float only when 2 bound is a power of two (at bound 1.5 it
+    // moved a coordinate by one ulp, 9e-5 on a finest-level feature)
+    const float two_b = 2.f * a.bound;
     {
         // ---- inputs of this lane's two samples ------------------------------------------------------------------
         float px[NSF], py[NSF], pz[NSF], dx[NSF], dy[NSF], dz[NSF];
@@ -133,10 +135,10 @@ __device__ __forceinline__ void field_tile(const FusedArgs& a, const char* smem,
             live[sf] = m < M;
             m = live[sf] ? m : M - 1;
             if constexpr (DENS) {
-                px[sf] = (qx + a.bound) * inv2b; py[sf] = (qy + a.bound) * inv2b; pz[sf] = (qz + a.bound) * inv2b;
+                px[sf] = __fdiv_rn(qx + a.bound, two_b); py[sf] = __fdiv_rn(qy + a.bound, two_b); pz[sf] = __fdiv_rn(qz + a.bound, two_b);
                 dx[sf] = dy[sf] = dz[sf] = 0.f;
             } else {
-                px[sf] = (a.xyzs[3 * m] + a.bound) * inv2b; py[sf] = (a.xyzs[3 * m + 1] + a.bound) * inv2b; pz[sf] = (a.xyzs[3 * m + 2] + a.bound) * inv2b;
+                px[sf] = __fdiv_rn(a.xyzs[3 * m] + a.bound, two_b); py[sf] = __fdiv_rn(a.xyzs[3 * m + 1] + a.bound, two_b); pz[sf] = __fdiv_rn(a.xyzs[3 * m + 2] + a.bound, two_b);
                 dx[sf] = a.dirs[3 * m]; dy[sf] = a.dirs[3 * m + 1]; dz[sf] = a.dirs[3 * m + 2];
             }
         }

@@ -83,8 +83,8 @@ __global__ __launch_bounds__(256) void k_nf_prep(const float* __restrict__ xyzs,
                                                  int n_ind, float bound, int M, float* coords, bf16_t* ci_hi, bf16_t* ci_lo) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
-    const float inv = 1.f / (2.f * bound);
-    const float x = (xyzs[3 * m] + bound) * inv, y = (xyzs[3 * m + 1] + bound) * inv, z = (xyzs[3 * m + 2] + bound) * inv;
+    const float two_b = 2.f * bound;      // divided, as grid.py:144 does: a product with the rounded reciprocal differs by an ulp unless 2 bound is a power of two
+    const float x = __fdiv_rn(xyzs[3 * m] + bound, two_b), y = __fdiv_rn(xyzs[3 * m + 1] + bound, two_b), z = __fdiv_rn(xyzs[3 * m + 2] + bound, two_b);
     float* cxy = coords + (size_t)m * 2;
     float* cyz = coords + (size_t)M * 2 + (size_t)m * 2;
     float* cxz = coords + (size_t)M * 4 + (size_t)m * 2;
