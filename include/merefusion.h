@@ -80,6 +80,18 @@ int mf_wav2lip_forward(mf_wav2lip* h, const float* mel, const float* face, float
 int mf_wav2lip_forward_u8(mf_wav2lip* h, const float* mel, const uint8_t* faces_u8,
                           float* frames_hwc, int batch, void* stream);
 
+/* mf_wav2lip_forward_u8 with the faces picked from a pool (cross-session batching, lip_driver.LipBatcher): face_pool is device uint8
+ * [n_pool_rows,96,96,3] -- every session's cached crops, concatenated -- and batch row b is generated from face rows[b] (lipreal.py:112-114: the
+ * mirror-indexed crop).  rows: HOST array of `batch` pool rows, range-checked before anything is enqueued; it is read during the call only.  Bit-equal to
+ * mf_wav2lip_forward_u8 on the gathered faces at the same batch, with or without the hipGraph (the rows never enter the captured part). */
+int mf_wav2lip_forward_u8_rows(mf_wav2lip* h, const float* mel, const uint8_t* face_pool, int n_pool_rows,
+                               const int* rows, float* frames_hwc, int batch, void* stream);
+
+/* 1 when the handle holds an instantiated hipGraph for this batch size (the next forward at it is a replay), else 0 (first forward: eager; second: capture;
+ * always 0 under MF_NO_GRAPH=1).  Growing the handle's workspace -- a forward at a batch larger than any before -- drops every captured graph, so a
+ * warm-up sizes the handle with its LARGEST batch first (lip_driver.LipBatcher.prewarm). */
+int mf_wav2lip_graph_captured(const mf_wav2lip* h, int batch);
+
 /* Copies the NCHW fp32 activation named `tap` of the LAST forward into `dst` (device), for
  * parity tests.  tap: "audio_embedding", "face_encoder_blocks.N", "face_decoder_blocks.N". */
 int mf_wav2lip_read_tap(mf_wav2lip* h, const char* tap, float* dst, int batch, void* stream);
@@ -172,6 +184,12 @@ int mf_conv2d_pin_config(mf_conv2d* h, int batch, int bm, int bn, int wgm, int w
  * pad_mode: 0 = zeros (librosa >= 0.10 default "constant"), 1 = reflect (librosa < 0.10). */
 int mf_melspec(const float* wav, int n, float* out, int pad_mode, void* stream);
 int mf_melspec_frames(int n);
+/* The mel windows of MANY sessions' run_steps in one launch (lipasr.py:24-35): wav is device fp32 [n_windows][n], each row one session's whole
+ * sliding window of (2B + l + r) x 320 samples; starts: HOST array of the n_starts start columns lip_driver.mel_chunk_starts returns (shared: every
+ * row has the same n), each in [0, T - 16]; chunks: device fp32 [n_windows * n_starts][1][80][16], window-major -- per row exactly
+ * mf_melspec(row)[:, s : s + 16] for every start s, bit for bit.  Padding happens at each row's own ends.  n_starts <= 256. */
+int mf_melspec_windows(const float* wav, int n, int n_windows, const int* starts, int n_starts,
+                       float* chunks, int pad_mode, void* stream);
 
 /* ---- fused multi-head attention (test seam of the kernel both transformer stages run on) ---- */
 /* out = softmax(q k^T / sqrt(head_dim)) v per (batch, head): the `Attention` of the diffusers

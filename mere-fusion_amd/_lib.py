@@ -85,6 +85,8 @@ SIGNATURES = {
     "mf_wav2lip_create": (C.c_int, [C.POINTER(MfTensor), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mf_wav2lip_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_wav2lip_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mf_wav2lip_forward_u8_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_void_p]),
+    "mf_wav2lip_graph_captured": (C.c_int, [C.c_void_p, C.c_int]),
     "mf_wav2lip_read_tap": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_wav2lip_num_launches": (C.c_int, [C.c_void_p, C.c_int]),
     "mf_wav2lip_launch_info": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
@@ -160,6 +162,7 @@ SIGNATURES = {
     "mf_vae_encoder_destroy": (None, [C.c_void_p]),
     "mf_melspec": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_melspec_frames": (C.c_int, [C.c_int]),
+    "mf_melspec_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_attention_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "mf_rows_roundtrip": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] + [C.c_int] * 5 + [C.c_void_p] * 2),
     "mf_layernorm_forward": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] * 2 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 2),

@@ -13,6 +13,9 @@ int mf_act_to_nchw(const ActView& src, float* dst, int batch, hipStream_t s);
 // [masked b,g,r (rows >= H/2 zero), full b,g,r, 0, 0] / 255
 int mf_faces_u8_to_act(const uint8_t* faces, const ActBuf& dst, int batch, hipStream_t s);
 
+// the same for faces picked from a pool: batch row b reads pool[rows[b]] (uint8 [.,96,96,3]); rows is a HOST array the caller has range-checked
+int mf_faces_u8_rows_to_act(const uint8_t* pool, const int* rows, const ActBuf& dst, int batch, hipStream_t s);
+
 // output_block.1 (plain 1x1 Conv2d 32->3) + Sigmoid (wav2lip.py:84-85) on the NHWC activation
 // of output_block.0.  hwc255 == 0: fp32 NCHW [B,3,H,W] in [0,1];  hwc255 == 1: fp32 [B,H,W,3]*255
 // (the `pred.cpu().numpy().transpose(0,2,3,1) * 255.` of lipreal.py:126).

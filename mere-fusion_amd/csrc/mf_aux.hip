@@ -51,15 +51,8 @@ __global__ void k_act_to_nchw(const bf16_t* hi, const bf16_t* lo, int Cbuf, int 
     dst[idx] = v;
 }
 
-__global__ void k_faces_u8(const uint8_t* __restrict__ faces, int H, int W, bf16_t* hi, bf16_t* lo, int halo,
-                           int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int x = idx % W;
-    int64_t t = idx / W;
-    const int y = t % H;
-    const int b = t / H;
-    const uint8_t* px = faces + (((int64_t)b * H + y) * W + x) * 3;
+// one pixel of one face crop -> the 8-channel (hi, lo) planes of batch row b
+__device__ __forceinline__ void face_px_u8(const uint8_t* __restrict__ px, int b, int y, int x, int H, int W, bf16_t* hi, bf16_t* lo, int halo) {
     float v[8];
     const bool keep = y < H / 2;   // img_masked[:, face.shape[0]//2:] = 0  (lipreal.py:116)
 #pragma unroll
@@ -76,6 +69,36 @@ __global__ void k_faces_u8(const uint8_t* __restrict__ faces, int H, int W, bf16
     const int64_t o = (((int64_t)b * Hp + y + halo) * Wp + x + halo) * 8;
     *reinterpret_cast<uint4*>(hi + o) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
     if (lo) *reinterpret_cast<uint4*>(lo + o) = make_uint4(l[0] | l[1] << 16, l[2] | l[3] << 16, l[4] | l[5] << 16, l[6] | l[7] << 16);
+}
+
+__global__ void k_faces_u8(const uint8_t* __restrict__ faces, int H, int W, bf16_t* hi, bf16_t* lo, int halo,
+                           int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int x = idx % W;
+    int64_t t = idx / W;
+    const int y = t % H;
+    const int b = t / H;
+    face_px_u8(faces + (((int64_t)b * H + y) * W + x) * 3, b, y, x, H, W, hi, lo, halo);
+}
+
+// the same with the faces picked from a pool: batch row b0 + i reads pool face rows[i] (the mirror-indexed crop of a session, lipreal.py:112-114).  The rows
+// travel as kernel arguments (mf_gather_rows_f32's way): no host buffer to keep alive, and the launch sits in front of the captured graph
+constexpr int MAX_FACE_ROWS = 256;
+struct FaceRowsArgs {
+    const uint8_t* pool; bf16_t* hi; bf16_t* lo;
+    int H, W, halo, b0, n;
+    int rows[MAX_FACE_ROWS];
+};
+
+__global__ void k_faces_u8_rows(const FaceRowsArgs a) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;     // < 256 rows x 96 x 96
+    if (idx >= a.n * a.H * a.W) return;
+    const int x = idx % a.W;
+    const int t = idx / a.W;
+    const int y = t % a.H;
+    const int i = t / a.H;
+    face_px_u8(a.pool + (((int64_t)a.rows[i] * a.H + y) * a.W + x) * 3, a.b0 + i, y, x, a.H, a.W, a.hi, a.lo, a.halo);
 }
 
 // VAE.preprocess_img (vae.py:52-82) on an in-memory uint8 BGR crop: RGB order, x = fp32(u8 / 255.) (numpy divides in double, FloatTensor rounds
@@ -172,6 +195,20 @@ int mf_faces_u8_to_act(const uint8_t* faces, const ActBuf& dst, int batch, hipSt
     hipLaunchKernelGGL(k_faces_u8, dim3(blocks_for(total, 256)), dim3(256), 0, s, faces, dst.H, dst.W, dst.hi,
                        dst.lo, dst.halo, total);
     MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+int mf_faces_u8_rows_to_act(const uint8_t* pool, const int* rows, const ActBuf& dst, int batch, hipStream_t s) {
+    MF_REQUIRE(dst.C == 8, "faces_u8_rows_to_act: destination must have 8 channels");
+    MF_REQUIRE((int64_t)MAX_FACE_ROWS * dst.H * dst.W < (int64_t)1 << 31, "faces_u8_rows_to_act: %d x %d faces overflow the launch index", dst.H, dst.W);
+    for (int b0 = 0; b0 < batch; b0 += MAX_FACE_ROWS) {
+        FaceRowsArgs a{};
+        a.pool = pool; a.hi = dst.hi; a.lo = dst.lo; a.H = dst.H; a.W = dst.W; a.halo = dst.halo; a.b0 = b0;
+        a.n = batch - b0 < MAX_FACE_ROWS ? batch - b0 : MAX_FACE_ROWS;
+        for (int i = 0; i < a.n; ++i) a.rows[i] = rows[b0 + i];
+        hipLaunchKernelGGL(k_faces_u8_rows, dim3(blocks_for((int64_t)a.n * dst.H * dst.W, 256)), dim3(256), 0, s, a);
+        MF_HIP(hipGetLastError());
+    }
     return MF_OK;
 }
 

@@ -78,13 +78,12 @@ int ensure_tables(int dev) {
     return MF_OK;
 }
 
-__global__ __launch_bounds__(256) void k_melspec(const float* __restrict__ wav, int n, int T, int pad_mode,
-                                                 const double* __restrict__ win, const double* __restrict__ tw,
-                                                 const float* __restrict__ basis, float* __restrict__ out) {
-    __shared__ double s_x[N_FFT];
-    __shared__ double s_tw[2 * N_FFT];
-    __shared__ double s_mag[N_BINS + 7];
-    const int t = blockIdx.x, tid = threadIdx.x;
+// One STFT frame of one signal by one 256-thread workgroup: returns mel band `threadIdx.x` of frame t (threads >= 80 return nothing of use).
+// Both kernels below run this body, so a frame's value does not depend on which of them computed it.
+__device__ __forceinline__ float mel_frame(const float* __restrict__ wav, int n, int t, int pad_mode, const double* __restrict__ win,
+                                           const double* __restrict__ tw, const float* __restrict__ basis, double* s_x, double* s_tw,
+                                           double* s_mag) {
+    const int tid = threadIdx.x;
     for (int j = tid; j < N_FFT; j += 256) {
         int p = t * HOP - N_FFT / 2 + j;   // index into the un-padded pre-emphasised signal
         double y = 0.0;
@@ -113,15 +112,51 @@ __global__ __launch_bounds__(256) void k_melspec(const float* __restrict__ wav, 
         s_mag[f] = sqrt(re * re + im * im);
     }
     __syncthreads();
-    if (tid < N_MELS) {
-        const float* row = basis + (size_t)tid * N_BINS;
-        double acc = 0.0;
-        for (int k = 0; k < N_BINS; ++k) acc = fma((double)row[k], s_mag[k], acc);
-        const double min_level = 1e-5;                            // exp(-100/20*ln 10)
-        const double S = 20.0 * log10(fmax(min_level, acc)) - 20.0;
-        double v = 8.0 * ((S + 100.0) / 100.0) - 4.0;
-        v = fmin(fmax(v, -4.0), 4.0);
-        out[(size_t)tid * T + t] = (float)v;
+    if (tid >= N_MELS) return 0.f;
+    const float* row = basis + (size_t)tid * N_BINS;
+    double acc = 0.0;
+    for (int k = 0; k < N_BINS; ++k) acc = fma((double)row[k], s_mag[k], acc);
+    const double min_level = 1e-5;                            // exp(-100/20*ln 10)
+    const double S = 20.0 * log10(fmax(min_level, acc)) - 20.0;
+    double v = 8.0 * ((S + 100.0) / 100.0) - 4.0;
+    v = fmin(fmax(v, -4.0), 4.0);
+    return (float)v;
+}
+
+__global__ __launch_bounds__(256) void k_melspec(const float* __restrict__ wav, int n, int T, int pad_mode,
+                                                 const double* __restrict__ win, const double* __restrict__ tw,
+                                                 const float* __restrict__ basis, float* __restrict__ out) {
+    __shared__ double s_x[N_FFT];
+    __shared__ double s_tw[2 * N_FFT];
+    __shared__ double s_mag[N_BINS + 7];
+    const int t = blockIdx.x, tid = threadIdx.x;
+    const float v = mel_frame(wav, n, t, pad_mode, win, tw, basis, s_x, s_tw, s_mag);
+    if (tid < N_MELS) out[(size_t)tid * T + t] = v;
+}
+
+// LipASR.run_step's mel for MANY sliding windows in one launch (lipasr.py:23-35): workgroup (frame, window) computes frame t0 + blockIdx.x of window
+// blockIdx.y from that window's own row of `wav` (padding at the row's own ends) and stores its 80 values into every 16-column chunk that holds the
+// frame.  The chunk starts are the same for all windows (same n) and travel as kernel arguments, as mf_gather_rows_f32's rows do.
+constexpr int MAX_STARTS = 256;
+constexpr int MEL_STEP = 16;
+struct MelWindowArgs {
+    const float* wav; float* chunks;
+    int n, t0, n_starts, pad_mode;
+    int starts[MAX_STARTS];
+};
+
+__global__ __launch_bounds__(256) void k_melspec_windows(const MelWindowArgs a, const double* __restrict__ win, const double* __restrict__ tw,
+                                                         const float* __restrict__ basis) {
+    __shared__ double s_x[N_FFT];
+    __shared__ double s_tw[2 * N_FFT];
+    __shared__ double s_mag[N_BINS + 7];
+    const int t = a.t0 + blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
+    const float v = mel_frame(a.wav + (size_t)w * a.n, a.n, t, a.pad_mode, win, tw, basis, s_x, s_tw, s_mag);
+    if (tid >= N_MELS) return;
+    float* dst = a.chunks + (size_t)w * a.n_starts * N_MELS * MEL_STEP + (size_t)tid * MEL_STEP;
+    for (int i = 0; i < a.n_starts; ++i) {
+        const int d = t - a.starts[i];
+        if (d >= 0 && d < MEL_STEP) dst[(size_t)i * N_MELS * MEL_STEP + d] = v;
     }
 }
 
@@ -143,6 +178,39 @@ extern "C" int mf_melspec(const float* wav, int n, float* out, int pad_mode, voi
     const int T = 1 + n / HOP;
     hipLaunchKernelGGL(k_melspec, dim3(T), dim3(256), 0, (hipStream_t)stream, wav, n, T, pad_mode, t.win, t.tw,
                        t.basis, out);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+extern "C" int mf_melspec_windows(const float* wav, int n, int n_windows, const int* starts, int n_starts, float* chunks, int pad_mode,
+                                  void* stream) {
+    MF_REQUIRE(n > 0, "melspec_windows: empty signal (n=%d)", n);
+    MF_REQUIRE(n_windows > 0, "melspec_windows: n_windows must be positive (got %d)", n_windows);
+    MF_REQUIRE(n_windows <= 65535, "melspec_windows: at most 65535 windows per call (got %d)", n_windows);
+    MF_REQUIRE(wav && starts && chunks, "melspec_windows: null argument");
+    MF_REQUIRE(n_starts > 0 && n_starts <= MAX_STARTS, "melspec_windows: 1 to %d chunk starts per window (got %d)", MAX_STARTS, n_starts);
+    MF_REQUIRE(pad_mode == 0 || pad_mode == 1, "melspec_windows: pad_mode must be 0 (zeros) or 1 (reflect)");
+    MF_REQUIRE(pad_mode == 0 || n > N_FFT / 2, "melspec_windows: reflect padding needs more than %d samples", N_FFT / 2);
+    const int T = 1 + n / HOP;
+    MelWindowArgs a{};
+    int lo = T, hi = 0;
+    for (int i = 0; i < n_starts; ++i) {
+        MF_REQUIRE(starts[i] >= 0 && starts[i] <= T - MEL_STEP, "melspec_windows: start %d = %d outside [0, %d] (T = %d frames)", i, starts[i],
+                   T - MEL_STEP, T);
+        a.starts[i] = starts[i];
+        lo = starts[i] < lo ? starts[i] : lo;
+        hi = starts[i] + MEL_STEP > hi ? starts[i] + MEL_STEP : hi;
+    }
+    int dev = 0;
+    MF_HIP(hipGetDevice(&dev));
+    MF_REQUIRE(dev < 16, "melspec_windows: device index %d not supported", dev);
+    int rc = ensure_tables(dev);
+    if (rc) return rc;
+    const MelTables& t = g_tab[dev];
+    // the span of the chunks, [min start, max start + 16): the l / r context frames outside it are never computed (a start list with gaps wider than a
+    // chunk -- none at the fps the reference runs -- would still compute the frames inside its gaps)
+    a.wav = wav; a.chunks = chunks; a.n = n; a.t0 = lo; a.n_starts = n_starts; a.pad_mode = pad_mode;
+    hipLaunchKernelGGL(k_melspec_windows, dim3(hi - lo, n_windows), dim3(256), 0, (hipStream_t)stream, a, t.win, t.tw, t.basis);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

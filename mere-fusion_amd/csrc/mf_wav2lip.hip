@@ -435,6 +435,30 @@ extern "C" int mf_wav2lip_forward_u8(mf_wav2lip* h, const float* mel, const uint
     return mf_head_1x1_sigmoid(ActView{h->out0, 0, 32}, h->head_w, h->head_b, frames_hwc, 1, batch, s);
 }
 
+extern "C" int mf_wav2lip_forward_u8_rows(mf_wav2lip* h, const float* mel, const uint8_t* face_pool, int n_pool_rows, const int* rows,
+                                          float* frames_hwc, int batch, void* stream) {
+    MF_REQUIRE(h && mel && face_pool && rows && frames_hwc, "wav2lip_forward_u8_rows: null argument");
+    MF_REQUIRE(batch > 0, "wav2lip_forward_u8_rows: batch must be positive (got %d)", batch);
+    MF_REQUIRE(n_pool_rows > 0, "wav2lip_forward_u8_rows: the pool must hold at least one face (got %d)", n_pool_rows);
+    for (int i = 0; i < batch; ++i)   // before anything is enqueued or allocated
+        MF_REQUIRE(rows[i] >= 0 && rows[i] < n_pool_rows, "wav2lip_forward_u8_rows: row %d = %d out of range (%d pool rows)", i, rows[i], n_pool_rows);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = h->ensure_capacity(batch);
+    if (rc) return rc;
+    if ((rc = mf_nchw_to_act(mel, 1, *h->mel_in, batch, s))) return rc;
+    // the rows change every step: this launch carries them as kernel arguments and runs IN FRONT of the captured conv chain (run() replays only that),
+    // exactly where mf_faces_u8_to_act sits -- a replayed graph never holds a row
+    if ((rc = mf_faces_u8_rows_to_act(face_pool, rows, *h->face_in, batch, s))) return rc;
+    if ((rc = h->run(batch, s))) return rc;
+    return mf_head_1x1_sigmoid(ActView{h->out0, 0, 32}, h->head_w, h->head_b, frames_hwc, 1, batch, s);
+}
+
+extern "C" int mf_wav2lip_graph_captured(const mf_wav2lip* h, int batch) {
+    if (!h) return 0;
+    auto it = h->graphs.find(batch);
+    return it != h->graphs.end() && it->second != nullptr;
+}
+
 extern "C" int mf_wav2lip_read_tap(mf_wav2lip* h, const char* tap, float* dst, int batch, void* stream) {
     MF_REQUIRE(h && tap && dst, "wav2lip_read_tap: null argument");
     MF_REQUIRE(batch > 0 && batch <= h->cap, "wav2lip_read_tap: batch %d exceeds the last forward's workspace (%d)", batch, h->cap);

@@ -469,23 +469,7 @@ class EndToEndScheduler(SessionScheduler):
                 popped.append((k, item))
                 arrival[k], (wins[k], audio[k]) = item
             t0 = self.clock()
-            chunks = [None] * len(self.queues)
-            speaking = [k for k in ks if wins[k] is not None]
-            if speaking and self.fixed_chunks is not None:
-                for k in speaking:
-                    chunks[k] = self.fixed_chunks
-            elif speaking:
-                cur = torch.cuda.current_stream(dev)
-                side = self.asr_stream if self.asr_stream is not None else cur
-                with torch.cuda.stream(side):
-                    wav = torch.from_numpy(np.stack([wins[k] for k in speaking])).to(dev, non_blocking=True)
-                    feats = self.audio_processor.audio2feat_windows_device(wav)        # every picked session's window in one encoder call
-                    for i, k in enumerate(speaking):
-                        chunks[k] = self.frontends[k].chunks_from_features(feats[i])
-                if side is not cur:
-                    cur.wait_stream(side)                                              # the UNet below reads the chunks
-                    for t in [wav, feats] + [chunks[k] for k in speaking]:
-                        t.record_stream(cur)
+            chunks = self._audio_stage(ks, wins, dev)
             out = self.batcher.step(chunks, only=ks)
             ev = torch.cuda.Event()
             if self.rings is not None:
@@ -516,6 +500,28 @@ class EndToEndScheduler(SessionScheduler):
         self.steps += 1
         self.sessions_served += len(ks)
         return done
+
+    def _audio_stage(self, ks, wins, dev):
+        """The audio front end of one step: wins[k] is what submit() queued for session k (None: a silent batch).  Returns the batcher's per-session input list
+        (None for every session that is silent or not picked).  lip_driver.LipEndToEndScheduler replaces this stage (and submit) and inherits everything else."""
+        chunks = [None] * len(self.queues)
+        speaking = [k for k in ks if wins[k] is not None]
+        if speaking and self.fixed_chunks is not None:
+            for k in speaking:
+                chunks[k] = self.fixed_chunks
+        elif speaking:
+            cur = torch.cuda.current_stream(dev)
+            side = self.asr_stream if self.asr_stream is not None else cur
+            with torch.cuda.stream(side):
+                wav = torch.from_numpy(np.stack([wins[k] for k in speaking])).to(dev, non_blocking=True)
+                feats = self.audio_processor.audio2feat_windows_device(wav)        # every picked session's window in one encoder call
+                for i, k in enumerate(speaking):
+                    chunks[k] = self.frontends[k].chunks_from_features(feats[i])
+            if side is not cur:
+                cur.wait_stream(side)                                              # the UNet below reads the chunks
+                for t in [wav, feats] + [chunks[k] for k in speaking]:
+                    t.record_stream(cur)
+        return chunks
 
     def drain(self):
         """Waits for everything in flight (end of a run)."""

@@ -93,6 +93,48 @@ def _(wav, pad_mode):
     return wav.new_empty((80, 1 + wav.shape[0] // 200), dtype=torch.float32)
 
 
+def wav2lip_forward_u8_rows(handle, mel, face_pool, rows):
+    """wav2lip_forward_u8 with the faces picked from a pool: face_pool uint8 [n,96,96,3] on the device (every session's cached crops), rows the host list of
+    pool rows, one per mel chunk -- batch row b is generated from face_pool[rows[b]] without a gather in between (mf_wav2lip_forward_u8_rows).  A plain
+    function, not a custom op: `rows` is a host list that changes every step."""
+    _require_cuda("wav2lip_forward_u8_rows", mel, face_pool)
+    if face_pool.dtype != torch.uint8 or face_pool.dim() != 4 or tuple(face_pool.shape[1:]) != (96, 96, 3):
+        raise RuntimeError(f"wav2lip_forward_u8_rows: the pool must be uint8 [n,96,96,3], got {face_pool.dtype} {tuple(face_pool.shape)}")
+    rows = [int(r) for r in rows]
+    if mel.dim() != 4 or tuple(mel.shape[1:]) != (1, 80, 16) or mel.shape[0] != len(rows):
+        raise RuntimeError(f"wav2lip_forward_u8_rows: mel must be [B,1,80,16] with B = {len(rows)} rows, got {tuple(mel.shape)}")
+    mel = mel.contiguous().float()
+    face_pool = face_pool.contiguous()
+    B = len(rows)
+    out = torch.empty((B, 96, 96, 3), dtype=torch.float32, device=mel.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(mel.device):
+        _lib.check(_lib.lib().mf_wav2lip_forward_u8_rows(handle, mel.data_ptr(), face_pool.data_ptr(), face_pool.shape[0], (C.c_int * B)(*rows),
+                                                         out.data_ptr(), B, _stream_ptr(mel.device)), "wav2lip_forward_u8_rows")
+    return out
+
+
+def melspec_windows(wav, starts, pad_mode, out=None):
+    """The mel chunks of many LipASR.run_steps in one launch (lipasr.py:24-35): wav fp32 [n_windows, n] on the device, one sliding window per row; starts the
+    host list lip_driver.mel_chunk_starts returns for n -> fp32 [n_windows * len(starts), 1, 80, 16], window-major (mf_melspec_windows)."""
+    _require_cuda("melspec_windows", wav)
+    if wav.dim() != 2:
+        raise RuntimeError(f"melspec_windows: wav must be [n_windows, n], got {tuple(wav.shape)}")
+    wav = wav.contiguous().float()
+    nw, n = wav.shape
+    starts = [int(v) for v in starts]
+    shape = (nw * len(starts), 1, 80, 16)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=wav.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError(f"melspec_windows: out must be a contiguous fp32 device tensor {shape}, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(wav.device):
+        _lib.check(_lib.lib().mf_melspec_windows(wav.data_ptr(), n, nw, (C.c_int * len(starts))(*starts), len(starts), out.data_ptr(), int(pad_mode),
+                                                 _stream_ptr(wav.device)), "melspec_windows")
+    return out
+
+
 # ---- MuseTalk / Whisper stages as custom ops too (the drop-in modules call these; handles are the C ABI's opaque pointers) ----------
 @torch.library.custom_op("merefusion::unet_forward", mutates_args=())
 def unet_forward(handle: int, latents: torch.Tensor, audio: torch.Tensor, add_pe: bool, out_channels: int) -> torch.Tensor:

@@ -138,6 +138,21 @@ class Wav2Lip(nn.Module):
         h = self._ensure_handle(faces_u8.device)
         return ops.wav2lip_forward_u8(h, mel_batch, faces_u8)
 
+    def forward_u8_rows(self, mel_batch, face_pool, rows):
+        """forward_u8 on face_pool[rows] without the gather: face_pool uint8 [n,96,96,3] on the device, rows a host list of len(mel_batch) pool rows
+        (lip_driver.LipBatcher: every session's cached crops in one pool, the rows are their mirror indices)."""
+        if self.training:
+            raise RuntimeError("the MI355X Wav2Lip generator is inference-only: call .eval()")
+        if not face_pool.is_cuda or not mel_batch.is_cuda:
+            raise RuntimeError("Wav2Lip.forward_u8_rows needs HIP device tensors (model.to('cuda')); no CPU path exists here")
+        h = self._ensure_handle(face_pool.device)
+        return ops.wav2lip_forward_u8_rows(h, mel_batch, face_pool, rows)
+
+    def graph_captured(self, batch):
+        """Diagnostic (tests of LipBatcher.prewarm read it; serving code has no use for it): True when the next forward at this batch size replays a captured
+        hipGraph (mf_wav2lip_graph_captured)."""
+        return bool(self._handle) and bool(_lib.lib().mf_wav2lip_graph_captured(self._handle, int(batch)))
+
     def tune(self, batch):
         """Explicit launch-configuration warm-up (mf_wav2lip_tune): times every implicit-GEMM layer at this batch size on the buffers of the last
         forward at that size and keeps the fastest.  A forward itself never measures: it uses the tuning table (MF_TUNE_CACHE or the one shipped
