@@ -472,6 +472,29 @@ int mf_nerf_frame_background(const uint8_t* torso_rgba, const float* bg_image, f
 int mf_nerf_frame_out(const float* render, int h, int w, int H, int W, const uint8_t* body_bgr, int FH, int FW, int x0, int y0, int linear_to_srgb,
                       uint8_t* frame_rgb, void* stream);
 
+/* ---- the audio features of many ER-NeRF sessions (mf_nerf_featpool.hip; nerf_serving.NerfFeaturePool) ---- */
+/* What `NerfASR` keeps per session in torch tensors, for N sessions in two caller-owned device buffers: rings fp32 [N][R][dim] (`feat_queue`,
+ * nerfasr.py:48-50; R = feat_buffer_size * m = 32) and hist fp32 [N][8][dim][16] (`att_feats`, nerfasr.py:55, as a circular buffer).  Both entries are
+ * stateless, take HOST int arrays of one value per picked session (read during the call only; they travel as launch arguments), check every argument
+ * before anything is enqueued and never wait for the host: one launch per 64 picked sessions.  dim 1..1024, R >= 16, rows distinct and inside N, else
+ * MF_ERR_INVALID.  They move fp32 values only.
+ *
+ * mf_nerf_feat_scatter (nerfasr.py:119-124, 140-142): feats is the net's output for the n_sessions picked sessions, device fp32 [n_sessions][T][dim];
+ * rows [left, right) of feats[i] are copied to ring rows starts[i] .. starts[i] + right - left of session rows[i] (starts[i] = feat_buffer_idx * m); a
+ * block that leaves the ring is refused, as the slice assignment raises. */
+int mf_nerf_feat_scatter(const float* feats, int n_sessions, int T, int dim, int left, int right, float* rings, int N, int R,
+                         const int* rows, const int* starts, void* stream);
+/* mf_nerf_feat_windows (nerfasr.py:75-103), per picked session i: out[i] (device fp32 [n_sessions][8][dim][16]) receives the session's eight windows,
+ * oldest first; fronts (HOST int [n_sessions][8]) names the ring row each starts at, or -1 for a zero window of nerfasr.py:55.  A window is ring rows
+ * (front + t) mod R, t = 0..15, transposed to [dim][16].  The last n_new[i] windows are new: read from the ring and also stored in history slots
+ * (heads[i] + j) mod 8.  The older ones occupy the slots from (heads[i] + n_new[i]) mod 8 on and come out as `torch.stack` finds them in the reference: a
+ * window that wraps round the ring's end (front + 16 >= R) was concatenated, a copy -- from its history slot, as a zero window is (the caller zeroes
+ * those slots); one that does not wrap is a view of `feat_queue` and shows what has been written under it since -- read from the ring again.  n_new is 1
+ * in steady state and 4 on a session's first call.  att == 0: no history (hist, heads may be NULL), fronts is [n_sessions][1], n_new[i] must be 1 and
+ * out is [n_sessions][1][dim][16]. */
+int mf_nerf_feat_windows(const float* rings, float* hist, int N, int R, int dim, int n_sessions, const int* rows, const int* fronts,
+                         const int* heads, const int* n_new, int att, float* out, void* stream);
+
 /* ---- ER-NeRF head frame without host round trips ----------------------------------------------- */
 typedef struct mf_nerf_head mf_nerf_head;
 /* Scratch for up to max_rays rays over `field` (which must outlive the head and use the fused field kernel). */

@@ -137,15 +137,15 @@ class NerfSession:
                    "mf_nerf_frame_background")
         return out
 
-    def frame_out(self, image, body=None):
-        """The uint8 RGB frame: `image` [H, W, 3] fp32 (or None: `body` alone, channels reversed) resized to the GUI size, over `body` at the offset."""
+    def frame_out(self, image, body=None, out=None):
+        """The uint8 RGB frame: `image` [H, W, 3] fp32 (or None: `body` alone, channels reversed) resized to the GUI size, over `body` at the offset.
+        out: the contiguous uint8 device tensor of the frame's size to write instead of a new one (nerf_serving.NerfBatcher: one block per step)."""
         dev = self.poses.device
-        if body is None:
-            out = torch.empty(self.GH, self.GW, 3, dtype=torch.uint8, device=dev)
-            FH, FW = self.GH, self.GW
-        else:
-            FH, FW = int(body.shape[0]), int(body.shape[1])
+        FH, FW = (self.GH, self.GW) if body is None else (int(body.shape[0]), int(body.shape[1]))
+        if out is None:
             out = torch.empty(FH, FW, 3, dtype=torch.uint8, device=dev)
+        elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (FH, FW, 3)):
+            _refuse(f"out must be a contiguous uint8 CUDA tensor [{FH}, {FW}, 3]")
         x0, y0 = (self.x0, self.y0) if (image is not None and body is not None) else (0, 0)
         _lib.check(self._lib.mf_nerf_frame_out(C.c_void_p(image.data_ptr()) if image is not None else None, self.H, self.W, self.GH, self.GW,
                                                C.c_void_p(body.data_ptr()) if body is not None else None, FH, FW, x0, y0, int(self.linear_to_srgb),
@@ -165,15 +165,16 @@ class NerfSession:
 
     # ---- one frame ---------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self, auds, audiotype=(0, 0)):
+    def step(self, auds, audiotype=(0, 0), out=None):
         """One `NeRFReal.test_step`: the uint8 RGB frame as a device tensor -- [GH, GW, 3], [FH, FW, 3] with body frames, or the custom image's size.
-        auds: `NerfASRFrontend.get_next_feat()`; audiotype: the types of the frame's two audio chunks (nerfreal.py:81-88)."""
+        auds: `NerfASRFrontend.get_next_feat()`; audiotype: the types of the frame's two audio chunks (nerfreal.py:81-88); out: see frame_out."""
         ai, mi = loader_indices(self.size, self.index)          # the loader advances on every frame, a custom-video one included (nerfreal.py:72-76)
         self.index += 1
         self.last_audio_index, self.last_index = ai, mi
+        dst = {} if out is None else {"out": out}
         custom = self.next_custom(audiotype)
         if custom is not None:
-            return self.frame_out(None, custom)
+            return self.frame_out(None, custom, **dst)
         pose = self.poses[mi:mi + 1]
         rays = frontend.get_rays(self._ref_get_rays, pose, self.intrinsics, self.H, self.W)
         eye = None if self.eye_area is None else self.eye_area[mi:mi + 1]
@@ -190,7 +191,7 @@ class NerfSession:
         if image.dtype != torch.float32 or not image.is_contiguous():
             image = image.float().contiguous()
         body = None if self.fullbody_frames is None else self.fullbody_frames[mi]
-        return self.frame_out(image, body)
+        return self.frame_out(image, body, **dst)
 
     def step_to_ring(self, ring, auds, audio_frames, audiotype=(0, 0)):
         """step() and the frame into `ring` (transport.FrameRing): one DMA into the slot behind the frame's kernels, one stream fence, then the consumer's

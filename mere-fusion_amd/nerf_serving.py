@@ -1,0 +1,365 @@
+"""Many ER-NeRF sessions on one GPU: the counterpart of muse_driver's and lip_driver's serving stacks for the third model the reference serves.
+
+  NerfFeaturePool / NerfASRDeviceFrontend   the `NerfASR` state of N sessions (nerfasr.py:15-126) in one place: feature rings [N, R, dim] and attention-window
+                                            histories [N, 8, dim, 16] on the device, counters and the 28-chunk PCM windows on the host.  `step` runs
+                                            `run_step, run_step, get_next_feat` (nerfreal.py:139-141) for B frames of every picked session in lockstep: the
+                                            windows that complete go through ONE net call and ONE mf_nerf_feat_scatter launch, and every frame's `auds` of all
+                                            sessions come out of ONE mf_nerf_feat_windows launch
+  NerfBatcher                               a list of NerfSessions (several may share one model object: one avatar resident once) stepped B frames each; the
+                                            lip-smoothing EMA, which lives in the model, is kept per session
+  NerfSessionScheduler                      muse_driver.SessionScheduler over a NerfBatcher
+  NerfEndToEndScheduler                     muse_driver.EndToEndScheduler with the ER-NeRF audio stage: PCM chunks in, (frame, idx, audio_frames) tuples out of each
+                                            session's FrameRing; picking, back-pressure, publication and the waiter thread are the inherited code
+
+`ernerf.asr.NerfASRFrontend` stays the per-session restatement of the reference these are tested against."""
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .muse_driver import EndToEndScheduler, SessionScheduler
+
+
+def _refuse(who, msg):
+    raise RuntimeError(f"{who}: {msg}")
+
+
+class NerfFeaturePool:
+    """model: `HipWav2Vec2ForCTC(max_windows >= n_sessions)` or any callable that takes the raw samples [S, (m + l + r) * chunk] as a device tensor and returns an
+    object with `.logits` or `.last_hidden_state` [S, T, audio_dim] on the device (normalisation is the callable's business, as with `RawProcessor`).
+    A fresh pool is in the state `NerfASR.__init__` leaves; `warm_up` adds `NerfASR.warm_up()` (nerfreal.py always warms up)."""
+
+    HIST = 8                                                          # windows of one `auds` with att > 0 (nerfasr.py:77)
+
+    def __init__(self, n_sessions, model, audio_dim, att=2, m=8, l=10, r=10, fps=50, device="cuda"):
+        who = "NerfFeaturePool"
+        self.n_sessions, self.model, self.audio_dim, self.att = int(n_sessions), model, int(audio_dim), int(att)
+        self.m, self.l, self.r, self.chunk = int(m), int(l), int(r), 16000 // fps
+        if self.n_sessions < 1:
+            _refuse(who, "at least one session is required")
+        if not 1 <= self.audio_dim <= 1024:
+            _refuse(who, f"audio_dim {audio_dim} (1..1024)")
+        if self.m < 2 or self.l < 0 or self.r < 0 or self.l + self.r < 1:
+            _refuse(who, f"m = {m}, l = {l}, r = {r}: m >= 2 and l + r >= 1 are required (with l + r == 0 nerfasr.py:117 keeps every chunk it has seen)")
+        self.device = torch.device(device)
+        self.feat_buffer_size = 4                                       # nerfasr.py:48
+        self.R = self.feat_buffer_size * self.m
+        if self.R < 16:
+            _refuse(who, f"a ring of {self.R} rows cannot hold a 16-row window")
+        self.total = self.m + self.l + self.r                          # chunks of one net window; also NerfASR.warm_up_steps (nerfasr.py:58)
+        self.warm_up_steps = self.total
+        self.rings = torch.zeros((self.n_sessions, self.R, self.audio_dim), dtype=torch.float32, device=self.device)
+        self.hist = torch.zeros((self.n_sessions, self.HIST, self.audio_dim, 16), dtype=torch.float32, device=self.device) if self.att > 0 else None
+        self.pcm = np.zeros((self.n_sessions, self.total, self.chunk), np.float32)
+        N = self.n_sessions
+        self.frames, self.feat_buffer_idx, self.front, self.tail, self.head, self.first = [0] * N, [0] * N, [0] * N, [0] * N, [0] * N, [True] * N
+        self.win_fronts = [[] for _ in range(N)]                        # ring rows the windows `att_feats` holds start at, oldest first; -1: a zero window
+        for k in range(N):
+            self._reset_counters(k)
+        self.launches = self.net_calls = 0                              # kernel launches of this module's two entries / calls of the net, since creation
+
+    # ---- host state ----------------------------------------------------------------------------------------------------------------------
+    def _reset_counters(self, k):
+        self.pcm[k] = 0.0
+        self.frames[k] = self.l                                         # nerfasr.py:35-36: l chunks of silence
+        self.feat_buffer_idx[k] = 0                                     # :49
+        self.front[k], self.tail[k] = self.R - 8, 8                     # :52-53
+        self.head[k], self.first[k] = 4, True                           # :55: four zero windows; the first get_next_feat appends four more (:77)
+        self.win_fronts[k] = [-1] * 4 if self.att > 0 else []
+
+    def _rows(self, ks, who):
+        ks = [int(k) for k in ks]
+        if not ks:
+            _refuse(who, "no session picked")
+        if len(set(ks)) != len(ks):
+            _refuse(who, f"a session appears twice in {ks}")
+        if min(ks) < 0 or max(ks) >= self.n_sessions:
+            _refuse(who, f"sessions {ks}: rows run from 0 to {self.n_sessions - 1}")
+        return ks
+
+    def host_block(self, chunks, n_frames):
+        """the 2 * n_frames new 20 ms chunks of one session as one fp32 [2 * n_frames, chunk] array; refuses anything else (before any state moves)"""
+        if len(chunks) != 2 * n_frames:
+            _refuse("NerfFeaturePool", f"expected {2 * n_frames} chunks (two per frame), got {len(chunks)}")
+        return np.stack([self._chunk(c) for c in chunks])
+
+    def _chunk(self, c):
+        a = np.asarray(c, dtype=np.float32).reshape(-1)
+        if a.shape[0] != self.chunk:
+            _refuse("NerfFeaturePool", f"expected chunks of {self.chunk} samples, got one of {a.shape[0]}")
+        return a
+
+    def _advance(self, k, chunk):
+        """the host side of one `run_step` (nerfasr.py:105-117): the completed window [total * chunk] (a copy) when the net is due, else None"""
+        self.pcm[k, self.frames[k]] = chunk
+        self.frames[k] += 1
+        if self.frames[k] < self.total:
+            return None
+        win = self.pcm[k].reshape(-1).copy()
+        keep = self.l + self.r
+        self.pcm[k, :keep] = self.pcm[k, self.total - keep:].copy()
+        self.frames[k] = keep
+        return win
+
+    # ---- device state --------------------------------------------------------------------------------------------------------------------
+    def _fire(self, due):
+        """nerfasr.py:119-124 + 128-143 for every session whose window completed: due = [(session, window)].  One upload, one net call, one scatter."""
+        if not due:
+            return
+        cuda = self.device.type == "cuda"
+        host = torch.empty((len(due), self.total * self.chunk), dtype=torch.float32, pin_memory=cuda)
+        np.stack([w for _, w in due], out=host.numpy())
+        res = self.model(host.to(self.device, non_blocking=True))
+        self.net_calls += 1
+        logits = res.last_hidden_state if hasattr(res, "last_hidden_state") else res.logits
+        if logits.dim() != 3 or logits.shape[0] != len(due) or logits.shape[2] != self.audio_dim:
+            _refuse("NerfFeaturePool", f"the net returned {tuple(logits.shape)} for {len(due)} windows of audio_dim {self.audio_dim}")
+        T = int(logits.shape[1])
+        left, right = max(0, self.l), min(T, T - self.r + 1)          # nerfasr.py:140-141
+        ks = [k for k, _ in due]
+        ops.nerf_feat_scatter(logits, left, right, self.rings, ks, [self.feat_buffer_idx[k] * self.m for k in ks])
+        self.launches += 1
+        for k in ks:
+            self.feat_buffer_idx[k] = (self.feat_buffer_idx[k] + 1) % self.feat_buffer_size
+
+    def run_step(self, ks, chunks):
+        """one `run_step` of sessions ks at once: chunks[i] is session ks[i]'s next 20 ms chunk"""
+        ks = self._rows(ks, "NerfFeaturePool.run_step")
+        blocks = [self._chunk(c) for c in chunks]
+        if len(blocks) != len(ks):
+            _refuse("NerfFeaturePool.run_step", f"{len(blocks)} chunks for {len(ks)} sessions")
+        self._fire([(k, w) for k, w in ((k, self._advance(k, c)) for k, c in zip(ks, blocks)) if w is not None])
+
+    def next_feat(self, ks, out=None):
+        """`get_next_feat` of sessions ks in one launch -> [len(ks), 8 or 1, audio_dim, 16]"""
+        ks = self._rows(ks, "NerfFeaturePool.next_feat")
+        n_new = [(4 if self.first[k] else 1) if self.att > 0 else 1 for k in ks]                   # nerfasr.py:77: `while len(self.att_feats) < 8`
+        fronts = [self.win_fronts[k] + [(self.front[k] + 2 * j) % self.R for j in range(n)] for k, n in zip(ks, n_new)]
+        out = ops.nerf_feat_windows(self.rings, self.hist, ks, fronts, [self.head[k] for k in ks], n_new, self.att, out=out)
+        self.launches += 1
+        for k, n, f in zip(ks, n_new, fronts):
+            self.front[k], self.tail[k] = (self.front[k] + 2 * n) % self.R, (self.tail[k] + 2 * n) % self.R
+            self.head[k], self.first[k] = (self.head[k] + n) % self.HIST, False
+            self.win_fronts[k] = f[1:] if self.att > 0 else []         # :90
+        return out
+
+    def step(self, ks, chunks, B):
+        """nerfreal.py:139-141 for B frames of sessions ks in lockstep: chunks[i] holds session ks[i]'s 2B new chunks.  Returns [len(ks), B, 8 or 1, audio_dim, 16]
+        (a view: entry [i, b] is contiguous).  Launches besides the net: the B window launches and one scatter per frame in which some session's net window
+        completes -- ONE for sessions in phase (each session is due once per m / 2 frames; sessions that joined on a step boundary of B = m / 2 frames share it),
+        whatever their number.  The scatter sits between the window launches exactly where the reference's run_step fires."""
+        ks = self._rows(ks, "NerfFeaturePool.step")
+        B = int(B)
+        if B < 1 or len(chunks) != len(ks):
+            _refuse("NerfFeaturePool.step", f"{len(chunks)} chunk blocks for {len(ks)} sessions, B = {B}")
+        blocks = [self.host_block(c, B) for c in chunks]               # everything is checked before any session moves
+        buf = torch.empty((B, len(ks), self.HIST if self.att > 0 else 1, self.audio_dim, 16), dtype=torch.float32, device=self.device)
+        for b in range(B):
+            due = []
+            for k, blk in zip(ks, blocks):
+                for c in (2 * b, 2 * b + 1):
+                    w = self._advance(k, blk[c])
+                    if w is not None:
+                        due.append((k, w))
+            self._fire(due)
+            self.next_feat(ks, out=buf[b])
+        return buf.transpose(0, 1)
+
+    def reset(self, ks=None):
+        """sessions ks (default: all) back to the state `NerfASR.__init__` leaves"""
+        ks = list(range(self.n_sessions)) if ks is None else self._rows([ks] if isinstance(ks, int) else ks, "NerfFeaturePool.reset")
+        for k in ks:
+            self._reset_counters(k)
+            self.rings[k].zero_()
+            if self.hist is not None:
+                self.hist[k].zero_()
+        return ks
+
+    def warm_up(self, ks=None):
+        """sessions ks (one number, a list; default: all) to the state `NerfASR.__init__` plus `warm_up()` leave (nerfasr.py:146-152: m + l + r run_steps on
+        silence), so that a session can join or start again while the others go on"""
+        ks = self.reset(ks)
+        silence = np.zeros(self.chunk, np.float32)
+        for _ in range(self.warm_up_steps):
+            self.run_step(ks, [silence] * len(ks))
+
+
+class NerfASRDeviceFrontend:
+    """The per-session surface of `NerfASRFrontend` over row `row` of a NerfFeaturePool: put_audio_frame / run_step / get_next_feat / warm_up."""
+
+    def __init__(self, pool, row):
+        self.pool, self.row = pool, int(row)
+        if not 0 <= self.row < pool.n_sessions:
+            _refuse("NerfASRDeviceFrontend", f"row {row} of a pool of {pool.n_sessions} sessions")
+        self.att, self.audio_dim, self.device, self.chunk, self.warm_up_steps = pool.att, pool.audio_dim, pool.device, pool.chunk, pool.warm_up_steps
+        self.pending = []
+
+    def put_audio_frame(self, frame):
+        self.pending.append(np.asarray(frame, np.float32))
+
+    def run_step(self):
+        self.pool.run_step([self.row], [self.pending.pop(0) if self.pending else np.zeros(self.chunk, np.float32)])
+
+    def get_next_feat(self):
+        return self.pool.next_feat([self.row])[0]
+
+    def warm_up(self):
+        self.pool.warm_up([self.row])
+
+
+class NerfBatcher:
+    """The `batcher` the schedulers drive, over a list of NerfSessions.  batch_size 4 is one wav2vec2 cadence (m / 2 frames): every picked session's net window
+    completes in every step.  Sessions may share one model object; the lip-smoothing EMA `model.enc_a` (the drop-in module and the bare HipHeadRenderer keep it
+    there) is then one value per session here, installed before the session's frames and read back after them."""
+
+    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None):
+        who = "NerfBatcher"
+        self.sessions, self.batch_size, self.pool, self.device = list(sessions), int(batch_size), pool, torch.device(device)
+        if not self.sessions:
+            _refuse(who, "at least one session is required")
+        if self.batch_size < 1:
+            _refuse(who, f"batch_size {batch_size}")
+        self.max_sessions_per_step = len(self.sessions) if max_sessions_per_step is None else int(max_sessions_per_step)
+        if pool is not None and pool.n_sessions != len(self.sessions):
+            _refuse(who, f"a feature pool of {pool.n_sessions} rows for {len(self.sessions)} sessions")
+        self.out_shape = []
+        for k, s in enumerate(self.sessions):
+            hw = (int(s.fullbody_frames.shape[1]), int(s.fullbody_frames.shape[2])) if s.fullbody_frames is not None else (s.GH, s.GW)
+            for t, cycle in s.custom_img_cycle.items():
+                for f in cycle:
+                    if tuple(f.shape[:2]) != hw:
+                        _refuse(who, f"session {k}: custom_img_cycle[{t}] holds a {f.shape[1]} x {f.shape[0]} frame, the session's frames are {hw[1]} x {hw[0]} "
+                                     f"(a step's {self.batch_size} frames leave as one block)")
+            self.out_shape.append(hw + (3,))
+        self.enc_a = [None] * len(self.sessions)
+
+    def _check_input(self, k, inp):
+        B = self.batch_size
+        if not (isinstance(inp, (tuple, list)) and len(inp) == 2):
+            _refuse("NerfBatcher", f"session {k}: expected (windows [{B}, 8 or 1, dim, 16], {B} audiotype pairs), got {type(inp).__name__} (ER-NeRF renders silent "
+                                   f"batches too: there is no None input)")
+        auds, types = inp
+        if not torch.is_tensor(auds) or auds.dim() != 4 or auds.shape[0] != B or auds.shape[1] not in (1, 8) or auds.shape[3] != 16 \
+                or auds.device.type != self.device.type:
+            what = f"{tuple(auds.shape)} on {auds.device}" if torch.is_tensor(auds) else type(auds).__name__
+            _refuse("NerfBatcher", f"session {k}: expected windows [{B}, 8 or 1, dim, 16] on {self.device}, got {what}")
+        try:
+            ok = len(types) == B and all(len(t) == 2 and all(int(v) == v for v in t) for t in types)
+        except TypeError:
+            ok = False
+        if not ok:
+            _refuse("NerfBatcher", f"session {k}: expected {B} (audiotype, audiotype) pairs")
+
+    @torch.no_grad()
+    def step(self, inputs, only=None):
+        """inputs: one entry per session -- (windows [B, 8 or 1, dim, 16] as NerfFeaturePool.step returns them, the B frames' audiotype pairs).  Returns one
+        (frames uint8 [B, h, w, 3] RGB on the device, the B mirrored indices) per session, on the caller's stream.  only: session numbers that take part; every
+        other session is left untouched (index, custom-video counters and EMA do not move; its entry is None and its input is not looked at)."""
+        B = self.batch_size
+        if len(inputs) != len(self.sessions):
+            _refuse("NerfBatcher", f"{len(inputs)} entries for {len(self.sessions)} sessions")
+        take = None if only is None else set(int(k) for k in only)
+        if take is not None and (min(take, default=0) < 0 or max(take, default=0) >= len(self.sessions)):
+            _refuse("NerfBatcher", f"only={sorted(take)}: session numbers run from 0 to {len(self.sessions) - 1}")
+        picked = [k for k in range(len(self.sessions)) if take is None or k in take]
+        if len(picked) > self.max_sessions_per_step:
+            _refuse("NerfBatcher", f"{len(picked)} active sessions in one step; a step holds {self.max_sessions_per_step} x {B} frames")
+        for k in picked:                                                 # every input is checked BEFORE any session moves
+            self._check_input(k, inputs[k])
+        out = [None] * len(self.sessions)
+        for k in picked:
+            s, (auds, types) = self.sessions[k], inputs[k]
+            frames = torch.empty((B,) + self.out_shape[k], dtype=torch.uint8, device=auds.device)
+            idx = []
+            shared = hasattr(s.model, "enc_a")
+            if shared:
+                s.model.enc_a = self.enc_a[k]
+            try:
+                for b in range(B):
+                    s.step(auds[b], (int(types[b][0]), int(types[b][1])), out=frames[b])
+                    idx.append(s.last_index)
+            finally:
+                if shared:
+                    self.enc_a[k] = s.model.enc_a
+            out[k] = (frames, idx)
+        return out
+
+    @torch.no_grad()
+    def prewarm(self, auds=None):
+        """One rendered frame per session, so that the serving loop meets no first-time cost (ray directions per size, handles, workspaces).  Session state --
+        the loader's position, custom-video counters, the EMA -- is left as it was.  auds: one frame's windows; default: zeros of the pool's shape."""
+        if auds is None:
+            if self.pool is None:
+                _refuse("NerfBatcher.prewarm", "without a feature pool the windows of one frame must be given")
+            auds = torch.zeros((self.pool.HIST if self.pool.att > 0 else 1, self.pool.audio_dim, 16), dtype=torch.float32, device=self.device)
+        for s in self.sessions:
+            keep = (s.index, s.last_index, s.last_audio_index, dict(s.custom_index))
+            shared = hasattr(s.model, "enc_a")
+            ema = s.model.enc_a if shared else None
+            try:
+                s.step(auds, (0, 0))
+            finally:
+                s.index, s.last_index, s.last_audio_index = keep[:3]
+                s.custom_index.clear()
+                s.custom_index.update(keep[3])
+                if shared:
+                    s.model.enc_a = ema
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+
+class NerfSessionScheduler(SessionScheduler):
+    """muse_driver.SessionScheduler over a NerfBatcher: submit(k, (windows, audiotype pairs), t_arrival), run_once(now), next_due() -- the same queues, the same
+    pick_sessions policy, B frames per session and step.  Period default: B x 40 ms (25 fps)."""
+
+
+class NerfEndToEndScheduler(EndToEndScheduler):
+    """The whole per-GPU ER-NeRF session loop: what reaches a session's consumer, from what its ASR thread saw.
+
+      nerfasr.py:105-124   submit(k, chunks, t): the 2B new 20 ms PCM chunks of session k.  When the batch is picked, NerfFeaturePool.step runs the run_steps and
+      nerfasr.py:75-103    get_next_feats of all picked sessions in lockstep: one net call for the windows that complete, B + 1 launches around it
+      nerfreal.py:70-127   NerfBatcher.step: B frames per picked session; a frame whose two chunks carry a custom audio type is the custom-video frame (:98)
+      the ring             each session's B (frame, idx, audio_frames[2i:2i+2]) tuples leave through ITS FrameRing
+
+    ER-NeRF has no silent-batch skip: an all-silent batch renders like any other.  Everything else -- pick_sessions, try_reserve before anything irreversible,
+    deferral, publish order, the waiter thread, close() / the context manager, single_stream -- is EndToEndScheduler's code, unchanged.  A session's features
+    advance when its batch is PICKED, not when it is submitted, and once: a batch whose step failed returns to its queue with its windows attached."""
+
+    def __init__(self, batcher, pool=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
+        pool = batcher.pool if pool is None else pool
+        if not isinstance(pool, NerfFeaturePool) or pool.n_sessions != len(batcher.sessions):     # before anything (streams, the parent's state) is created
+            _refuse("NerfEndToEndScheduler", "a NerfFeaturePool with one row per session of the batcher is required")
+        fes = [NerfASRDeviceFrontend(pool, k) for k in range(pool.n_sessions)]
+        super().__init__(batcher, fes, None, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, asr_stream=False, single_stream=single_stream)
+        self.pool = pool
+
+    def submit(self, k, pcm_chunks, t_arrival=None):
+        """pcm_chunks: the batch's 2B 20 ms chunks -- bare arrays (type 0) or (chunk, type) pairs as `get_audio_frame` hands them out (nerfasr.py:60-73).  Refused
+        here, before it is queued, when malformed."""
+        t = self.clock() if t_arrival is None else t_arrival
+        B = self.batcher.batch_size
+        if not 0 <= int(k) < len(self.queues):
+            _refuse("NerfEndToEndScheduler.submit", f"session {k}: numbers run from 0 to {len(self.queues) - 1}")
+        pairs = [(c if isinstance(c, tuple) else (c, 0)) for c in pcm_chunks]
+        if any(len(p) != 2 for p in pairs):
+            _refuse("NerfEndToEndScheduler.submit", "expected chunks or (chunk, type) pairs")
+        block = self.pool.host_block([c for c, _ in pairs], B)
+        try:
+            types = [(int(pairs[2 * i][1]), int(pairs[2 * i + 1][1])) for i in range(B)]      # nerfreal.py:81-88
+        except (TypeError, ValueError):
+            _refuse("NerfEndToEndScheduler.submit", "audio types must be integers")
+        self.queues[int(k)].append((t, ({"block": block, "types": types, "feats": None}, pairs)))
+
+    def _audio_stage(self, ks, wins, dev):
+        inputs = [None] * len(self.queues)
+        # A batch whose step failed returns to the HEAD of its session's queue with its windows: the session's features have advanced already and must not advance
+        # again.  No other batch of that session can be picked in between (a session's batches are served in queue order).
+        todo = sorted(k for k in ks if wins[k]["feats"] is None)
+        if todo:
+            feats = self.pool.step(todo, [wins[k]["block"] for k in todo], self.batcher.batch_size)
+            for i, k in enumerate(todo):
+                wins[k]["feats"] = feats[i]
+        for k in ks:
+            inputs[k] = (wins[k]["feats"], wins[k]["types"])
+        return inputs

@@ -135,6 +135,67 @@ def melspec_windows(wav, starts, pad_mode, out=None):
     return out
 
 
+def _ints(v):
+    v = [int(x) for x in v]
+    return (C.c_int * len(v))(*v), len(v)
+
+
+def _fp32_pool(name, what, t, tail):
+    if not (t.dtype == torch.float32 and t.is_contiguous() and t.dim() == len(tail) + 1 and tuple(t.shape[1:]) == tuple(tail)):
+        raise RuntimeError(f"{name}: {what} must be a contiguous fp32 tensor [N, {', '.join(str(v) for v in tail)}], got {t.dtype} {tuple(t.shape)}")
+
+
+def nerf_feat_scatter(feats, left, right, rings, rows, starts):
+    """nerfasr.py:119-124 for many sessions in one launch: rows [left, right) of feats[i] (the net's output [S, T, dim] for the S picked sessions) into ring
+    rows starts[i]... of session rows[i] of rings [N, R, dim] (mf_nerf_feat_scatter).  rows / starts are host lists.  In place; returns nothing."""
+    _require_cuda("nerf_feat_scatter", feats, rings)
+    if feats.dim() != 3 or rings.dim() != 3 or feats.shape[2] != rings.shape[2]:
+        raise RuntimeError(f"nerf_feat_scatter: feats [S, T, dim] and rings [N, R, dim] must share dim, got {tuple(feats.shape)} and {tuple(rings.shape)}")
+    _fp32_pool("nerf_feat_scatter", "rings", rings, rings.shape[1:])
+    feats = feats.contiguous().float()
+    crows, S = _ints(rows)
+    cstarts, n = _ints(starts)
+    if S != feats.shape[0] or n != S:
+        raise RuntimeError(f"nerf_feat_scatter: {S} rows and {n} starts for {feats.shape[0]} slices of the net output")
+    with torch.cuda.device(rings.device):
+        _lib.check(_lib.lib().mf_nerf_feat_scatter(feats.data_ptr(), S, feats.shape[1], feats.shape[2], int(left), int(right), rings.data_ptr(), rings.shape[0],
+                                                   rings.shape[1], crows, cstarts, _stream_ptr(rings.device)), "nerf_feat_scatter")
+
+
+def nerf_feat_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
+    """nerfasr.py:75-103 for many sessions in one launch (mf_nerf_feat_windows): rings [N, R, dim], hist [N, 8, dim, 16] (None with att == 0); rows, heads,
+    n_new host lists, one value per picked session; fronts one list per session of the ring rows its 8 (or 1) windows start at, oldest first, -1 for a zero
+    window -> fp32 [S, 8 or 1, dim, 16], the sessions' `auds`.  The history is updated in place."""
+    _require_cuda("nerf_feat_windows", rings)
+    if rings.dim() != 3:
+        raise RuntimeError(f"nerf_feat_windows: rings must be [N, R, dim], got {tuple(rings.shape)}")
+    N, R, dim = rings.shape
+    _fp32_pool("nerf_feat_windows", "rings", rings, (R, dim))
+    if att:
+        if hist is None:
+            raise RuntimeError("nerf_feat_windows: att > 0 needs the history [N, 8, dim, 16]")
+        _require_cuda("nerf_feat_windows", hist)
+        _fp32_pool("nerf_feat_windows", "hist", hist, (8, dim, 16))
+        if hist.shape[0] != N:
+            raise RuntimeError(f"nerf_feat_windows: {hist.shape[0]} histories for {N} rings")
+    crows, S = _ints(rows)
+    shape = (S, 8 if att else 1, dim, 16)
+    fronts = [list(f) for f in fronts]
+    if any(len(f) != shape[1] for f in fronts):
+        raise RuntimeError(f"nerf_feat_windows: every session needs the fronts of its {shape[1]} windows")
+    lists = [_ints(v for f in fronts for v in f), _ints(heads if att else [0] * S), _ints(n_new)]
+    if [n for _, n in lists] != [S * shape[1], S, S]:
+        raise RuntimeError(f"nerf_feat_windows: {S} rows, {len(fronts)} lists of fronts, {lists[1][1]} heads, {lists[2][1]} n_new")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rings.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError(f"nerf_feat_windows: out must be a contiguous fp32 device tensor {shape}, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(rings.device):
+        _lib.check(_lib.lib().mf_nerf_feat_windows(rings.data_ptr(), hist.data_ptr() if att else None, N, R, dim, S, crows, lists[0][0], lists[1][0], lists[2][0],
+                                                   int(bool(att)), out.data_ptr(), _stream_ptr(rings.device)), "nerf_feat_windows")
+    return out
+
+
 # ---- MuseTalk / Whisper stages as custom ops too (the drop-in modules call these; handles are the C ABI's opaque pointers) ----------
 @torch.library.custom_op("merefusion::unet_forward", mutates_args=())
 def unet_forward(handle: int, latents: torch.Tensor, audio: torch.Tensor, add_pe: bool, out_channels: int) -> torch.Tensor:

@@ -1,0 +1,429 @@
+"""CPU: the host side of the multi-session ER-NeRF stack (mere_fusion_amd/nerf_serving.py) -- the pool's counter walk against `NerfASRFrontend`'s own counters,
+with the two launches replaced by a restatement of what include/merefusion.h says they do, so that positions, order and values are held to the frontend
+bit for bit without a device; `NerfBatcher` and scheduler bookkeeping and refusals with stand-in sessions; and the C ABI of the two entries (header, exports,
+ctypes table, argument checks that never launch)."""
+import ctypes as C
+import os
+import re
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+import nerf_serving_util as U
+
+B = 4
+
+
+# ---- the two launches, restated from the header (host tensors) -----------------------------------------------------------------------------
+def _emu_scatter(feats, left, right, rings, rows, starts):
+    for i, (k, st) in enumerate(zip(rows, starts)):
+        assert 0 <= st and st + right - left <= rings.shape[1]
+        rings[k, st:st + right - left] = feats[i, left:right]
+
+
+def _emu_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
+    N, R, dim = rings.shape
+    o = torch.full((len(rows), 8 if att else 1, dim, 16), float("nan")) if out is None else out
+    n_out = 8 if att else 1
+    for i, k in enumerate(rows):
+        assert len(fronts[i]) == n_out
+        for q, f in enumerate(fronts[i]):
+            j = q - (n_out - n_new[i])
+            if j >= 0 or (f >= 0 and f + 16 < R):                        # a new window, or a view of the ring
+                o[i, q] = rings[k, [(f + t) % R for t in range(16)]].t()
+                if att and j >= 0:
+                    hist[k, (heads[i] + j) % 8] = o[i, q]
+            else:                                                        # a copy (it wrapped), or a zero window
+                o[i, q] = hist[k, (heads[i] + n_new[i] + q) % 8]
+    return o
+
+
+@pytest.fixture
+def host_ops(monkeypatch):
+    from mere_fusion_amd import nerf_serving as S
+    calls = []
+    monkeypatch.setattr(S.ops, "nerf_feat_scatter", lambda *a, **k: (calls.append(("scatter", list(a[4]), list(a[5]))), _emu_scatter(*a, **k))[1])
+    monkeypatch.setattr(S.ops, "nerf_feat_windows", lambda *a, **k: (calls.append(("windows", list(a[2]), list(a[5]))), _emu_windows(*a, **k))[1])
+    return calls
+
+
+@pytest.mark.parametrize("att", [2, 0])
+def test_counter_walk_over_40_frames_matches_the_frontend(host_ops, att):
+    """frames, feat_buffer_idx, front, tail after every frame, the four windows of the first call, where the scatter falls, and -- through the restated
+    launches -- every value of every frame's `auds`, for two sessions of which one sits out two frames (so their phases differ)."""
+    from mere_fusion_amd.nerf_serving import NerfFeaturePool
+    dim = 5
+    net = U.StubNet(dim, "cpu")
+    pool = NerfFeaturePool(2, net, dim, att=att, device="cpu")
+    assert pool_state(pool, 0) == (10, 0, 24, 8) and pool.first == [True, True]
+    pool.warm_up()
+    fes = [U.warmed_frontend(U.StubNet(dim, "cpu"), dim, att, "cpu") for _ in range(2)]
+    assert net.calls == [2, 2] and pool_state(pool, 0) == U.counters(fes[0]) == (22, 2, 24, 8)
+    done, wrapped = [0, 0], False
+    for f in range(40):
+        ks = [0] if f in (5, 6) else [0, 1]
+        del host_ops[:]
+        got = pool.step(ks, [U.pcm(k, done[k]) for k in ks], 1)
+        assert tuple(got.shape) == (len(ks), 1, 8 if att else 1, dim, 16)
+        for i, k in enumerate(ks):
+            wrapped |= fes[k].front > fes[k].tail                                            # the window this frame reads wraps round the ring's end
+            want = U.reference_frame(fes[k], U.pcm(k, done[k]))
+            done[k] += 1
+            assert torch.equal(got[i, 0], want), (f, k)
+            assert pool_state(pool, k) == U.counters(fes[k]), (f, k)
+        kinds = [c[0] for c in host_ops]
+        assert kinds in (["windows"], ["scatter", "windows"]) and host_ops[-1][1] == ks
+        assert host_ops[-1][2] == [4 if (att and f == 0) else 1] * len(ks)                 # nerfasr.py:77: the first call appends four windows
+        due = [k for k in ks if done[k] % 4 == 3]                                           # after warm_up: inside the third frame of each four
+        assert (kinds[0] == "scatter") == bool(due) and (not due or host_ops[0][1] == due)
+    assert wrapped and done == [40, 38]
+
+
+def pool_state(pool, k):
+    return U.pool_counters(pool, k)
+
+
+def test_step_of_four_frames_is_b_plus_one_launches_and_one_net_call(host_ops):
+    from mere_fusion_amd.nerf_serving import NerfFeaturePool
+    net = U.StubNet(3, "cpu")
+    pool = NerfFeaturePool(5, net, 3, device="cpu")
+    pool.warm_up()
+    n0, l0 = len(net.calls), pool.launches
+    for step in range(3):
+        del host_ops[:]
+        pool.step(range(5), [sum((U.pcm(k, 4 * step + b) for b in range(B)), []) for k in range(5)], B)
+        assert [c[0] for c in host_ops] == ["windows", "windows", "scatter", "windows", "windows"]
+    assert net.calls[n0:] == [5, 5, 5] and pool.launches - l0 == 3 * (B + 1)                # whatever the number of sessions
+    # a session that joins later is warmed up alone while the others keep their state
+    before = pool_state(pool, 0), pool.rings[0].clone()
+    pool.warm_up(3)
+    assert pool_state(pool, 3) == (22, 2, 24, 8) and pool.first[3] and pool_state(pool, 0) == before[0] and torch.equal(pool.rings[0], before[1])
+
+
+def test_pool_refusals_move_nothing(host_ops):
+    from mere_fusion_amd.nerf_serving import NerfASRDeviceFrontend, NerfFeaturePool
+    net = U.StubNet(3, "cpu")
+    pool = NerfFeaturePool(2, net, 3, device="cpu")
+    state = lambda: [pool_state(pool, k) for k in range(2)]
+    s0 = state()
+    good = U.pcm(0, 0)
+    for ks, chunks, n in (([0, 0], [good, good], 1), ([2], [good], 1), ([-1], [good], 1), ([], [], 1), ([0, 1], [good], 1), ([0], [good[:1]], 1), ([0], [good], 2),
+                          ([0, 1], [good, [good[0], np.zeros(319, np.float32)]], 1), ([0], [good], 0)):
+        with pytest.raises(RuntimeError, match="NerfFeaturePool"):
+            pool.step(ks, chunks, n)
+        assert state() == s0 and not host_ops and not net.calls
+    for kw in (dict(audio_dim=0), dict(audio_dim=1025), dict(m=1), dict(l=0, r=0), dict(m=2)):
+        with pytest.raises(RuntimeError, match="NerfFeaturePool"):
+            NerfFeaturePool(**{**dict(n_sessions=1, model=net, audio_dim=3, device="cpu"), **kw})
+    with pytest.raises(RuntimeError, match="NerfFeaturePool"):
+        NerfFeaturePool(0, net, 3, device="cpu")
+    with pytest.raises(RuntimeError, match="NerfASRDeviceFrontend"):
+        NerfASRDeviceFrontend(pool, 2)
+    bad = NerfFeaturePool(1, U.StubNet(4, "cpu"), 3, device="cpu")                           # a net of another width: refused where nerfasr.py:123 would raise
+    with pytest.raises(RuntimeError, match="audio_dim 3"):
+        bad.warm_up()
+
+
+def test_device_frontend_keeps_the_frontends_surface(host_ops):
+    from mere_fusion_amd.nerf_serving import NerfASRDeviceFrontend, NerfFeaturePool
+    pool = NerfFeaturePool(2, U.StubNet(6, "cpu", hidden=True), 6, device="cpu")
+    fe, ref = NerfASRDeviceFrontend(pool, 1), U.warmed_frontend(U.StubNet(6, "cpu", hidden=True), 6, 2, "cpu")
+    fe.warm_up()
+    assert fe.warm_up_steps == ref.warm_up_steps == 28
+    for f in range(9):
+        want = U.reference_frame(ref, U.pcm(1, f) if f != 4 else [])                         # frame 4: nothing was put, both run on silence
+        for c in (U.pcm(1, f) if f != 4 else []):
+            fe.put_audio_frame(c)
+        fe.run_step()
+        fe.run_step()
+        assert torch.equal(fe.get_next_feat(), want), f
+    assert pool_state(pool, 0) == (10, 0, 24, 8)                                            # the other row never moved
+
+
+# ---- NerfBatcher with stand-in sessions ------------------------------------------------------------------------------------------------------
+class FakeModel:
+    """keeps an EMA where the renderers keep it: enc_a <- 0.5 * enc_a + mean(auds)"""
+
+    def __init__(self):
+        self.enc_a = None
+
+
+class FakeSession:
+    def __init__(self, model, value, size=5, hw=(6, 4), body=None, cycle=None):
+        self.model, self.value, self.size, self.GH, self.GW = model, value, size, hw[0], hw[1]
+        self.fullbody_frames = body
+        self.custom_img_cycle = dict(cycle or {})
+        self.custom_index = {k: 0 for k in self.custom_img_cycle}
+        self.index, self.last_index, self.last_audio_index, self.seen = 0, None, None, []
+
+    def step(self, auds, audiotype=(0, 0), out=None):
+        from mere_fusion_amd.nerf_driver import loader_indices
+        self.last_audio_index, self.last_index = loader_indices(self.size, self.index)
+        self.index += 1
+        m = float(auds.mean())
+        self.model.enc_a = m if self.model.enc_a is None else 0.5 * self.model.enc_a + m
+        self.seen.append((tuple(audiotype), self.model.enc_a))
+        frame = torch.full((self.GH, self.GW, 3), int(self.value + self.model.enc_a) % 256, dtype=torch.uint8)
+        if out is not None:
+            out.copy_(frame)
+        return frame if out is None else out
+
+
+def _inp(v, types=None, dim=3):
+    return torch.full((B, 8, dim, 16), float(v)), list(types or [(0, 0)] * B)
+
+
+def test_batcher_keeps_one_ema_per_session_of_a_shared_model():
+    from mere_fusion_amd.nerf_serving import NerfBatcher
+    shared = FakeModel()
+    ss = [FakeSession(shared, 10), FakeSession(shared, 20), FakeSession(FakeModel(), 30)]
+    bat = NerfBatcher(ss, device="cpu")
+    assert (bat.batch_size, bat.max_sessions_per_step, len(bat.sessions), bat.device) == (4, 3, 3, torch.device("cpu"))
+    out = bat.step([_inp(1), _inp(2), _inp(3)])
+    alone = FakeSession(FakeModel(), 20)
+    want = [alone.step(torch.full((8, 3, 16), 2.0)).clone() for _ in range(B)]
+    assert torch.equal(out[1][0], torch.stack(want)) and out[1][1] == [0, 1, 2, 3] and out[1][0].dtype == torch.uint8
+    assert ss[1].seen == alone.seen and bat.enc_a[1] == alone.model.enc_a and bat.enc_a[0] != bat.enc_a[1]
+    # only=: the others' indices, EMAs and inputs are left alone
+    keep = (ss[0].index, bat.enc_a[0], ss[2].index, bat.enc_a[2])
+    out = bat.step([None, _inp(5, [(0, 0), (2, 2), (1, 0), (0, 0)]), "not looked at"], only=[1])
+    assert out[0] is None and out[2] is None and out[1][1] == [4, 4, 3, 2]
+    assert (ss[0].index, bat.enc_a[0], ss[2].index, bat.enc_a[2]) == keep and ss[1].seen[-3][0] == (2, 2)
+    for _ in range(B):
+        alone.step(torch.full((8, 3, 16), 5.0))
+    assert bat.enc_a[1] == alone.model.enc_a
+
+
+def test_batcher_refusals_come_before_any_state_moves():
+    from mere_fusion_amd.nerf_serving import NerfBatcher
+    ss = [FakeSession(FakeModel(), 10), FakeSession(FakeModel(), 20), FakeSession(FakeModel(), 30)]
+    bat = NerfBatcher(ss, device="cpu", max_sessions_per_step=2)
+    good = _inp(1)
+    bad = [
+        dict(inputs=[good, good]),                                                          # one entry per session
+        dict(inputs=[good, good, good]),                                                    # more active sessions than a step holds
+        dict(inputs=[good, None, None], only=[0, 1]),                                       # no silent-batch skip: a picked session needs an input
+        dict(inputs=[good, (torch.zeros(B + 1, 8, 3, 16), good[1]), None], only=[0, 1]),
+        dict(inputs=[good, (torch.zeros(B, 8, 3), good[1]), None], only=[0, 1]),
+        dict(inputs=[good, (torch.zeros(B, 5, 3, 16), good[1]), None], only=[0, 1]),
+        dict(inputs=[good, (np.zeros((B, 8, 3, 16), np.float32), good[1]), None], only=[0, 1]),
+        dict(inputs=[good, (good[0].to("meta"), good[1]), None], only=[0, 1]),
+        dict(inputs=[good, (good[0], good[1][:-1]), None], only=[0, 1]),
+        dict(inputs=[good, (good[0], [(0, 0, 0)] * B), None], only=[0, 1]),
+        dict(inputs=[good, (good[0], [(0, 0.5)] * B), None], only=[0, 1]),
+        dict(inputs=[good, good, good], only=[0, 3]),
+        dict(inputs=[good, good, good], only=[-1]),
+    ]
+    for kw in bad:
+        with pytest.raises(RuntimeError, match="NerfBatcher"):
+            bat.step(**kw)
+        assert [s.index for s in ss] == [0, 0, 0] and bat.enc_a == [None] * 3, kw
+    assert [o is not None for o in bat.step([good, "x", good], only=[2, 0])] == [True, False, True]
+    with pytest.raises(RuntimeError, match="at least one session"):
+        NerfBatcher([], device="cpu")
+    # a custom-video cycle of another size than the session's frames: a step's B frames leave as one block
+    for body, hw in ((None, (6, 4)), (torch.zeros(5, 9, 7, 3, dtype=torch.uint8), (9, 7))):
+        ok = FakeSession(FakeModel(), 1, body=body, cycle={2: [torch.zeros(hw + (3,), dtype=torch.uint8)] * 2})
+        assert NerfBatcher([ok], device="cpu").out_shape == [hw + (3,)]
+        wrong = FakeSession(FakeModel(), 1, body=body, cycle={2: [torch.zeros(hw + (3,), dtype=torch.uint8), torch.zeros(hw[0], hw[1] + 1, 3, dtype=torch.uint8)]})
+        with pytest.raises(RuntimeError, match=r"custom_img_cycle\[2\]"):
+            NerfBatcher([wrong], device="cpu")
+    with pytest.raises(RuntimeError, match="feature pool"):
+        NerfBatcher(ss, device="cpu", pool=SimpleNamespace(n_sessions=2))
+    with pytest.raises(RuntimeError, match="prewarm"):
+        bat.prewarm()
+    state = [(s.index, s.last_index, dict(s.custom_index)) for s in ss], list(bat.enc_a), [s.model.enc_a for s in ss]
+    bat.prewarm(torch.ones(8, 3, 16))                                                       # one frame per session, and nothing has moved
+    assert ([(s.index, s.last_index, dict(s.custom_index)) for s in ss], list(bat.enc_a), [s.model.enc_a for s in ss]) == state
+    assert [len(s.seen) for s in ss] == [B + 1, 1, B + 1]
+
+
+# ---- the schedulers ------------------------------------------------------------------------------------------------------------------------
+class FakeRing:
+    def __init__(self, places):
+        self.places, self.taken, self.msgs = places, 0, []
+
+    def free_slots(self):
+        return self.places - self.taken
+
+    def try_reserve(self, n):
+        if self.free_slots() < n:
+            return None
+        self.taken += n
+        return {"n": n}
+
+    def unreserve(self, tok):
+        self.taken -= tok["n"]
+
+    def begin_batch(self, fr, idx, stream=None, reserved=None):
+        reserved.update(fr=fr, idx=idx)
+        return reserved
+
+    def abort_batch(self, tok):
+        self.taken -= tok["n"]
+
+    def commit_batch(self, tok, audio):
+        self.msgs += [(tok["fr"][i], tok["idx"][i], audio[2 * i:2 * i + 2]) for i in range(len(tok["idx"]))]
+
+    def get(self):
+        self.taken -= 1
+        return self.msgs.pop(0)
+
+
+def _scheduler(monkeypatch, n, rings, clock):
+    from mere_fusion_amd.nerf_serving import NerfBatcher, NerfEndToEndScheduler, NerfFeaturePool
+    ev = SimpleNamespace(record=lambda *_: None, query=lambda: True, synchronize=lambda: None)
+    monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: ev)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+    pool = NerfFeaturePool(n, U.StubNet(3, "cpu"), 3, device="cpu")
+    pool.warm_up()
+    ss = [FakeSession(FakeModel(), 10 * k) for k in range(n)]
+    bat = NerfBatcher(ss, pool=pool, device="cpu")
+    return NerfEndToEndScheduler(bat, rings=rings, clock=clock, hold_s=0.0, single_stream=True), pool, ss
+
+
+def _batch(k, j, types=None):
+    chunks = sum((U.pcm(k, B * j + b) for b in range(B)), [])
+    return chunks if types is None else list(zip(chunks, types))
+
+
+def test_end_to_end_scheduler_defers_a_full_ring_and_serves_it_later(host_ops, monkeypatch):
+    """Session 0's consumer does not read: its second batch is deferred (one episode), its features do NOT advance for the deferred batch, and it is served, in
+    order, once the consumer has read.  Every frame leaves with its two (pcm, type) pairs; all-silent batches render like any other."""
+    now = [0.0]
+    rings = [FakeRing(B), FakeRing(3 * B)]
+    sch, pool, ss = _scheduler(monkeypatch, 2, rings, lambda: now[0])
+    with sch:
+        assert sch._waiter is None and abs(sch.period - B * 0.040) < 1e-12
+        silent = [1] * (2 * B)
+        mixed = [0, 0, 2, 2, 1, 0, 0, 0]
+        for j in range(3):
+            sch.submit(0, _batch(0, j), 0.001 * j)
+            sch.submit(1, _batch(1, j, silent if j == 1 else mixed), 0.001 * j + 0.0005)
+        for bad in (_batch(0, 0)[:-1], _batch(0, 0)[:-1] + [np.zeros(100, np.float32)], [(c, "x") for c in _batch(0, 0)], [(c, 0, 0) for c in _batch(0, 0)]):
+            with pytest.raises(RuntimeError):
+                sch.submit(0, bad)                                                           # refused before it is queued
+        with pytest.raises(RuntimeError, match="session 2"):
+            sch.submit(2, _batch(0, 0))
+        assert [len(q) for q in sch.queues] == [3, 3]
+        served, got1 = [], []
+        for _ in range(8):
+            now[0] += 0.05
+            done = sch.run_once() + sch.drain()
+            served += [k for k, *_ in done]
+            got1 += [rings[1].get() for k, *_ in done if k == 1 for _ in range(B)]
+        assert sch._waiter is not None and served.count(1) == 3 and served.count(0) == 1 and len(sch.queues[0]) == 2 and sch.ring_full >= 1
+        assert [g[1] for g in got1] == [0, 1, 2, 3, 4, 4, 3, 2, 1, 0, 0, 1]                # the loader's mirrored walk over 5 poses
+        assert all(g[0] is not None and g[0].dtype == torch.uint8 for g in got1)            # the all-silent batch was rendered
+        for i, g in enumerate(got1):
+            want = _batch(1, i // B, silent if i // B == 1 else mixed)[2 * (i % B):2 * (i % B) + 2]
+            assert len(g[2]) == 2 and all(np.array_equal(a[0], w[0]) and a[1] == w[1] for a, w in zip(g[2], want))
+        assert [t for t, _ in ss[1].seen[:B]] == [(0, 0), (2, 2), (1, 0), (0, 0)] and [t for t, _ in ss[1].seen[B:2 * B]] == [(1, 1)] * B
+        assert U.pool_counters(pool, 0) == (22, 3, 6, 22) and U.pool_counters(pool, 1) == (22, 1, 22, 6)   # 4 frames (first call: 4 windows) against 12
+        episodes = sch.ring_full
+        first = [rings[0].get() for _ in range(B)]                                          # the consumer catches up ...
+        assert [g[1] for g in first] == [0, 1, 2, 3]
+        for _ in range(3):
+            now[0] += 0.05
+            served += [k for k, *_ in sch.run_once() + sch.drain()]
+            while rings[0].msgs:
+                first.append(rings[0].get())
+        assert served.count(0) == 3 and not sch.pending() and sch.ring_full == episodes     # ... and the batches are served, with the indices that follow
+        assert [g[1] for g in first] == [0, 1, 2, 3, 4, 4, 3, 2, 1, 0, 0, 1] and U.pool_counters(pool, 0) == U.pool_counters(pool, 1)
+    assert sch._waiter is None
+
+
+def test_a_failed_step_does_not_advance_the_features_twice(host_ops, monkeypatch):
+    sch, pool, ss = _scheduler(monkeypatch, 1, [FakeRing(2 * B)], lambda: 1.0)
+    good_step, fail = sch.batcher.step, [True]
+
+    def step(inputs, only=None):
+        if fail[0]:
+            raise RuntimeError("step failed")
+        return good_step(inputs, only=only)
+
+    sch.batcher.step = step
+    sch.submit(0, _batch(0, 0), 0.5)
+    with pytest.raises(RuntimeError, match="step failed"):
+        sch.run_once()
+    assert len(sch.queues[0]) == 1 and sch.rings[0].taken == 0
+    after = U.pool_counters(pool, 0), pool.rings.clone(), pool.hist.clone(), len(host_ops)
+    fail[0] = False
+    sch.run_once()
+    sch.drain()
+    assert (U.pool_counters(pool, 0), len(host_ops)) == (after[0], after[3]) and torch.equal(pool.rings, after[1]) and torch.equal(pool.hist, after[2])
+    assert ss[0].index == B and len(sch.rings[0].msgs) == B
+    sch.close()
+
+
+def test_scheduler_refuses_a_pool_that_is_not_the_batchers_size(host_ops):
+    from mere_fusion_amd.nerf_serving import NerfBatcher, NerfEndToEndScheduler, NerfFeaturePool, NerfSessionScheduler
+    bat = NerfBatcher([FakeSession(FakeModel(), 1), FakeSession(FakeModel(), 2)], device="cpu")
+    for pool in (None, NerfFeaturePool(3, U.StubNet(3, "cpu"), 3, device="cpu"), "pool"):
+        with pytest.raises(RuntimeError, match="NerfFeaturePool"):
+            NerfEndToEndScheduler(bat, pool)
+    now = [0.0]
+    sch = NerfSessionScheduler(bat, clock=lambda: now[0], sync=lambda: None)
+    assert abs(sch.period - 4 * 0.040) < 1e-12 and sch.capacity == 2
+    sch.submit(1, _inp(1), 0.0)
+    sch.submit(0, _inp(2), 0.001)
+    done = sch.run_once()
+    assert [d[0] for d in done] == [1, 0] and done[0][2] == [0, 1, 2, 3] and tuple(done[0][1].shape) == (4, 6, 4, 3)
+
+
+# ---- the C ABI of the two entries ------------------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = {"mf_nerf_feat_scatter": 12, "mf_nerf_feat_windows": 13}
+
+
+def test_header_exports_and_ctypes_table_agree_for_the_new_symbols(lib_built):
+    from mere_fusion_amd import _lib
+    text = open(os.path.join(ROOT, "include", "merefusion.h")).read()
+    bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    names = sorted(set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", bare)))
+    lib = C.CDLL(lib_built)
+    for n, n_args in NEW_SYMBOLS.items():
+        assert n in names and hasattr(lib, n) and n in _lib.SIGNATURES, n
+        args = re.search(r"\b%s\s*\(([^)]*)\)" % n, bare).group(1)
+        assert len(args.split(",")) == len(_lib.SIGNATURES[n][1]) == n_args, n
+    assert sorted(_lib.SIGNATURES) == names
+    assert _lib.lib().mf_abi_version() == 4
+
+
+def test_argument_checks_that_never_launch(lib_built):
+    """every call is refused with MF_ERR_INVALID before a pointer is read or anything is enqueued (this box has no device)"""
+    from mere_fusion_amd import _lib
+    l = _lib.lib()
+    one = C.c_void_p(64)                                                # non-null, never dereferenced
+    ints = lambda *v: (C.c_int * len(v))(*v)
+    rows, starts = ints(0, 2), ints(16, 24)
+
+    def scatter(feats=one, S=2, T=27, dim=44, left=10, right=18, rings=one, N=3, R=32, rows=rows, starts=starts):
+        return l.mf_nerf_feat_scatter(feats, S, T, dim, left, right, rings, N, R, rows, starts, None)
+
+    for kw, needle in ((dict(feats=None), b"null"), (dict(rings=None), b"null"), (dict(rows=None), b"null"), (dict(starts=None), b"null"),
+                       (dict(dim=0), b"dim"), (dict(dim=1025), b"dim"), (dict(dim=-3), b"dim"), (dict(R=15), b"ring"), (dict(R=1 << 30), b"ring"),
+                       (dict(N=0), b"pool"), (dict(N=1 << 30), b"pool"), (dict(S=0), b"picked"), (dict(S=4), b"picked"), (dict(T=0), b"net frames"),
+                       (dict(left=-1), b"net frames"), (dict(left=18), b"net frames"), (dict(right=28), b"net frames"),
+                       (dict(rows=ints(0, 3)), b"out of range"), (dict(rows=ints(-1, 0)), b"out of range"), (dict(rows=ints(1 << 30, 0)), b"out of range"),
+                       (dict(rows=ints(2, 2)), b"twice"), (dict(starts=ints(16, 25)), b"leave the ring"), (dict(starts=ints(-1, 0)), b"leave the ring"),
+                       (dict(starts=ints(0, 2147483647)), b"leave the ring")):
+        assert scatter(**kw) == -1 and needle in l.mf_last_error(), (kw, l.mf_last_error())
+    fronts, heads, n_new = ints(-1, -1, -1, -1, 24, 26, 28, 30, 2, 4, 6, 8, 10, 12, 14, 16), ints(4, 7), ints(4, 1)
+    bad_front = lambda i, v: ints(*[v if q == i else f for q, f in enumerate(fronts)])
+
+    def windows(rings=one, hist=one, N=3, R=32, dim=1024, S=2, rows=rows, fronts=fronts, heads=heads, n_new=n_new, att=1, out=one):
+        return l.mf_nerf_feat_windows(rings, hist, N, R, dim, S, rows, fronts, heads, n_new, att, out, None)
+
+    for kw, needle in ((dict(rings=None), b"null"), (dict(out=None), b"null"), (dict(rows=None), b"null"), (dict(fronts=None), b"null"), (dict(n_new=None), b"null"),
+                       (dict(hist=None), b"null history"), (dict(heads=None), b"null history"), (dict(dim=0), b"dim"), (dict(dim=1025), b"dim"),
+                       (dict(R=15), b"ring"), (dict(R=-32), b"ring"), (dict(N=0), b"pool"), (dict(S=0), b"picked"), (dict(S=-2), b"picked"), (dict(S=4), b"picked"),
+                       (dict(rows=ints(0, 3)), b"out of range"), (dict(rows=ints(0, -1)), b"out of range"), (dict(rows=ints(1, 1)), b"twice"),
+                       (dict(fronts=bad_front(7, 32)), b"front"), (dict(fronts=bad_front(0, -2)), b"front"), (dict(fronts=bad_front(4, -1)), b"front"),
+                       (dict(fronts=bad_front(15, -1)), b"front"), (dict(fronts=bad_front(8, 1 << 30)), b"front"), (dict(heads=ints(8, 0)), b"history slot"),
+                       (dict(heads=ints(0, -1)), b"history slot"), (dict(n_new=ints(0, 1)), b"new windows"), (dict(n_new=ints(1, 9)), b"new windows"),
+                       (dict(att=0, hist=None, heads=None, n_new=ints(1, 4), fronts=ints(3, 5)), b"without attention"),
+                       (dict(att=0, hist=None, heads=None, n_new=ints(1, 1), fronts=ints(3, -1)), b"front")):
+        assert windows(**kw) == -1 and needle in l.mf_last_error(), (kw, l.mf_last_error())
