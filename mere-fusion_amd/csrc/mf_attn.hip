@@ -415,20 +415,10 @@ int mf_attention_composite(ConvPlan* ps, ConvPlan* pv, const ActBuf* sc, const A
 namespace {
 struct TokBuf {
     ActBuf b;
-    ~TokBuf() {
-        if (b.hi) (void)hipFree(b.hi);
-        if (b.lo) (void)hipFree(b.lo);
-    }
-    int alloc(int C, int T, int batch, bool x3) {
+    ~TokBuf() { mf_actbuf_free(&b); }
+    int alloc(int C, int T, int batch, int precision) {
         b.C = C; b.H = 1; b.W = T; b.halo = 0;
-        const size_t bytes = ((size_t)batch * b.per_batch() + 64) * sizeof(bf16_t);
-        MF_HIP(hipMalloc(&b.hi, bytes));
-        MF_HIP(hipMemset(b.hi, 0, bytes));
-        if (x3) {
-            MF_HIP(hipMalloc(&b.lo, bytes));
-            MF_HIP(hipMemset(b.lo, 0, bytes));
-        }
-        return MF_OK;
+        return mf_actbuf_alloc(&b, batch, precision);
     }
 };
 }  // namespace
@@ -440,12 +430,11 @@ extern "C" int mf_attention_forward(const float* q, const float* k, const float*
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "attention_forward: unknown precision %d", precision);
     MF_REQUIRE(mf_attention_supported(head_dim), "attention_forward: head_dim %d has no fused kernel (40, 64, 80, 160)", head_dim);
     hipStream_t s = (hipStream_t)stream;
-    const bool x3 = precision == MF_PREC_BF16X3;
     const int C = heads * head_dim;
     TokBuf bq, bk, bv, bo;
     int rc;
-    if ((rc = bq.alloc(C, tq, batch, x3)) || (rc = bk.alloc(C, tk, batch, x3)) || (rc = bv.alloc(C, tk, batch, x3)) ||
-        (rc = bo.alloc(C, tq, batch, x3)))
+    if ((rc = bq.alloc(C, tq, batch, precision)) || (rc = bk.alloc(C, tk, batch, precision)) || (rc = bv.alloc(C, tk, batch, precision)) ||
+        (rc = bo.alloc(C, tq, batch, precision)))
         return rc;
     MF_HIP(hipDeviceSynchronize());
     if ((rc = mf_rows_from_f32(q, nullptr, ActView{&bq.b, 0, C}, batch, s))) return rc;

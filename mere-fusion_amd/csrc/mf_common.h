@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdarg>
 #include <cstdlib>
+#include <map>
 #include <string>
 #include "../../include/merefusion.h"
 
@@ -19,6 +20,19 @@ static inline bool mf_debug_has(const char* word) {
     if (!e) return false;
     const std::string s = std::string(",") + e + ",";
     return s.find(std::string(",") + word + ",") != std::string::npos;
+}
+
+// A handle's state dict by name.  Tensor `k` if it is there with `numel` elements; else null, with "<who>: " and which of the two it was in mf_last_error (left
+// alone for an optional tensor that is absent: required == false).  who == "": no prefix.
+typedef std::map<std::string, const mf_tensor*> MfStateDict;
+static inline const mf_tensor* mf_sd_find(const MfStateDict& sd, const char* who, const std::string& k, int64_t numel, bool required = true) {
+    const std::string pre = *who ? std::string(who) + ": " : std::string();
+    auto it = sd.find(k);
+    if (it == sd.end()) { if (required) mf_set_error("%sstate dict has no tensor '%s'", pre.c_str(), k.c_str()); return nullptr; }
+    int64_t n = 1;
+    for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
+    if (n != numel) { mf_set_error("%stensor '%s' has %lld elements, expected %lld", pre.c_str(), k.c_str(), (long long)n, (long long)numel); return nullptr; }
+    return it->second;
 }
 
 #define MF_HIP(call)                                                                       \

@@ -24,6 +24,23 @@ struct ActBuf {
     int Wp() const { return W + 2 * halo; }
     int64_t per_batch() const { return (int64_t)Hp() * Wp() * C; }
 };
+inline void mf_actbuf_free(ActBuf* b) {
+    if (b->hi) (void)hipFree(b->hi);
+    if (b->lo) (void)hipFree(b->lo);
+    b->hi = b->lo = nullptr;
+}
+// The planes of `batch` items (whatever the buffer held is freed first): 64 elements of slack past the last pixel, zero-filled -- the halo ring and the padded
+// channels stay zero forever -- and a lo plane for every precision that has one (all but plain bf16).
+inline int mf_actbuf_alloc(ActBuf* b, int batch, int precision) {
+    mf_actbuf_free(b);
+    const size_t bytes = ((size_t)batch * b->per_batch() + 64) * sizeof(bf16_t);
+    MF_HIP(hipMalloc(&b->hi, bytes));
+    MF_HIP(hipMemset(b->hi, 0, bytes));
+    if (precision == MF_PREC_BF16) return MF_OK;
+    MF_HIP(hipMalloc(&b->lo, bytes));
+    MF_HIP(hipMemset(b->lo, 0, bytes));
+    return MF_OK;
+}
 
 // channel slice [coff, coff+C) of a buffer (concat-free skip connections, wav2lip.py:108)
 struct ActView {

@@ -14,10 +14,7 @@ struct mf_conv2d {
     int cap = 0;
     ~mf_conv2d() {
         mf_conv_plan_destroy(&plan);
-        for (ActBuf* b : {&in, &out}) {
-            if (b->hi) (void)hipFree(b->hi);
-            if (b->lo) (void)hipFree(b->lo);
-        }
+        for (ActBuf* b : {&in, &out}) mf_actbuf_free(b);
     }
 };
 
@@ -49,18 +46,7 @@ extern "C" int mf_conv2d_forward(mf_conv2d* h, const float* x, float* y, int bat
     hipStream_t s = (hipStream_t)stream;
     if (batch > h->cap) {
         MF_HIP(hipDeviceSynchronize());
-        for (ActBuf* b : {&h->in, &h->out}) {
-            if (b->hi) (void)hipFree(b->hi);
-            if (b->lo) (void)hipFree(b->lo);
-            b->hi = b->lo = nullptr;
-            const size_t bytes = ((size_t)batch * b->per_batch() + 64) * sizeof(bf16_t);
-            MF_HIP(hipMalloc(&b->hi, bytes));
-            MF_HIP(hipMemset(b->hi, 0, bytes));
-            if (h->plan.precision != MF_PREC_BF16) {
-                MF_HIP(hipMalloc(&b->lo, bytes));
-                MF_HIP(hipMemset(b->lo, 0, bytes));
-            }
-        }
+        for (ActBuf* b : {&h->in, &h->out}) { const int rc = mf_actbuf_alloc(b, batch, h->plan.precision); if (rc) return rc; }
         MF_HIP(hipDeviceSynchronize());
         h->cap = batch;
     }

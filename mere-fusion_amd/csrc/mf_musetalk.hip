@@ -12,13 +12,13 @@
 //   * GroupNorm(+SiLU) = fp64 statistics pass + one apply pass.
 #include "mf_nn.h"
 #include "mf_aux.h"
+#include "mf_graph_run.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <map>
-#include <set>
 #include <memory>
 #include <string>
 #include <tuple>
@@ -58,14 +58,10 @@ struct Net {
     static constexpr int GN_MAX_OPS = 96;
     size_t gn_slice = 0;
     int gn_count = 0;
-    std::map<int, hipGraphExec_t> graphs;
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    bool use_graph = true;
+    GraphRunner graph;
     // implicit-GEMM layers with their bound views: measured launch configurations (mf_conv_tune) on the first forward at a batch size
     struct Tunable { ConvPlan* p; ActView in, out, res; int op; ConvPlan* pq = nullptr; };   // pq: the f16 + FP6 plan that takes the launches of >= q_dual_min() frames (gn_conv)
     std::vector<Tunable> tunables;
-    std::set<int> looked_up;                     // (graph-less mode: batch sizes whose table lookup is done)
     // Side branches of the schedule: an op whose result is not needed by its successors in the list -- the hoisted k | v GEMM, a resnet's 1x1
     // shortcut conv -- runs on a second stream beside the chain (a parallel branch of the captured graph) and is joined right before its first
     // consumer.  The UNet's batch-8 launches leave most CUs idle, so the branch costs the chain nothing (Wav2Lip's forked audio encoder is worth
@@ -102,17 +98,14 @@ struct Net {
     std::string err;
 
     ~Net() {
-        for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
+        graph.drop_all();
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
         for (auto& t : tails) mf_tail_conv_destroy(t.get());
-        for (auto& b : bufs) { if (b->hi) (void)hipFree(b->hi); if (b->lo) (void)hipFree(b->lo); }
+        for (auto& b : bufs) mf_actbuf_free(b.get());
         for (void* d : dev) (void)hipFree(d);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (side_stream) (void)hipStreamDestroy(side_stream);
         for (hipEvent_t e : ev_fork) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_join) (void)hipEventDestroy(e);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
     }
 
     // ---- resources ----------------------------------------------------------------------------------------
@@ -120,9 +113,7 @@ struct Net {
         bufs.emplace_back(new ActBuf());
         ActBuf* b = bufs.back().get();
         b->C = (C + 7) / 8 * 8; b->H = H; b->W = W; b->halo = halo;
-        const size_t bytes = ((size_t)cap * b->per_batch() + 64) * sizeof(bf16_t);
-        if (hipMalloc(&b->hi, bytes) != hipSuccess || hipMemset(b->hi, 0, bytes) != hipSuccess) { err = "hipMalloc failed for an activation buffer"; return nullptr; }
-        if (precision == MF_PREC_BF16X3 && (hipMalloc(&b->lo, bytes) != hipSuccess || hipMemset(b->lo, 0, bytes) != hipSuccess)) { err = "hipMalloc failed for an activation buffer"; return nullptr; }
+        if (mf_actbuf_alloc(b, cap, precision)) { err = "hipMalloc failed for an activation buffer"; return nullptr; }
         return b;
     }
     // scratch reused by every block that asks for the same (slot, shape): blocks run one after another
@@ -141,12 +132,9 @@ struct Net {
         return d;
     }
     const float* T(const std::string& k, int64_t numel) {
-        auto it = sd.find(k);
-        if (it == sd.end()) { err = "state dict has no tensor '" + k + "'"; return nullptr; }
-        int64_t n = 1;
-        for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-        if (n != numel) { err = "tensor '" + k + "' has " + std::to_string(n) + " elements, expected " + std::to_string(numel); return nullptr; }
-        return it->second->data;
+        const mf_tensor* t = mf_sd_find(sd, "", k, numel);
+        if (!t) { err = mf_last_error(); return nullptr; }
+        return t->data;
     }
     bool has(const std::string& k) const { return sd.count(k) != 0; }
     ConvPlan* new_plan() { plans.emplace_back(new ConvPlan()); return plans.back().get(); }
@@ -737,63 +725,18 @@ struct Net {
         }
         return MF_OK;
     }
-    // The explicit warm-up behind mf_unet_tune / mf_vae_tune: measure at batch B on the data the last forward at B left in the buffers, then drop
-    // the graph captured with the old configurations (the next forward re-captures).  Seconds per full-size network: call it at start-up for every
-    // batch size the serving loop can emit, or ship MF_TUNE_CACHE.
+    // launch configurations: a table lookup per implicit-GEMM layer, never a measurement
+    void lookup(int B) {
+        for (auto& t : tunables)
+            if (mf_conv_tune_lookup(t.p, t.in, B)) name_kernel(t, B);
+    }
+    // The explicit warm-up behind mf_unet_tune / mf_vae_tune (GraphRunner::retune).  Seconds per full-size network: call it at start-up for every batch size
+    // the serving loop can emit, or ship MF_TUNE_CACHE.
     int tune(int B, hipStream_t s) {
-        auto it = graphs.find(B);
-        if (use_graph && it == graphs.end()) { mf_set_error("tune: run one forward at batch %d first (the layers are timed on its buffers)", B); return MF_ERR_INVALID; }
-        MF_HIP(hipStreamSynchronize(cap_stream));
-        MF_HIP(hipStreamSynchronize(s));
-        int rc = measure(B, s);
-        if (rc) return rc;
-        MF_HIP(hipStreamSynchronize(s));
-        // the next forward at B runs eagerly again (layers that share a measured signature size their split-K workspaces there), then re-captures
-        if (use_graph) { if (it->second) (void)hipGraphExecDestroy(it->second); graphs.erase(it); }
-        return MF_OK;
+        return graph.retune(B, s, "tune: run one forward", [&](hipStream_t st) { return measure(B, st); });
     }
     int run(int B, hipStream_t s) {
-        if (!use_graph) {
-            if (!looked_up.count(B)) {
-                looked_up.insert(B);
-                for (auto& t : tunables)
-                    if (mf_conv_tune_lookup(t.p, t.in, B)) name_kernel(t, B);
-            }
-            return run_body(B, s);
-        }
-        auto it = graphs.find(B);
-        if (it == graphs.end()) {                                                        // first call eager
-            graphs.emplace(B, nullptr);
-            // launch configurations: a table lookup per implicit-GEMM layer (MF_TUNE_CACHE / the shipped table), never a measurement -- a serving loop
-            // that meets a new batch size pays one eager forward and one capture, nothing more.  (MF_AUTOTUNE=1, development: measure here.)
-            for (auto& t : tunables)
-                if (mf_conv_tune_lookup(t.p, t.in, B)) name_kernel(t, B);
-            int rc = run_body(B, s);
-            if (rc || !mf_autotune_enabled()) return rc;
-            if ((rc = measure(B, s))) return rc;
-            return run_body(B, s);
-        }
-        if (!it->second) {
-            hipGraph_t graph = nullptr;
-            MF_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-            int rc = run_body(B, cap_stream);
-            hipError_t e = hipStreamEndCapture(cap_stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            if (e != hipSuccess) { mf_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return MF_ERR_HIP; }
-            hipGraphExec_t exec = nullptr;
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) { mf_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return MF_ERR_HIP; }
-            it->second = exec;
-        }
-        // the graph replays on the handle's own stream, fenced by events against the caller's stream: the
-        // caller usually hands in the legacy NULL stream, whose implicit ordering a graph launch does not inherit
-        MF_HIP(hipEventRecord(ev_in, s));
-        MF_HIP(hipStreamWaitEvent(cap_stream, ev_in, 0));
-        MF_HIP(hipGraphLaunch(it->second, cap_stream));
-        MF_HIP(hipEventRecord(ev_out, cap_stream));
-        MF_HIP(hipStreamWaitEvent(s, ev_out, 0));
-        return MF_OK;
+        return graph.run(B, s, [&](hipStream_t st) { return run_body(B, st); }, [&] { lookup(B); }, [&](hipStream_t st) { return measure(B, st); });
     }
     int init(const mf_tensor* weights, int n, int prec, int max_batch, int max_groups, int ln_tokens_per_sample = 0) {
         precision = prec; cap = max_batch;
@@ -815,16 +758,14 @@ struct Net {
             const int n = (int)(GN_MAX_OPS * gn_slice + ln_cap_doubles);
             push("groupnorm / layernorm statistics reset", "k_zero_f64", 0.0, [=](int, hipStream_t s) { return mf_zero_f64(st, n, s); });
         }
-        MF_HIP(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-        MF_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        MF_HIP(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
-        MF_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
         // MF_NO_GRAPH=1: every forward an eager launch chain (side branches still forked onto the second stream).  MF_NO_GRAPH=2: eager AND single-stream, no
-        // side branches -- the host-lean mode of a serving rank: on ROCm 7.2 any hipGraphLaunch or cross-stream event wait keeps a runtime thread spinning for
+        // side branches -- the host-lean mode of a serving rank: on ROCm 7.2 any graph launch or cross-stream event wait keeps a runtime thread spinning for
         // as long as the GPU is busy (0.8 - 0.9 host core per process, tools/host_wait_probe2.py), a plain launch chain on one stream does not.
-        const char* ng = std::getenv("MF_NO_GRAPH");
-        use_graph = !(ng && (ng[0] == '1' || ng[0] == '2'));
-        fork_on = !(ng && ng[0] == '2');
+        const int ng = mf_no_graph_mode();
+        fork_on = ng != 2;
+        const int rc = graph.init(ng == 0);
+        if (rc) return rc;
+        MF_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
         return MF_OK;
     }
 };

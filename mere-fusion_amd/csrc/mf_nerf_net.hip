@@ -175,7 +175,7 @@ struct TokenNet {
 
     ~TokenNet() {
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) { if (b->hi) (void)hipFree(b->hi); if (b->lo) (void)hipFree(b->lo); }
+        for (auto& b : bufs) mf_actbuf_free(b.get());
         for (void* d : dev) (void)hipFree(d);
     }
     ActBuf* seq(int C) {
@@ -185,11 +185,7 @@ struct TokenNet {
         return b;
     }
     int alloc() {
-        for (auto& b : bufs) {
-            const size_t bytes = ((size_t)cap_batches * b->per_batch() + 64) * sizeof(bf16_t);
-            MF_HIP(hipMalloc(&b->hi, bytes)); MF_HIP(hipMemset(b->hi, 0, bytes));
-            if (precision == MF_PREC_BF16X3) { MF_HIP(hipMalloc(&b->lo, bytes)); MF_HIP(hipMemset(b->lo, 0, bytes)); }
-        }
+        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap_batches, precision); if (rc) return rc; }
         return MF_OK;
     }
     // Linear(cin -> cout, bias=False) (network.py:79) as a 1x1 convolution; `w` is [cout][cin_buf] with the input-channel order of

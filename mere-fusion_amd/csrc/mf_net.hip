@@ -7,9 +7,10 @@
 // residual epilogues, torch.cat as channel slices of one buffer); the rest are one-pass HBM kernels on the padded NHWC (hi, lo) planes:
 //   max-pool, per-pixel L2Norm, global average pool, y = x * s[b][c] + t (+ v[b][c]) (channel attention, broadcast adds), nearest upsample,
 //   bilinear resize with align_corners (the parser's output head).
-// The op list is replayed as a hipGraph per batch size like the other stages.
+// The op list is one hipGraph per batch size like the other stages (mf_graph_run.h).
 #include "mf_nn.h"
 #include "mf_aux.h"
+#include "mf_graph_run.h"
 #include "mf_net_planes.h"
 #include <cfloat>
 #include <cmath>
@@ -141,25 +142,23 @@ struct mf_net {
     std::vector<Tunable> tunables;
     std::vector<std::string> names;
     std::vector<double> flops;
-    std::map<int, hipGraphExec_t> graphs;
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    bool use_graph = true;
+    GraphRunner graph;
     void* scratch = nullptr;                                               // mf_net_scratch: the candidate lists of mf_s3fd_detect
     size_t scratch_bytes = 0;
 
     ~mf_net() {
-        for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
+        graph.drop_all();
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) { if (b->hi) (void)hipFree(b->hi); if (b->lo) (void)hipFree(b->lo); }
+        for (auto& b : bufs) mf_actbuf_free(b.get());
         for (float* d : dev) (void)hipFree(d);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
     }
     ActBuf* B(int id) { return id >= 0 && id < (int)bufs.size() ? bufs[id].get() : nullptr; }
     int run_body(int batch, hipStream_t s) {
         for (auto& op : ops) { int rc = op(batch, s); if (rc) return rc; }
+        return MF_OK;
+    }
+    int measure(int batch, hipStream_t s) {
+        for (auto& t : tunables) { int rc = mf_conv_tune(t.p, t.in, t.out, t.res, batch, s); if (rc) return rc; }
         return MF_OK;
     }
 };
@@ -171,10 +170,8 @@ extern "C" int mf_net_create(int max_batch, int precision, mf_net** out) {
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "net_create: unknown precision %d", precision);
     std::unique_ptr<mf_net> h(new mf_net());
     h->precision = precision; h->cap = max_batch;
-    MF_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-    { const char* e = getenv("MF_NO_GRAPH"); h->use_graph = !(e && atoi(e) != 0); }
+    const int rc = h->graph.init(mf_no_graph_mode() == 0);   // eager for any non-zero MF_NO_GRAPH
+    if (rc) return rc;
     *out = h.release();
     return MF_OK;
 }
@@ -184,10 +181,8 @@ extern "C" int mf_net_buffer(mf_net* h, int C, int H, int W, int halo) {
     h->bufs.emplace_back(new ActBuf());
     ActBuf* b = h->bufs.back().get();
     b->C = (C + 7) / 8 * 8; b->H = H; b->W = W; b->halo = halo;
-    const size_t bytes = ((size_t)h->cap * b->per_batch() + 64) * sizeof(bf16_t);
-    if (hipMalloc(&b->hi, bytes) != hipSuccess || hipMemset(b->hi, 0, bytes) != hipSuccess) { mf_set_error("net_buffer: hipMalloc of %zu bytes failed", bytes); return MF_ERR_HIP; }
-    if (h->precision == MF_PREC_BF16X3 && (hipMalloc(&b->lo, bytes) != hipSuccess || hipMemset(b->lo, 0, bytes) != hipSuccess)) { mf_set_error("net_buffer: hipMalloc failed"); return MF_ERR_HIP; }
-    return (int)h->bufs.size() - 1;
+    const int rc = mf_actbuf_alloc(b, h->cap, h->precision);
+    return rc ? rc : (int)h->bufs.size() - 1;
 }
 
 extern "C" int mf_net_conv(mf_net* h, const mf_conv2d_desc* d, const float* weight, const float* bias, const float* bn_gamma, const float* bn_beta,
@@ -313,56 +308,16 @@ extern "C" int mf_net_set_input(mf_net* h, int buf, const float* nchw, int C, in
     return mf_nchw_to_act(nchw, C, *b, batch, (hipStream_t)stream);
 }
 
-// the explicit warm-up: time every conv's launch configurations on the buffers the last run at this batch size filled, drop the graph captured with the old ones
+// the explicit warm-up (GraphRunner::retune): time every conv's launch configurations on the buffers the last run at this batch size filled
 extern "C" int mf_net_tune(mf_net* h, int batch, void* stream) {
     MF_REQUIRE(h && batch >= 1 && batch <= h->cap, "net_tune: batch %d exceeds the capacity %d", batch, h ? h->cap : 0);
-    hipStream_t s = (hipStream_t)stream;
-    auto it = h->graphs.find(batch);
-    MF_REQUIRE(!h->use_graph || it != h->graphs.end(), "net_tune: run the net once at batch %d first (the layers are timed on its buffers)", batch);
-    MF_HIP(hipStreamSynchronize(h->cap_stream));
-    MF_HIP(hipStreamSynchronize(s));
-    for (auto& t : h->tunables) {
-        int rc = mf_conv_tune(t.p, t.in, t.out, t.res, batch, s);
-        if (rc) return rc;
-    }
-    MF_HIP(hipStreamSynchronize(s));
-    if (h->use_graph) { if (it->second) (void)hipGraphExecDestroy(it->second); h->graphs.erase(it); }   // next run: eager (workspaces), then re-capture
-    return MF_OK;
+    return h->graph.retune(batch, (hipStream_t)stream, "net_tune: run the net once", [=](hipStream_t s) { return h->measure(batch, s); });
 }
 
 extern "C" int mf_net_run(mf_net* h, int batch, void* stream) {
     MF_REQUIRE(h && batch >= 1 && batch <= h->cap, "net_run: batch %d exceeds the capacity %d", batch, h ? h->cap : 0);
-    hipStream_t s = (hipStream_t)stream;
-    if (!h->use_graph) {
-        for (auto& t : h->tunables) mf_conv_tune_lookup(t.p, t.in, batch);
-        return h->run_body(batch, s);
-    }
-    auto it = h->graphs.find(batch);
-    if (it == h->graphs.end()) {                                                                        // first call eager (split-K workspaces grow here)
-        h->graphs.emplace(batch, nullptr);
-        for (auto& t : h->tunables) mf_conv_tune_lookup(t.p, t.in, batch);                              // launch configurations: a table lookup, never a measurement
-        int rc = h->run_body(batch, s);
-        if (rc || !mf_autotune_enabled()) return rc;
-        for (auto& t : h->tunables)                                                                     // MF_AUTOTUNE=1 (development): measure here, then the real outputs again
-            if ((rc = mf_conv_tune(t.p, t.in, t.out, t.res, batch, s))) return rc;
-        return h->run_body(batch, s);
-    }
-    if (!it->second) {
-        hipGraph_t graph = nullptr;
-        MF_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        int rc = h->run_body(batch, h->cap_stream);
-        hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        MF_HIP(e);
-        MF_HIP(hipGraphInstantiate(&it->second, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-    }
-    MF_HIP(hipEventRecord(h->ev_in, s));
-    MF_HIP(hipStreamWaitEvent(h->cap_stream, h->ev_in, 0));
-    MF_HIP(hipGraphLaunch(it->second, h->cap_stream));
-    MF_HIP(hipEventRecord(h->ev_out, h->cap_stream));
-    MF_HIP(hipStreamWaitEvent(s, h->ev_out, 0));
-    return MF_OK;
+    return h->graph.run(batch, (hipStream_t)stream, [=](hipStream_t s) { return h->run_body(batch, s); },
+                        [=] { for (auto& t : h->tunables) mf_conv_tune_lookup(t.p, t.in, batch); }, [=](hipStream_t s) { return h->measure(batch, s); });
 }
 
 extern "C" int mf_net_get_output(mf_net* h, int buf, int coff, int C, float* nchw, int batch, void* stream) {

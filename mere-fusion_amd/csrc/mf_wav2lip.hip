@@ -5,16 +5,15 @@
 // block b and the last layer of decoder block 6-b write into disjoint channel slices of ONE buffer
 // (cat[k] = [decoder k | encoder 6-k]), and the next layers read slices or the whole of it.
 // The audio encoder runs on a forked stream beside the face encoder; the whole schedule is
-// captured once per batch size into a hipGraph and replayed.
+// one hipGraph per batch size (mf_graph_run.h).
 #include "mf_conv.h"
 #include "mf_aux.h"
+#include "mf_graph_run.h"
 #include <map>
-#include <set>
 #include <memory>
 #include <string>
 #include <vector>
 #include <cstring>
-#include <cstdlib>
 
 namespace {
 
@@ -111,40 +110,28 @@ struct mf_wav2lip {
     float* head_w = nullptr;
     float* head_b = nullptr;
     std::map<std::string, ActView> taps;
-    std::map<int, hipGraphExec_t> graphs;
-    std::set<int> looked_up;                     // batch sizes whose launch configurations have been looked up (no-graph path)
+    GraphRunner graph;
     hipStream_t side = nullptr;       // audio-encoder lane
-    hipStream_t cap_stream = nullptr; // capture origin
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_gin = nullptr, ev_gout = nullptr;
-    bool use_graph = true;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
     ~mf_wav2lip() {
-        for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
+        graph.drop_all();
         for (auto& s : steps) mf_conv_plan_destroy(&s->plan);
         free_bufs();
         if (head_w) (void)hipFree(head_w);
         if (head_b) (void)hipFree(head_b);
         if (side) (void)hipStreamDestroy(side);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
-        if (ev_gin) (void)hipEventDestroy(ev_gin);
-        if (ev_gout) (void)hipEventDestroy(ev_gout);
     }
-    void free_bufs() {
-        for (auto& b : bufs) {
-            if (b->hi) (void)hipFree(b->hi);
-            if (b->lo) (void)hipFree(b->lo);
-            b->hi = b->lo = nullptr;
-        }
-    }
+    void free_bufs() { for (auto& b : bufs) mf_actbuf_free(b.get()); }
     ActBuf* new_buf(int C, int H, int W, int halo) {
         bufs.emplace_back(new ActBuf());
         ActBuf* b = bufs.back().get();
         b->C = C; b->H = H; b->W = W; b->halo = halo;
         return b;
     }
-    int add_step(const LayerSpec& ls, int group, const std::map<std::string, const mf_tensor*>& sd,
+    int add_step(const LayerSpec& ls, int group, const MfStateDict& sd,
                  ActView in, ActView out);
     int ensure_capacity(int batch);
     int run_body(int batch, hipStream_t s);
@@ -155,16 +142,9 @@ struct mf_wav2lip {
 
 namespace {
 
-const float* find(const std::map<std::string, const mf_tensor*>& sd, const std::string& key, int64_t numel) {
-    auto it = sd.find(key);
-    if (it == sd.end()) { mf_set_error("wav2lip: state dict has no tensor '%s'", key.c_str()); return nullptr; }
-    int64_t n = 1;
-    for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-    if (n != numel) {
-        mf_set_error("wav2lip: tensor '%s' has %lld elements, expected %lld", key.c_str(), (long long)n, (long long)numel);
-        return nullptr;
-    }
-    return it->second->data;
+const float* find(const MfStateDict& sd, const std::string& key, int64_t numel) {
+    const mf_tensor* t = mf_sd_find(sd, "wav2lip", key, numel);
+    return t ? t->data : nullptr;
 }
 
 ActView whole(ActBuf* b) { return ActView{b, 0, b->C}; }
@@ -172,7 +152,7 @@ ActView slice(ActBuf* b, int coff, int C) { return ActView{b, coff, C}; }
 
 }  // namespace
 
-int mf_wav2lip::add_step(const LayerSpec& ls, int group, const std::map<std::string, const mf_tensor*>& sd,
+int mf_wav2lip::add_step(const LayerSpec& ls, int group, const MfStateDict& sd,
                          ActView in, ActView out) {
     const std::string p = ls.prefix;
     const int64_t wn = (int64_t)ls.cin * ls.cout * ls.k * ls.k;
@@ -202,34 +182,17 @@ int mf_wav2lip::add_step(const LayerSpec& ls, int group, const std::map<std::str
 
 int mf_wav2lip::ensure_capacity(int batch) {
     if (batch <= cap) return MF_OK;
-    for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
+    graph.drop_all();
     MF_HIP(hipDeviceSynchronize());
     free_bufs();
-    for (auto& b : bufs) {
-        // +64 elements of slack past the last pixel
-        const size_t bytes = ((size_t)batch * b->per_batch() + 64) * sizeof(bf16_t);
-        MF_HIP(hipMalloc(&b->hi, bytes));
-        MF_HIP(hipMemset(b->hi, 0, bytes));   // halo ring and padded channels stay zero forever
-        if (precision == MF_PREC_BF16X3) {
-            MF_HIP(hipMalloc(&b->lo, bytes));
-            MF_HIP(hipMemset(b->lo, 0, bytes));
-        }
-    }
+    for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), batch, precision); if (rc) return rc; }
     MF_HIP(hipDeviceSynchronize());
     cap = batch;
     return MF_OK;
 }
 
 int mf_wav2lip::run_body(int batch, hipStream_t s) {
-    const bool fork = true;                                           // (one serial chain measured 11 % slower: 1.12 vs 1.00 ms at batch 16)
-    if (!fork) {
-        for (int g = 0; g < 3; ++g)
-            for (auto& st : steps)
-                if (st->group == g) { int rc = mf_conv_launch(&st->plan, st->in, st->out, st->res, batch, s); if (rc) return rc; }
-        return MF_OK;
-    }
-    // fork: audio encoder on the side stream beside the face encoder, join before the decoder
+    // fork: audio encoder on the side stream beside the face encoder, join before the decoder (one serial chain measured 11 % slower: 1.12 vs 1.00 ms at batch 16)
     MF_HIP(hipEventRecord(ev_fork, s));
     MF_HIP(hipStreamWaitEvent(side, ev_fork, 0));
     for (auto& st : steps)
@@ -252,61 +215,14 @@ int mf_wav2lip::measure(int batch, hipStream_t s) {
     return MF_OK;
 }
 
-// mf_wav2lip_tune: the explicit warm-up -- time every layer's launch configurations on the buffers the last forward at this batch size filled, drop the
-// graph captured with the old ones
+// mf_wav2lip_tune: the explicit warm-up (GraphRunner::retune)
 int mf_wav2lip::tune(int batch, hipStream_t s) {
-    auto it = graphs.find(batch);
-    if (use_graph && it == graphs.end()) { mf_set_error("wav2lip_tune: run one forward at batch %d first (the layers are timed on its buffers)", batch); return MF_ERR_INVALID; }
-    MF_HIP(hipStreamSynchronize(cap_stream));
-    MF_HIP(hipStreamSynchronize(s));
-    int rc = measure(batch, s);
-    if (rc) return rc;
-    MF_HIP(hipStreamSynchronize(s));
-    // the next forward at this batch runs eagerly again (split-K workspaces of the new configurations), then re-captures
-    if (use_graph) { if (it->second) (void)hipGraphExecDestroy(it->second); graphs.erase(it); }
-    return MF_OK;
+    return graph.retune(batch, s, "wav2lip_tune: run one forward", [&](hipStream_t st) { return measure(batch, st); });
 }
 
 int mf_wav2lip::run(int batch, hipStream_t s) {
-    if (!use_graph) {
-        if (looked_up.insert(batch).second)                                          // (MF_NO_GRAPH: one table lookup per layer and batch size, not one per forward)
-            for (auto& st : steps) mf_conv_tune_lookup(&st->plan, st->in, batch);
-        return run_body(batch, s);
-    }
-    auto it = graphs.find(batch);
-    if (it == graphs.end()) {
-        // first forward at this batch size runs eagerly (it also sets the kernels' LDS attributes,
-        // which must not happen inside a capture); the second one captures
-        graphs.emplace(batch, nullptr);
-        // launch configurations: a table lookup per layer (MF_TUNE_CACHE / the table shipped beside the library), never a measurement
-        for (auto& st : steps) mf_conv_tune_lookup(&st->plan, st->in, batch);
-        int rc = run_body(batch, s);
-        if (rc || !mf_autotune_enabled()) return rc;
-        // MF_AUTOTUNE=1 (development): the buffers hold real data now -- measure every implicit-GEMM layer in place, then run once more so that the
-        // outputs belong to the configurations the graph will capture
-        if ((rc = measure(batch, s))) return rc;
-        return run_body(batch, s);
-    }
-    if (it->second == nullptr) {
-        hipGraph_t graph = nullptr;
-        MF_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-        int rc = run_body(batch, cap_stream);
-        hipError_t e = hipStreamEndCapture(cap_stream, &graph);
-        if (rc != MF_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) { mf_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return MF_ERR_HIP; }
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { mf_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return MF_ERR_HIP; }
-        it->second = exec;
-    }
-    // replay on the handle's own stream, fenced by events against the caller's (usually the legacy NULL) stream
-    MF_HIP(hipEventRecord(ev_gin, s));
-    MF_HIP(hipStreamWaitEvent(cap_stream, ev_gin, 0));
-    MF_HIP(hipGraphLaunch(it->second, cap_stream));
-    MF_HIP(hipEventRecord(ev_gout, cap_stream));
-    MF_HIP(hipStreamWaitEvent(s, ev_gout, 0));
-    return MF_OK;
+    return graph.run(batch, s, [&](hipStream_t st) { return run_body(batch, st); },
+                     [&] { for (auto& st : steps) mf_conv_tune_lookup(&st->plan, st->in, batch); }, [&](hipStream_t st) { return measure(batch, st); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -316,7 +232,7 @@ extern "C" int mf_wav2lip_create(const mf_tensor* weights, int n_weights, int pr
     MF_REQUIRE(weights && out && n_weights > 0, "wav2lip_create: null argument");
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "wav2lip_create: unknown precision %d", precision);
     *out = nullptr;
-    std::map<std::string, const mf_tensor*> sd;
+    MfStateDict sd;
     for (int i = 0; i < n_weights; ++i) {
         MF_REQUIRE(weights[i].name && weights[i].data, "wav2lip_create: tensor %d has no name/data", i);
         std::string k = weights[i].name;
@@ -326,14 +242,11 @@ extern "C" int mf_wav2lip_create(const mf_tensor* weights, int n_weights, int pr
     }
     std::unique_ptr<mf_wav2lip> h(new mf_wav2lip());
     h->precision = precision;
-    const char* ng = std::getenv("MF_NO_GRAPH");
-    h->use_graph = !(ng && ng[0] == '1');
     MF_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    MF_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
+    int rc = h->graph.init(mf_no_graph_mode() != 1);   // eager under MF_NO_GRAPH=1 only: =2 (the MuseTalk nets' single-stream mode) leaves this handle on its graphs
+    if (rc) return rc;
     MF_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     MF_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_gin, hipEventDisableTiming));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_gout, hipEventDisableTiming));
 
     // ---- buffers ---------------------------------------------------------------------------
     h->mel_in = h->new_buf(8, 80, 16, 1);     // 1 real channel, padded to an 8-channel group
@@ -342,7 +255,6 @@ extern "C" int mf_wav2lip_create(const mf_tensor* weights, int n_weights, int pr
     for (int k = 0; k < 7; ++k) cat[k] = h->new_buf(kDecC[k] + kSkipC[k], kCatHW[k], kCatHW[k], 1);
     h->out0 = h->new_buf(32, 96, 96, 0);
 
-    int rc;
     // ---- audio encoder: 80x16 -> 27x16 -> 9x6 -> 3x3 -> 1x1 ----------------------------------
     {
         const int hs[13] = {80, 80, 80, 27, 27, 27, 9, 9, 9, 3, 3, 1, 1};
@@ -454,9 +366,7 @@ extern "C" int mf_wav2lip_forward_u8_rows(mf_wav2lip* h, const float* mel, const
 }
 
 extern "C" int mf_wav2lip_graph_captured(const mf_wav2lip* h, int batch) {
-    if (!h) return 0;
-    auto it = h->graphs.find(batch);
-    return it != h->graphs.end() && it->second != nullptr;
+    return h && h->graph.captured(batch);
 }
 
 extern "C" int mf_wav2lip_read_tap(mf_wav2lip* h, const char* tap, float* dst, int batch, void* stream) {

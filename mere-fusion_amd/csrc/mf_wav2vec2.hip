@@ -13,6 +13,7 @@
 // padding symmetric and the output length T; its GELU and the `hidden + pos` add are the conv epilogue (residual after activation).
 #include "mf_nn.h"
 #include "mf_aux.h"
+#include "mf_graph_run.h"
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -85,12 +86,8 @@ struct mf_wav2vec2 {
 
     ~mf_wav2vec2() {
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) { if (b->hi) (void)hipFree(b->hi); if (b->lo) (void)hipFree(b->lo); }
+        for (auto& b : bufs) mf_actbuf_free(b.get());
         for (float* f : dev_f32) (void)hipFree(f);
-        for (auto& g : graphs) if (g.second) (void)hipGraphExecDestroy(g.second);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
     }
     ActBuf* seq(int C, int T_, int halo = 0) {
         bufs.emplace_back(new ActBuf());
@@ -99,11 +96,7 @@ struct mf_wav2vec2 {
         return b;
     }
     int alloc() {
-        for (auto& b : bufs) {
-            const size_t bytes = ((size_t)cap * b->per_batch() + 64) * sizeof(bf16_t);
-            MF_HIP(hipMalloc(&b->hi, bytes)); MF_HIP(hipMemset(b->hi, 0, bytes));
-            if (precision == MF_PREC_BF16X3) { MF_HIP(hipMalloc(&b->lo, bytes)); MF_HIP(hipMemset(b->lo, 0, bytes)); }
-        }
+        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap, precision); if (rc) return rc; }
         return MF_OK;
     }
     ConvPlan* new_plan() { plans.emplace_back(new ConvPlan()); return plans.back().get(); }
@@ -114,26 +107,13 @@ struct mf_wav2vec2 {
         return MF_OK;
     }
     int forward(const float* wav, int S, float* out, hipStream_t s);
-    int body(int S, hipStream_t s, ActBuf** last);
-    // the ~240 launches between the input normalisation and the output copy replay as one hipGraph per window count (first call eager: split-K
-    // workspaces are sized there; second call captures)
-    std::map<int, hipGraphExec_t> graphs;
-    std::map<int, ActBuf*> graph_last;
-    hipStream_t cap_stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    bool use_graph = true;
+    int body(int S, hipStream_t s);
+    GraphRunner graph;   // the ~240 launches between the input normalisation and the output copy: one hipGraph per window count
 };
 
 namespace {
 
-const mf_tensor* get(const std::map<std::string, const mf_tensor*>& sd, const std::string& k, int64_t numel, bool required = true) {
-    auto it = sd.find(k);
-    if (it == sd.end()) { if (required) mf_set_error("wav2vec2: state dict has no tensor '%s'", k.c_str()); return nullptr; }
-    int64_t cnt = 1;
-    for (int i = 0; i < it->second->ndim; ++i) cnt *= it->second->shape[i];
-    if (cnt != numel) { mf_set_error("wav2vec2: tensor '%s' has %lld elements, expected %lld", k.c_str(), (long long)cnt, (long long)numel); return nullptr; }
-    return it->second;
-}
+const mf_tensor* get(const MfStateDict& sd, const std::string& k, int64_t numel, bool required = true) { return mf_sd_find(sd, "wav2vec2", k, numel, required); }
 
 int conv1d_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int k, int stride, int pad, int T_in, int act, int residual, int precision) {
     mf_conv2d_desc d{};
@@ -150,39 +130,12 @@ int mf_wav2vec2::forward(const float* wav, int S, float* out, hipStream_t s) {
     hipLaunchKernelGGL(k_w2v_normalize, dim3(S), dim3(1024), 0, s, wav, n, cfg.do_normalize, wav_in->hi + mf_interior(*wav_in),
                        wav_in->lo ? wav_in->lo + mf_interior(*wav_in) : nullptr, wav_in->C, wav_in->per_batch());
     MF_HIP(hipGetLastError());
-    ActBuf* cur = nullptr;
-    if (!use_graph) {
-        if ((rc = body(S, s, &cur))) return rc;
-    } else {
-        auto it = graphs.find(S);
-        if (it == graphs.end()) {
-            graphs.emplace(S, nullptr);
-            if ((rc = body(S, s, &cur))) return rc;
-            graph_last[S] = cur;
-        } else {
-            if (!it->second) {
-                hipGraph_t graph = nullptr;
-                MF_HIP(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-                rc = body(S, cap_stream, &cur);
-                hipError_t e = hipStreamEndCapture(cap_stream, &graph);
-                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                MF_HIP(e);
-                MF_HIP(hipGraphInstantiate(&it->second, graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-            }
-            cur = graph_last[S];
-            MF_HIP(hipEventRecord(ev_in, s));
-            MF_HIP(hipStreamWaitEvent(cap_stream, ev_in, 0));
-            MF_HIP(hipGraphLaunch(it->second, cap_stream));
-            MF_HIP(hipEventRecord(ev_out, cap_stream));
-            MF_HIP(hipStreamWaitEvent(s, ev_out, 0));
-        }
-    }
-    if (cfg.out_hidden) return mf_rows_to_f32(V(cur), out, S, s);
+    if ((rc = graph.run(S, s, [&](hipStream_t st) { return body(S, st); }, nullptr, nullptr))) return rc;
+    if (cfg.out_hidden) return mf_rows_to_f32(V(xb), out, S, s);
     return mf_rows_to_f32(ActView{logit, 0, cfg.vocab}, out, S, s);
 }
 
-int mf_wav2vec2::body(int S, hipStream_t s, ActBuf** last) {
+int mf_wav2vec2::body(int S, hipStream_t s) {
     int rc;
     // feature extractor: conv -> LayerNorm over channels -> GELU (Wav2Vec2LayerNormConvLayer)
     ActBuf* x = wav_in;
@@ -198,11 +151,10 @@ int mf_wav2vec2::body(int S, hipStream_t s, ActBuf** last) {
     const int gc = cfg.hidden / cfg.pos_groups;
     for (int g = 0; g < cfg.pos_groups; ++g)
         if ((rc = mf_conv_launch(pos[g], ActView{hid, g * gc, gc}, ActView{xa, g * gc, gc}, ActView{hid, g * gc, gc}, S, s))) return rc;
-    ActBuf *cur = xa, *oth = xb;
-    if (!cfg.stable_ln) {       // post-LN encoder: LayerNorm right after the positional add (Wav2Vec2Encoder.forward)
-        if ((rc = mf_layernorm(V(cur), V(oth), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
-        std::swap(cur, oth);
-    }
+    // The encoder's one LayerNorm moves the hidden state xa -> xb: in front of the layers (post-LN, Wav2Vec2Encoder.forward), which then work in xb, or behind
+    // them ("stable" pre-LN), which work in xa.  Every layer ends in the buffer it began in, so the last hidden state is xb whatever the depth.
+    ActBuf *cur = cfg.stable_ln ? xa : xb, *oth = cfg.stable_ln ? xb : xa;
+    if (!cfg.stable_ln && (rc = mf_layernorm(V(xa), V(xb), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
     for (auto& L : layers) {
         if (cfg.stable_ln) {
             // h = x + attn(LN(x)); x = h + ff(LN(h))   (Wav2Vec2EncoderLayerStableLayerNorm)
@@ -226,13 +178,9 @@ int mf_wav2vec2::body(int S, hipStream_t s, ActBuf** last) {
             if ((rc = mf_layernorm(V(oth), V(cur), L.g2, L.b2, cfg.layer_norm_eps, S, s))) return rc;
         }
     }
-    if (cfg.stable_ln) {
-        if ((rc = mf_layernorm(V(cur), V(oth), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
-        std::swap(cur, oth);
-    }
-    *last = cur;
+    if (cfg.stable_ln && (rc = mf_layernorm(V(xa), V(xb), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
     if (cfg.out_hidden) return MF_OK;
-    return mf_conv_launch(head, V(cur), ActView{logit, 0, vocab_pad}, ActView{}, S, s);
+    return mf_conv_launch(head, V(xb), ActView{logit, 0, vocab_pad}, ActView{}, S, s);
 }
 
 extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor* weights, int n_weights, int n_samples, int max_windows, int precision,
@@ -250,7 +198,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
                "wav2vec2_create: positional conv needs an even kernel and channel groups that are multiples of 8");
     MF_REQUIRE(c.out_hidden || c.vocab > 0, "wav2vec2_create: vocab size missing");
     MF_REQUIRE(max_windows >= 1 && max_windows <= 64, "wav2vec2_create: 1..64 windows per call");
-    std::map<std::string, const mf_tensor*> sd;
+    MfStateDict sd;
     for (int i = 0; i < n_weights; ++i) {
         MF_REQUIRE(weights[i].name && weights[i].data, "wav2vec2_create: tensor %d has no name/data", i);
         std::string k = weights[i].name;
@@ -260,10 +208,8 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
     }
     std::unique_ptr<mf_wav2vec2> h(new mf_wav2vec2());
     h->cfg = c; h->precision = precision; h->n = n_samples; h->cap = max_windows;
-    MF_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-    MF_HIP(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming));
-    { const char* e = getenv("MF_NO_GRAPH"); h->use_graph = !(e && atoi(e) != 0); }
+    int rc = h->graph.init(mf_no_graph_mode() == 0);   // eager for any non-zero MF_NO_GRAPH
+    if (rc) return rc;
     int L = n_samples;
     for (int i = 0; i < c.n_conv; ++i) {
         MF_REQUIRE(c.conv_kernel[i] >= 1 && c.conv_stride[i] >= 1 && c.conv_dim[i] % 8 == 0, "wav2vec2_create: bad conv layer %d", i);
@@ -277,8 +223,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
     h->fp_ln = h->seq(Cf, T); h->hid = h->seq(C, T, half);
     h->xa = h->seq(C, T); h->xb = h->seq(C, T); h->ln = h->seq(C, T); h->qkv = h->seq(3 * C, T); h->ao = h->seq(C, T); h->h1 = h->seq(c.ffn, T);
     if (!c.out_hidden) h->logit = h->seq(c.vocab, T);
-    int rc = h->alloc();
-    if (rc) return rc;
+    if ((rc = h->alloc())) return rc;
 
     auto ln_pair = [&](const std::string& p, int ch, float** g, float** b) -> int {
         const mf_tensor *gw = get(sd, p + ".weight", ch), *gb = get(sd, p + ".bias", ch);
@@ -386,7 +331,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         std::copy(b->data, b->data + c.vocab, bp.begin());
         h->head = h->new_plan();
         if ((rc = conv1d_plan(h->head, wp.data(), bp.data(), C, vp, 1, 1, 0, T, 0, 0, precision))) return rc;
-        if ((rc = mf_conv_bind(h->head, *h->xa))) return rc;
+        if ((rc = mf_conv_bind(h->head, *h->xb))) return rc;
         h->vocab_pad = vp;
     }
     *out = h.release();

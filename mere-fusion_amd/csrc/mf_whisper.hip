@@ -166,7 +166,7 @@ struct mf_whisper {
 
     ~mf_whisper() {
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) { if (b->hi) (void)hipFree(b->hi); if (b->lo) (void)hipFree(b->lo); }
+        for (auto& b : bufs) mf_actbuf_free(b.get());
         for (float* f : dev_f32) (void)hipFree(f);
         if (raw) (void)hipFree(raw);
         if (gmax) (void)hipFree(gmax);
@@ -178,13 +178,7 @@ struct mf_whisper {
         return b;
     }
     int alloc() {
-        for (auto& b : bufs) {
-            if (b->hi) { (void)hipFree(b->hi); b->hi = nullptr; }
-            if (b->lo) { (void)hipFree(b->lo); b->lo = nullptr; }
-            const size_t bytes = ((size_t)cap * b->per_batch() + 64) * sizeof(bf16_t);
-            MF_HIP(hipMalloc(&b->hi, bytes)); MF_HIP(hipMemset(b->hi, 0, bytes));
-            if (precision == MF_PREC_BF16X3) { MF_HIP(hipMalloc(&b->lo, bytes)); MF_HIP(hipMemset(b->lo, 0, bytes)); }
-        }
+        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap, precision); if (rc) return rc; }
         if (raw) (void)hipFree(raw);
         if (gmax) (void)hipFree(gmax);
         raw = nullptr; gmax = nullptr;
@@ -218,14 +212,7 @@ namespace {
 
 ActView W(ActBuf* b) { return ActView{b, 0, b->C}; }
 
-const mf_tensor* get(const std::map<std::string, const mf_tensor*>& sd, const std::string& k, int64_t numel) {
-    auto it = sd.find(k);
-    if (it == sd.end()) { mf_set_error("whisper: state dict has no tensor '%s'", k.c_str()); return nullptr; }
-    int64_t n = 1;
-    for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
-    if (n != numel) { mf_set_error("whisper: tensor '%s' has %lld elements, expected %lld", k.c_str(), (long long)n, (long long)numel); return nullptr; }
-    return it->second;
-}
+const mf_tensor* get(const MfStateDict& sd, const std::string& k, int64_t numel) { return mf_sd_find(sd, "whisper", k, numel); }
 
 int linear_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int T, int act, int residual, int precision) {
     mf_conv2d_desc d{};

@@ -139,3 +139,58 @@ def test_hip_wav2vec2_batch_composition_and_errors(lib_built):
     sd2 = {k: v for k, v in sd.items() if "layers.1.attention.k_proj.weight" not in k}
     with pytest.raises(RuntimeError, match="k_proj.weight"):
         _run_hip(cfg, sd2, wav[:1])
+
+
+_REPLAY_WAV = np.stack([W.make_speech_like_wav(8960, s) * (0.3 + 0.3 * s) for s in range(3)])
+_replay_want = {}
+
+
+def _replay_reference(stable, layers):
+    """(config, state dict, transformers' logits, its last hidden state) for the three windows, computed once per configuration"""
+    if (stable, layers) not in _replay_want:
+        from transformers import Wav2Vec2FeatureExtractor
+        cfg = dict(W.WAV2VEC2_SMALL, do_stable_layer_norm=stable, num_hidden_layers=layers)
+        sd = W.make_wav2vec2_state_dict(cfg, 0)
+        model = R.build(cfg, sd)
+        fe = Wav2Vec2FeatureExtractor(feature_size=1, sampling_rate=16000, padding_value=0.0, do_normalize=True, return_attention_mask=False)
+        iv = fe([w for w in _REPLAY_WAV], sampling_rate=16000, return_tensors="pt", padding=True).input_values
+        with torch.no_grad():
+            hid = model.wav2vec2(iv).last_hidden_state
+            _replay_want[stable, layers] = cfg, sd, model.lm_head(hid).numpy(), hid.numpy()
+    return _replay_want[stable, layers]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hidden", [False, True])
+@pytest.mark.parametrize("stable,layers", [(True, 2), (True, 3), (False, 2), (False, 3)])
+def test_hip_wav2vec2_eager_capture_and_replays_give_the_same_bits(lib_built, monkeypatch, stable, layers, hidden):
+    """One max_windows=3 handle: four forwards per window count on the same input -- eager, capture, replay, replay -- are bit-identical, and stay so when
+    the window counts interleave (one graph per count); `hidden` returns the encoder's last buffer itself instead of the logits.  Pre-LN and post-LN
+    encoders of even and odd depth: the LayerNorm order and the depth are what could move the last hidden state between the two ping-pong buffers.
+    A handle created under MF_NO_GRAPH=1 gives the same bits.  Against transformers: the bound of the tests above (same formats, fewer layers)."""
+    from mere_fusion_amd.ernerf.asr import HipWav2Vec2ForCTC
+    cfg, sd, want_logits, want_hidden = _replay_reference(stable, layers)
+    wav = torch.from_numpy(_REPLAY_WAV)
+
+    def run(m, S):
+        r = m(wav[:S])
+        return (r.last_hidden_state if hidden else r.logits).cpu()
+
+    monkeypatch.delenv("MF_NO_GRAPH", raising=False)                          # read per handle, by mf_wav2vec2_create (at the first forward)
+    m = HipWav2Vec2ForCTC(cfg, sd, max_windows=3, out_hidden=hidden)
+    first = {}
+    for S in (1, 3):
+        outs = [run(m, S) for _ in range(4)]
+        for k in (1, 2, 3):
+            assert torch.equal(outs[k], outs[0]), f"{S} windows: forward {k} differs from the eager one"
+        first[S] = outs[0]
+    for S in (3, 1, 3):
+        assert torch.equal(run(m, S), first[S]), f"{S} windows after another window count"
+    want = want_hidden if hidden else want_logits
+    err = np.abs(first[3].numpy() - want).max()
+    print(f"[wav2vec2 small, stable_ln {stable}, {layers} layers, hidden {hidden}] L-inf vs transformers {err:.3e} (max {np.abs(want).max():.2f})")
+    assert first[3].shape == want.shape and err <= 2e-3
+    monkeypatch.setenv("MF_NO_GRAPH", "1")
+    eager = HipWav2Vec2ForCTC(cfg, sd, max_windows=3, out_hidden=hidden)
+    for S in (1, 3, 1):
+        assert torch.equal(run(eager, S), first[S]), f"MF_NO_GRAPH=1, {S} windows"
