@@ -11,9 +11,9 @@ Serving many sessions from one generator handle (the Wav2Lip counterpart of muse
                                          context is shifted on the device, and ONE mf_melspec_windows launch turns all picked rows into [N * B, 1, 80, 16]
   LipBatcher                             ONE generator handle serving N sessions: every session's cached crops in one uint8 pool, a step is one
                                          forward_u8_rows over the active sessions' mirror-indexed pool rows (+ one AvatarFrames.paste per session)
-  LipSessionScheduler                    muse_driver.SessionScheduler over a LipBatcher (mel chunks in, frames out)
-  LipEndToEndScheduler                   muse_driver.EndToEndScheduler with the Wav2Lip audio stage: PCM chunks in, (res_frame, idx, audio_frames) tuples out
-                                         of each session's FrameRing; pacing, silence, back-pressure and delivery are the inherited code
+  LipSessionScheduler                    serving.SessionScheduler over a LipBatcher (mel chunks in, frames out)
+  LipEndToEndScheduler                   serving.PipelinedScheduler with the Wav2Lip audio stage: PCM chunks in, (res_frame, idx, audio_frames) tuples out
+                                         of each session's FrameRing; pacing, back-pressure, advance-once and delivery are serving.py's code
 """
 import time
 
@@ -21,14 +21,9 @@ import numpy as np
 import torch
 
 from . import ops
-from .muse_driver import EndToEndScheduler, SessionScheduler, pick_sessions  # noqa: F401  (pick_sessions: the policy both models' schedulers share)
+from .serving import (PipelinedScheduler, PooledBatcher, SessionScheduler, SessionWalk, all_silent, mirror_index, pick_sessions,  # noqa: F401  (re-exported)
+                      split_batch)
 from .wav2lip import audio
-
-
-def mirror_index(size, index):
-    """Ping-pong walk over the cached face crops (lipreal.py:65-72, basereal.py:133-139)."""
-    turn, res = divmod(index, size)
-    return res if turn % 2 == 0 else size - res - 1
 
 
 def mel_chunk_starts(n_frames, stride_left, stride_right, fps, mel_len, mel_step=16):
@@ -76,7 +71,7 @@ class LipASRFrontend:
         return chunks
 
 
-class LipSession:
+class LipSession(SessionWalk):
     """One talking-head session: cached uint8 face crops on the device + the generator.  With `avatar_frames`
     (mere_fusion_amd.paste.AvatarFrames built from frame_list_cycle / coord_list_cycle with lip_order=True) `step_pasted` also does
     process_frames' paste-back (lipreal.py:207-214) on the device."""
@@ -86,23 +81,12 @@ class LipSession:
         self.faces = faces_u8 if torch.is_tensor(faces_u8) else torch.from_numpy(np.asarray(faces_u8))
         self.faces = self.faces.to(next(model.parameters()).device)
         self.avatar_frames = avatar_frames
-        self.index = 0
-        self.length = self.faces.shape[0]
-        self.pool_offset = None                                     # first row of this session's crops in a LipBatcher's pool
-
-    def next_indices(self, n):
-        """the next n face indices of the ping-pong walk; the walk moves on (lipreal.py:102-105 for a silent batch, :112-114 for a spoken one)"""
-        idx = [mirror_index(self.length, self.index + i) for i in range(n)]
-        self.index += n
-        return idx
+        self.length = self.faces.shape[0]                           # (pool_offset: first row of this session's crops in a LipBatcher's pool)
 
     def step(self, mel_batch):
         """lipreal.py:109-137 for one non-silent batch: returns fp32 frames [B,96,96,3] (pred*255) and
         the face indices they belong to; process_frames truncates with astype(uint8) (lipreal.py:211)."""
-        B = mel_batch.shape[0]
-        n = self.faces.shape[0]
-        idx = [mirror_index(n, self.index + i) for i in range(B)]
-        self.index += B
+        idx = self.next_indices(mel_batch.shape[0])
         sel = self.faces[torch.tensor(idx, device=self.faces.device)]
         return self.model.forward_u8(mel_batch, sel), idx
 
@@ -189,7 +173,7 @@ class LipASRDeviceFrontend:
         return self.pool.mel(self.pool.rows([self.row]))
 
 
-class LipBatcher:
+class LipBatcher(PooledBatcher):
     """N Wav2Lip sessions through one generator handle per step (BASELINE.json configs[3]: per-GPU batching).  The argument list is MuseBatcher's, with the
     generator in the place of the UNet / VAE pair."""
 
@@ -200,14 +184,12 @@ class LipBatcher:
             raise RuntimeError("LipBatcher needs at least one session")
         # more sessions than one step holds: step(..., only=[...]) serves a subset (LipSessionScheduler)
         self.max_sessions_per_step = len(self.sessions) if max_sessions_per_step is None else int(max_sessions_per_step)
-        off = 0
         for k, s in enumerate(self.sessions):
             if s.faces.dtype != torch.uint8 or s.faces.dim() != 4 or tuple(s.faces.shape[1:]) != (96, 96, 3):
                 raise RuntimeError(f"session {k}: the cached crops must be uint8 [n,96,96,3], got {s.faces.dtype} {tuple(s.faces.shape)}")
             if s.avatar_frames is not None and s.avatar_frames.n != s.length:
                 raise RuntimeError(f"session {k}: one cached full frame per cached crop is required (frame_list_cycle / face_list_cycle)")
-            s.pool_offset = off
-            off += s.length
+        self._lay_out_pool()
         # every session's cached crops in one pool: the generator's input kernel reads a batch's faces from it by row
         self.pool = torch.cat([s.faces.to(self.device) for s in self.sessions], dim=0).contiguous()
         self.window_pool = None
@@ -230,64 +212,27 @@ class LipBatcher:
         top = self.max_sessions_per_step * B
         mel = torch.zeros((top, 1, 80, 16), dtype=torch.float32, device=self.device)
         self.model.forward_u8_rows(mel, self.pool, [0] * top)              # sizes the handle
-        for k in range(1, self.max_sessions_per_step + 1):
-            n = k * B
-            for it in range(3 if tune else 2):                             # eager (+ table lookup), [tune + eager], capture: tune drops the graph, so the
-                self.model.forward_u8_rows(mel[:n], self.pool, [0] * n)    # capture that follows records the measured configurations
-                if tune and it == 0:
-                    self.model.tune(n)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
+        self._prewarm_sizes(tune, lambda n: self.model.forward_u8_rows(mel[:n], self.pool, [0] * n), lambda n: self.model.tune(n))
 
-    @torch.no_grad()
     def step(self, mel_chunks, only=None):
-        """mel_chunks: one entry per session -- a device tensor [B, 1, 80, 16] (LipASRFrontend.run_step / melspec_windows) or None for an all-silent batch
-        (lipreal.py:102-105: the net is skipped, only the face indices advance).  Returns one (frames, indices) per session: frames = fp32 [B, 96, 96, 3]
-        (`pred * 255`, lipreal.py:126) or, with paste=True, the composed uint8 BGR full frames [B, H, W, 3] (lipreal.py:207-214); None for a silent session.
-        only: session numbers that take part in this step; every other session is left untouched (its index does not move, its entry is None)."""
+        """mel_chunks: per session a device tensor [B, 1, 80, 16] or None (silent); frames: fp32 [B, 96, 96, 3] (`pred * 255`, lipreal.py:126), pasted: uint8 BGR"""
+        return super().step(mel_chunks, only)
+
+    def _check_input(self, k, ch):
         B = self.batch_size
-        if len(mel_chunks) != len(self.sessions):
-            raise RuntimeError(f"{len(mel_chunks)} entries for {len(self.sessions)} sessions")
-        take = None if only is None else set(int(k) for k in only)
-        if take is not None and (min(take, default=0) < 0 or max(take, default=0) >= len(self.sessions)):
-            raise RuntimeError(f"only={sorted(take)}: session numbers run from 0 to {len(self.sessions) - 1}")
-        picked = [k for k in range(len(self.sessions)) if take is None or k in take]
-        active = [k for k in picked if mel_chunks[k] is not None]
-        if len(active) > self.max_sessions_per_step:
-            raise RuntimeError(f"{len(active)} active sessions in one step; a step holds {self.max_sessions_per_step} x {B} frames")
-        for k in active:                                                 # every input is checked BEFORE any session's face index moves
-            ch = mel_chunks[k]
-            if not torch.is_tensor(ch) or tuple(ch.shape) != (B, 1, 80, 16) or ch.device.type != self.device.type:
-                what = f"{tuple(ch.shape)} on {ch.device}" if torch.is_tensor(ch) else type(ch).__name__
-                raise RuntimeError(f"session {k}: expected a tensor [{B}, 1, 80, 16] of mel chunks on {self.device}, got {what}")
-            if self.paste and self.sessions[k].avatar_frames is None:
-                raise RuntimeError(f"session {k} has no AvatarFrames to paste into")
-        out = [None] * len(self.sessions)
-        rows = []
-        for k in picked:                                                 # lipreal.py:102-105, 134-137: silent or not, the walk advances by B
-            s = self.sessions[k]
-            idx = s.next_indices(B)
-            out[k] = (None, idx)
-            if mel_chunks[k] is not None:
-                rows.extend(s.pool_offset + i for i in idx)
-        if not active:
-            return out
-        mel = mel_chunks[active[0]] if len(active) == 1 else torch.cat([mel_chunks[k] for k in active], dim=0)
-        frames = self.model.forward_u8_rows(mel, self.pool, rows)      # lipreal.py:109-126, once for everybody
-        for j, k in enumerate(active):
-            fr, idx = frames[j * B:(j + 1) * B], out[k][1]
-            if self.paste:
-                fr = self.sessions[k].avatar_frames.paste(fr, idx)        # lipreal.py:207-214, one launch per session (sizes differ between avatars)
-            out[k] = (fr, idx)
-        return out
+        if not torch.is_tensor(ch) or tuple(ch.shape) != (B, 1, 80, 16) or ch.device.type != self.device.type:
+            what = f"{tuple(ch.shape)} on {ch.device}" if torch.is_tensor(ch) else type(ch).__name__
+            raise RuntimeError(f"session {k}: expected a tensor [{B}, 1, 80, 16] of mel chunks on {self.device}, got {what}")
+
+    def _forward(self, mels, rows):
+        return self.model.forward_u8_rows(self.cat_inputs(mels), self.pool, rows)      # lipreal.py:109-126, once for everybody
 
 
 class LipSessionScheduler(SessionScheduler):
-    """muse_driver.SessionScheduler over a LipBatcher: submit(k, mel_chunks [B, 1, 80, 16] or None, t_arrival), run_once(now), next_due() -- the same queues,
-    the same pick_sessions policy, one batch of B frames per session and step.  Period default: B x 40 ms (25 fps, lipreal.py / basereal's pacing)."""
+    """serving.SessionScheduler over a LipBatcher: submit(k, mel_chunks [B, 1, 80, 16] or None, t_arrival).  Period default: B x 40 ms (lipreal.py's 25 fps)."""
 
 
-class LipEndToEndScheduler(EndToEndScheduler):
+class LipEndToEndScheduler(PipelinedScheduler):
     """The whole per-GPU Wav2Lip session loop: what reaches a session's `process_frames` thread, from what its ASR thread saw.
 
       lipasr.py:14-37     submit(k, chunks, t): the 2B new 20 ms PCM chunks of session k.  When the batch is picked its samples are uploaded and its window slides
@@ -297,38 +242,32 @@ class LipEndToEndScheduler(EndToEndScheduler):
       lipreal.py:207-214  paste-back on the device (batcher built with paste=True)
       lipreal.py:104,136  each session's B (res_frame, idx, audio_frames[2i:2i+2]) tuples leave through ITS FrameRing
 
-    Everything else -- pick_sessions, try_reserve before anything irreversible, deferral episodes in `ring_full`, publish order, the waiter thread started by the
-    first step, close() / the context manager, single_stream -- is EndToEndScheduler's code, unchanged.  A window slides when its batch is
-    PICKED, not when it is submitted: the window is one device row per session, and a session may have several batches queued."""
+    Everything else (picking, reservation, deferral episodes in `ring_full`, publish order, the waiter thread, close(), single_stream) is PipelinedScheduler's code.
+    A window slides when its batch is PICKED, not when it is submitted, and once (`_advance`): it is one device row per session, and several batches may be queued."""
 
     def __init__(self, batcher, frontends=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
         fes = batcher.frontends() if frontends is None else list(frontends)
-        for k, fe in enumerate(fes):                                      # before anything (streams, the parent's state) is created
+        if len(fes) != len(batcher.sessions):                             # before anything (streams, the parent's state) is created
+            raise RuntimeError("one LipASRDeviceFrontend per session is required")
+        for k, fe in enumerate(fes):
             if not isinstance(fe, LipASRDeviceFrontend) or fe.pool is not fes[0].pool or fe.row != k or fe.batch_size != batcher.batch_size:
                 raise RuntimeError(f"frontend {k}: one LipASRDeviceFrontend per session, row k of one pool, is required (LipBatcher.frontends())")
-        super().__init__(batcher, fes, None, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, asr_stream=False, single_stream=single_stream)
-        self.windows = fes[0].pool
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream)
+        self.frontends, self.windows = fes, fes[0].pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):
-        """pcm_chunks: the batch's 2B 20 ms chunks -- bare arrays (all speech, type 0) or (chunk, type) pairs as `get_audio_frame` hands them out (baseasr.py:33-45;
-        type 1 = silence).  An all-silent batch skips the network (lipreal.py:96-105): its B (None, idx, audio_frames) tuples still reach the ring, and its samples
-        still enter the window (lipasr.py:17-21 does not look at the type)."""
-        t = self.clock() if t_arrival is None else t_arrival
-        pairs = [(c if isinstance(c, tuple) else (c, 0)) for c in pcm_chunks]
-        block = self.windows.host_block([c for c, _ in pairs])           # refuses a malformed batch here, before it is queued
-        silent = all(ty != 0 for _, ty in pairs)
-        self.queues[k].append((t, ({"block": block, "silent": silent, "pushed": False}, pairs)))
+        """pcm_chunks: the batch's 2B 20 ms chunks (serving.split_batch).  An all-silent batch skips the network (lipreal.py:96-105): its B (None, idx,
+        audio_frames) tuples still reach the ring, and its samples still enter the window (lipasr.py:17-21 does not look at the type)."""
+        chunks, pairs, types = split_batch(pcm_chunks, "LipEndToEndScheduler.submit")
+        block = self.windows.host_block(chunks)                          # refuses a malformed batch here, before it is queued
+        super().submit(k, {"block": block, "silent": all_silent(types)}, t_arrival, pairs)
 
-    def _audio_stage(self, ks, wins, dev):
+    def _advance(self, ks, batches):
+        self.windows.push(ks, [batches[k]["block"] for k in ks])         # lipasr.py:17-21 + :36: the picked sessions' windows slide, one upload
+
+    def _inputs(self, ks, batches, dev):
         chunks = [None] * len(self.queues)
-        # A batch whose step failed returns to the HEAD of its session's queue with "pushed" set: its window has slid already and must not slide again.  No other
-        # batch of that session can be picked in between (a session's batches are served in queue order), so the window it meets on the retry is still its own.
-        todo = sorted(k for k in ks if not wins[k]["pushed"])
-        if todo:
-            self.windows.push(todo, [wins[k]["block"] for k in todo])
-            for k in todo:
-                wins[k]["pushed"] = True
-        speaking = sorted(k for k in ks if not wins[k]["silent"])
+        speaking = sorted(k for k in ks if not batches[k]["silent"])
         if speaking:
             B = self.batcher.batch_size
             mel = self.windows.mel(self.windows.rows(speaking))          # every speaking session's B chunks in one launch

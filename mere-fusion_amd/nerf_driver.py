@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .ernerf import frontend
-from .lip_driver import mirror_index
+from .serving import mirror_index, refuse
 
 
 def loader_indices(size, index):
@@ -29,7 +29,7 @@ def loader_indices(size, index):
 
 
 def _refuse(msg):
-    raise RuntimeError("NerfSession: " + msg)
+    refuse("NerfSession", msg)
 
 
 class NerfSession:

@@ -7,9 +7,9 @@
                                             sessions come out of ONE mf_nerf_feat_windows launch
   NerfBatcher                               a list of NerfSessions (several may share one model object: one avatar resident once) stepped B frames each; the
                                             lip-smoothing EMA, which lives in the model, is kept per session
-  NerfSessionScheduler                      muse_driver.SessionScheduler over a NerfBatcher
-  NerfEndToEndScheduler                     muse_driver.EndToEndScheduler with the ER-NeRF audio stage: PCM chunks in, (frame, idx, audio_frames) tuples out of each
-                                            session's FrameRing; picking, back-pressure, publication and the waiter thread are the inherited code
+  NerfSessionScheduler                      serving.SessionScheduler over a NerfBatcher
+  NerfEndToEndScheduler                     serving.PipelinedScheduler with the ER-NeRF audio stage: PCM chunks in, (frame, idx, audio_frames) tuples out of each
+                                            session's FrameRing; picking, back-pressure, advance-once and publication are serving.py's code
 
 `ernerf.asr.NerfASRFrontend` stays the per-session restatement of the reference these are tested against."""
 import time
@@ -18,11 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .muse_driver import EndToEndScheduler, SessionScheduler
-
-
-def _refuse(who, msg):
-    raise RuntimeError(f"{who}: {msg}")
+from .serving import PipelinedScheduler, SessionScheduler, refuse as _refuse, split_batch, step_sessions
 
 
 class NerfFeaturePool:
@@ -257,14 +253,7 @@ class NerfBatcher:
         (frames uint8 [B, h, w, 3] RGB on the device, the B mirrored indices) per session, on the caller's stream.  only: session numbers that take part; every
         other session is left untouched (index, custom-video counters and EMA do not move; its entry is None and its input is not looked at)."""
         B = self.batch_size
-        if len(inputs) != len(self.sessions):
-            _refuse("NerfBatcher", f"{len(inputs)} entries for {len(self.sessions)} sessions")
-        take = None if only is None else set(int(k) for k in only)
-        if take is not None and (min(take, default=0) < 0 or max(take, default=0) >= len(self.sessions)):
-            _refuse("NerfBatcher", f"only={sorted(take)}: session numbers run from 0 to {len(self.sessions) - 1}")
-        picked = [k for k in range(len(self.sessions)) if take is None or k in take]
-        if len(picked) > self.max_sessions_per_step:
-            _refuse("NerfBatcher", f"{len(picked)} active sessions in one step; a step holds {self.max_sessions_per_step} x {B} frames")
+        picked, _ = step_sessions(self, inputs, only, skip_none=False)          # (ER-NeRF renders silent batches too)
         for k in picked:                                                 # every input is checked BEFORE any session moves
             self._check_input(k, inputs[k])
         out = [None] * len(self.sessions)
@@ -310,11 +299,10 @@ class NerfBatcher:
 
 
 class NerfSessionScheduler(SessionScheduler):
-    """muse_driver.SessionScheduler over a NerfBatcher: submit(k, (windows, audiotype pairs), t_arrival), run_once(now), next_due() -- the same queues, the same
-    pick_sessions policy, B frames per session and step.  Period default: B x 40 ms (25 fps)."""
+    """serving.SessionScheduler over a NerfBatcher: submit(k, (windows, audiotype pairs), t_arrival).  Period default: B x 40 ms (25 fps)."""
 
 
-class NerfEndToEndScheduler(EndToEndScheduler):
+class NerfEndToEndScheduler(PipelinedScheduler):
     """The whole per-GPU ER-NeRF session loop: what reaches a session's consumer, from what its ASR thread saw.
 
       nerfasr.py:105-124   submit(k, chunks, t): the 2B new 20 ms PCM chunks of session k.  When the batch is picked, NerfFeaturePool.step runs the run_steps and
@@ -322,44 +310,33 @@ class NerfEndToEndScheduler(EndToEndScheduler):
       nerfreal.py:70-127   NerfBatcher.step: B frames per picked session; a frame whose two chunks carry a custom audio type is the custom-video frame (:98)
       the ring             each session's B (frame, idx, audio_frames[2i:2i+2]) tuples leave through ITS FrameRing
 
-    ER-NeRF has no silent-batch skip: an all-silent batch renders like any other.  Everything else -- pick_sessions, try_reserve before anything irreversible,
-    deferral, publish order, the waiter thread, close() / the context manager, single_stream -- is EndToEndScheduler's code, unchanged.  A session's features
-    advance when its batch is PICKED, not when it is submitted, and once: a batch whose step failed returns to its queue with its windows attached."""
+    ER-NeRF has no silent-batch skip: an all-silent batch renders like any other.  Everything else (picking, reservation, deferral, publish order, the waiter
+    thread, close(), single_stream) is PipelinedScheduler's code.  A session's features advance when its batch is PICKED, not when it is submitted, and once."""
 
     def __init__(self, batcher, pool=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
         pool = batcher.pool if pool is None else pool
         if not isinstance(pool, NerfFeaturePool) or pool.n_sessions != len(batcher.sessions):     # before anything (streams, the parent's state) is created
             _refuse("NerfEndToEndScheduler", "a NerfFeaturePool with one row per session of the batcher is required")
-        fes = [NerfASRDeviceFrontend(pool, k) for k in range(pool.n_sessions)]
-        super().__init__(batcher, fes, None, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, asr_stream=False, single_stream=single_stream)
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream)
         self.pool = pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):
-        """pcm_chunks: the batch's 2B 20 ms chunks -- bare arrays (type 0) or (chunk, type) pairs as `get_audio_frame` hands them out (nerfasr.py:60-73).  Refused
-        here, before it is queued, when malformed."""
-        t = self.clock() if t_arrival is None else t_arrival
-        B = self.batcher.batch_size
+        """pcm_chunks: the batch's 2B 20 ms chunks, bare or (chunk, type) pairs (nerfasr.py:60-73; serving.split_batch).  Refused here when malformed."""
+        who, B = "NerfEndToEndScheduler.submit", self.batcher.batch_size
         if not 0 <= int(k) < len(self.queues):
-            _refuse("NerfEndToEndScheduler.submit", f"session {k}: numbers run from 0 to {len(self.queues) - 1}")
-        pairs = [(c if isinstance(c, tuple) else (c, 0)) for c in pcm_chunks]
-        if any(len(p) != 2 for p in pairs):
-            _refuse("NerfEndToEndScheduler.submit", "expected chunks or (chunk, type) pairs")
-        block = self.pool.host_block([c for c, _ in pairs], B)
+            _refuse(who, f"session {k}: numbers run from 0 to {len(self.queues) - 1}")
+        chunks, pairs, types = split_batch(pcm_chunks, who)
+        block = self.pool.host_block(chunks, B)
         try:
-            types = [(int(pairs[2 * i][1]), int(pairs[2 * i + 1][1])) for i in range(B)]      # nerfreal.py:81-88
+            types = [(int(types[2 * i]), int(types[2 * i + 1])) for i in range(B)]            # nerfreal.py:81-88
         except (TypeError, ValueError):
-            _refuse("NerfEndToEndScheduler.submit", "audio types must be integers")
-        self.queues[int(k)].append((t, ({"block": block, "types": types, "feats": None}, pairs)))
+            _refuse(who, "audio types must be integers")
+        super().submit(int(k), {"block": block, "types": types, "feats": None}, t_arrival, pairs)
 
-    def _audio_stage(self, ks, wins, dev):
-        inputs = [None] * len(self.queues)
-        # A batch whose step failed returns to the HEAD of its session's queue with its windows: the session's features have advanced already and must not advance
-        # again.  No other batch of that session can be picked in between (a session's batches are served in queue order).
-        todo = sorted(k for k in ks if wins[k]["feats"] is None)
-        if todo:
-            feats = self.pool.step(todo, [wins[k]["block"] for k in todo], self.batcher.batch_size)
-            for i, k in enumerate(todo):
-                wins[k]["feats"] = feats[i]
-        for k in ks:
-            inputs[k] = (wins[k]["feats"], wins[k]["types"])
-        return inputs
+    def _advance(self, ks, batches):
+        feats = self.pool.step(ks, [batches[k]["block"] for k in ks], self.batcher.batch_size)
+        for i, k in enumerate(ks):
+            batches[k]["feats"] = feats[i]                                # kept with the batch: a retried step renders from the same windows
+
+    def _inputs(self, ks, batches, dev):
+        return [(batches[k]["feats"], batches[k]["types"]) if k in batches else None for k in range(len(self.queues))]

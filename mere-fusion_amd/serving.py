@@ -1,0 +1,417 @@
+"""The model-agnostic part of serving many sessions from one GPU: what muse_driver, lip_driver and nerf_serving share.
+
+  mirror_index, SessionWalk, split_batch, all_silent   the ping-pong walk over an avatar's cached frames; a submitted batch of PCM chunks taken apart
+  step_sessions, PooledBatcher                         a batcher step's `only=` handling; the step and prewarm loop of a batcher with its frames in one pool
+  pick_sessions, SessionScheduler, PipelinedScheduler  the per-GPU serving loop, and the same with steps in flight and delivery through FrameRings: a model's
+                                                       scheduler adds `submit`, what advancing its audio state means (`_advance`) and the batcher's `_inputs`
+Nothing here knows a model; a batcher is anything with `sessions`, `batch_size`, `max_sessions_per_step`, `device` and `step(inputs, only=)`."""
+import queue
+import threading
+import time
+import weakref
+from collections import deque
+
+import torch
+
+
+def refuse(who, msg):
+    raise RuntimeError(f"{who}: {msg}")
+
+
+def mirror_index(size, index):
+    """`__mirror_index` (musereal.py:44-50, lipreal.py:65-72, basereal.py:133-139; provider.py:276-283): ping-pong walk over the cached frames."""
+    turn, res = divmod(index, size)
+    return res if turn % 2 == 0 else size - res - 1
+
+
+class SessionWalk:
+    """A session's place in the ping-pong walk over its `length` cached frames (the session sets it), and where those frames start in its batcher's pool."""
+    index, pool_offset = 0, None
+
+    def next_indices(self, n):
+        """the next n indices of the walk; the walk moves on (silent batch or spoken one: musereal.py:82-97, lipreal.py:102-105, 112-114)"""
+        idx = [mirror_index(self.length, self.index + i) for i in range(n)]
+        self.index += n
+        return idx
+
+
+def split_batch(pcm_chunks, who):
+    """One submitted batch -- bare arrays (all speech, type 0) or (chunk, type) pairs exactly as `get_audio_frame` hands them out (baseasr.py:33-45; type 1 =
+    silence, above 1 = a custom video's audio) -> (the chunks, the (chunk, type) pairs that travel with the frames, the types)."""
+    pairs = [(c if isinstance(c, tuple) else (c, 0)) for c in pcm_chunks]
+    if any(len(p) != 2 for p in pairs):
+        refuse(who, "expected chunks or (chunk, type) pairs")
+    return [c for c, _ in pairs], pairs, [ty for _, ty in pairs]
+
+
+def all_silent(types):
+    return all(ty != 0 for ty in types)                              # musereal.py:82-86, lipreal.py:96-105: no type-0 chunk, the networks are skipped
+
+
+def step_sessions(batcher, inputs, only, skip_none=True):
+    """The `only=` handling of a batcher step.  inputs: one entry per session; only: session numbers that take part (None: all).  Returns (picked, active):
+    the sessions whose state moves in this step, and those of them that reach the networks (skip_none: a None input is a silent batch and does not).  Refuses a
+    list of another length, a session number out of range and more active sessions than a step holds -- all before anything moves."""
+    who, n_sessions, capacity = type(batcher).__name__, len(batcher.sessions), batcher.max_sessions_per_step
+    if len(inputs) != n_sessions:
+        refuse(who, f"{len(inputs)} entries for {n_sessions} sessions")
+    take = None if only is None else set(int(k) for k in only)
+    if take is not None and (min(take, default=0) < 0 or max(take, default=0) >= n_sessions):
+        refuse(who, f"only={sorted(take)}: session numbers run from 0 to {n_sessions - 1}")
+    picked = [k for k in range(n_sessions) if take is None or k in take]
+    active = [k for k in picked if inputs[k] is not None] if skip_none else picked
+    if len(active) > capacity:
+        refuse(who, f"{len(active)} active sessions in one step; a step holds {capacity} x {batcher.batch_size} frames")
+    return picked, active
+
+
+class PooledBatcher:
+    """N sessions (SessionWalks) through one set of handles per step, every session's cached frames in one pool.  A model's batcher says: _check_input(k, x), which
+    refuses session k's input if the forward cannot take it; _forward(xs, rows): the active sessions' inputs (`cat_inputs` joins them) and pool rows -> frames."""
+
+    def _lay_out_pool(self):
+        for k, s in enumerate(self.sessions):                            # every session's first row in the pool its frames are concatenated into
+            s.pool_offset = sum(t.length for t in self.sessions[:k])
+
+    @staticmethod
+    def cat_inputs(xs):
+        return xs[0] if len(xs) == 1 else torch.cat(xs, dim=0)
+
+    def _prewarm_sizes(self, tune, forward, measure):
+        for k in range(1, self.max_sessions_per_step + 1):
+            n = k * self.batch_size
+            for it in range(3 if tune else 2):                             # eager (+ table lookup), [tune + eager], capture: tune drops the graph, so the
+                forward(n)                                                 # capture that follows records the measured configurations
+                if tune and it == 0:
+                    measure(n)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+    @torch.no_grad()
+    def step(self, inputs, only=None):
+        """inputs: one entry per session -- what the forward takes for B frames, or None for an all-silent batch (musereal.py:82-86, lipreal.py:102-105: the net
+        is skipped, only the frame indices advance).  Returns one (frames, indices) per session: frames = B frames on the device -- with paste=True the composed
+        full frames [B, H, W, 3] (musereal.py:238-247, lipreal.py:207-214) -- or None for a silent session.  only: session numbers that take part; every other
+        session is left untouched (its index does not move, its entry is None, its input is not looked at): sessions on their own clocks do not all have a batch."""
+        B = self.batch_size
+        picked, active = step_sessions(self, inputs, only)
+        for k in active:                                                 # every input is checked BEFORE any session's frame index moves
+            self._check_input(k, inputs[k])
+            if self.paste and self.sessions[k].avatar_frames is None:
+                raise RuntimeError(f"session {k} has no AvatarFrames to paste into")
+        out, rows = [None] * len(self.sessions), []
+        for k in picked:                                                 # musereal.py:82-97, lipreal.py:102-105, 134-137: silent or not, the walk advances by B
+            s = self.sessions[k]
+            idx = s.next_indices(B)
+            out[k] = (None, idx)
+            if inputs[k] is not None:
+                rows.extend(s.pool_offset + i for i in idx)
+        if not active:
+            return out
+        frames = self._forward([inputs[k] for k in active], rows)        # once for everybody
+        for j, k in enumerate(active):
+            fr, idx = frames[j * B:(j + 1) * B], out[k][1]
+            if self.paste:
+                fr = self.sessions[k].avatar_frames.paste(fr, idx)        # one launch per session (sizes differ between avatars)
+            out[k] = (fr, idx)
+        return out
+
+
+def pick_sessions(pending, now, capacity, hold):
+    """Which sessions share the next step.  pending: {session number: arrival time of its OLDEST queued batch}.  Oldest first (ties: lower
+    session number); a step goes out as soon as `capacity` sessions wait, or once the oldest batch has waited `hold` seconds -- a partly
+    filled step costs almost what a full one does (the UNet is latency-bound at 8 frames), so a short hold buys throughput and
+    its cost is bounded by `hold`.  Returns [] while it is better to wait.  Pure host logic (tests/test_muse_driver.py runs it on the CPU)."""
+    if not pending or capacity < 1:
+        return []
+    order = sorted(pending, key=lambda k: (pending[k], k))
+    if len(order) >= capacity or now - pending[order[0]] >= hold:
+        return order[:capacity]
+    return []
+
+
+class SessionScheduler:
+    """Serving loop of one GPU over a batcher, for sessions that arrive on their own clocks (one batch of B frames per B * 40 ms of audio each,
+    musereal.py:53-58 / basereal's 25 fps pacing): queues every session's batches, picks which sessions share the next step (oldest first, up to the handle's
+    capacity; a short hold lets a step fill), and stamps every batch's arrival -> frames-ready latency.  bench.py's `paced_sessions` leg measures
+    BASELINE.json's "max concurrent >= 25 fps sessions" with it (p99 batch latency <= B * 40 ms) instead of dividing a free-running rate by 25.
+
+    submit(k, inputs, t_arrival)   queue one batch of session k (inputs: what the batcher's step takes for one session, or None = silent batch)
+    run_once(now)                  if pick_sessions says so, run ONE batcher step for the picked sessions, wait for its frames and
+                                   return [(k, frames, indices, latency_s)]; [] when nothing is due
+    next_due()                     the time at which run_once would act on what is queued now (None: nothing queued)
+    A session's batches are served in arrival order, one per step (its frame indices are consecutive: musereal.py:92-97)."""
+
+    def __init__(self, batcher, period_s=None, hold_s=None, clock=time.perf_counter, sync=None):
+        self.batcher = batcher
+        self.capacity = batcher.max_sessions_per_step
+        self.period = batcher.batch_size * 0.040 if period_s is None else float(period_s)          # B frames at 25 fps
+        self.hold = self.period / 4 if hold_s is None else float(hold_s)
+        self.clock = clock
+        self.sync = sync if sync is not None else (lambda: torch.cuda.synchronize(batcher.device))
+        self.queues = [deque() for _ in batcher.sessions]
+        self.steps = 0
+        self.sessions_served = 0
+        self.busy_s = 0.0
+
+    def submit(self, k, inputs, t_arrival=None):
+        self.queues[k].append((self.clock() if t_arrival is None else t_arrival, inputs))
+
+    def pending(self):
+        return {k: q[0][0] for k, q in enumerate(self.queues) if q}
+
+    def backlog(self):
+        return max((len(q) for q in self.queues), default=0)
+
+    def next_due(self):
+        p = self.pending()
+        if not p:
+            return None
+        t = sorted(p.values())
+        return t[self.capacity - 1] if len(t) >= self.capacity else t[0] + self.hold
+
+    def run_once(self, now=None):
+        now = self.clock() if now is None else now
+        ks = pick_sessions(self.pending(), now, self.capacity, self.hold)
+        if not ks:
+            return []
+        chunks = [None] * len(self.queues)
+        arrival = {}
+        for k in ks:
+            arrival[k], chunks[k] = self.queues[k].popleft()
+        t0 = self.clock()
+        out = self.batcher.step(chunks, only=ks)
+        self.sync()
+        t1 = self.clock()
+        self.steps += 1
+        self.sessions_served += len(ks)
+        self.busy_s += t1 - t0
+        return [(k, out[k][0], out[k][1], t1 - arrival[k]) for k in ks]
+
+
+class PipelinedScheduler(SessionScheduler):
+    """The whole per-GPU session loop in one place, for any model: what reaches a session's `process_frames` thread, from what its ASR
+    thread saw.  A step is: pick -> reserve ring places -> the model's audio stage -> batcher.step -> each session's frames leave through ITS FrameRing as
+    (res_frame, idx, audio_frames) tuples (musereal.py:116,153; lipreal.py:104,136): the D2H runs on a copy stream behind the step (the next step's kernels do
+    not wait for it) and the descriptors are published when its event is done.  run_once(now) -> finished batches [(k, frames_or_None, indices, latency_s)]:
+    latency = arrival -> descriptors published (rings given) or frames complete in HBM (rings=None).  With rings=None or single_stream=True no stream is created."""
+
+    def __init__(self, batcher, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
+        super().__init__(batcher, period_s=period_s, hold_s=hold_s, clock=clock)
+        self.rings = rings
+        self.depth = max(int(depth), 1)                              # steps in flight: the one computing + the one whose frames are being copied
+        # single_stream: a model's audio stage, the step and the D2H of its frames all on the caller's stream -- no cross-stream event wait anywhere (with handles
+        # created under MF_NO_GRAPH=2 the whole rank is one launch chain: no runtime thread spins, see mf_musetalk.hip); costs the copy / Whisper overlap
+        self.single_stream = bool(single_stream)
+        self.copy_stream = torch.cuda.Stream(device=batcher.device) if rings is not None and not self.single_stream else None
+        self.inflight = deque()
+        # The serving loop SLEEPS between steps (polling run_once at 2 - 5 kHz was part of the 1.3 - 1.9 host cores a rank cost at
+        # capacity): every step's event goes to one waiter thread that does nothing but hipEventQuery it every 0.5 ms and then sets `_wake`; the loop sleeps
+        # in idle_wait() until then or until the next arrival is due.  (Not hipEventSynchronize: on ROCm 7.2 it spins a full core for as long as the GPU is
+        # busy, with or without the blocking-sync event flag, and hipDeviceScheduleBlockingSync hangs on this driver: tools/host_wait_probe.py.)
+        self._wake = threading.Event()
+        self._evq = queue.SimpleQueue()
+        self._waiter = None                                          # started by the first step: a scheduler that never steps owns no thread
+        self.waiter_errors = []                                      # exceptions hipEventQuery raised in the waiter (a device error is not a completion)
+        self.ring_full = 0                                           # deferral EPISODES (a session found its ring full), not polls
+        self._deferred = {}                                          # session -> time at which it is offered again even if its ring still looks full
+        self._busy_until = 0.0
+
+    @staticmethod
+    def _wait_loop(evq, wake, errors):
+        """The waiter holds the queue, the wake flag and the error list -- NOT the scheduler: an abandoned scheduler (no close()) is collected with its batcher,
+        rings and GPU handles, and its finaliser below stops this thread."""
+        while True:
+            ev = evq.get()
+            if ev is None:
+                return
+            try:
+                while not ev.query():
+                    time.sleep(5e-4)
+            except Exception as e:                                   # recorded, then the loop is woken: _retire's own query raises the same error to the caller
+                errors.append(e)
+            wake.set()
+
+    def _start_waiter(self):
+        if self._waiter is None:
+            self._waiter = threading.Thread(target=PipelinedScheduler._wait_loop, args=(self._evq, self._wake, self.waiter_errors), daemon=True)
+            self._waiter.start()
+            weakref.finalize(self, self._evq.put, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def idle_wait(self, timeout):
+        """Sleeps until a step in flight completes or `timeout` seconds have passed, whichever is first (nothing in flight: a plain sleep).  What a serving
+        loop calls between run_once()s instead of polling."""
+        if timeout is None or timeout <= 0:
+            return
+        if self.inflight:
+            self._wake.wait(timeout)
+            self._wake.clear()
+        else:
+            time.sleep(timeout)
+
+    def close(self):
+        """stops the waiter thread (after drain(); `with ...Scheduler(...) as sch:` calls it)"""
+        if self._waiter is not None:
+            self._evq.put(None)
+            self._waiter.join(timeout=2.0)
+            self._waiter = None
+
+    def submit(self, k, payload, t_arrival=None, pairs=()):
+        """(a model's submit takes PCM chunks and ends here.)  A queue entry is (arrival, (payload, pairs)); a third item marks a batch that has advanced"""
+        self.queues[k].append((self.clock() if t_arrival is None else t_arrival, (payload, list(pairs))))
+
+    def _retire(self, block=False):
+        done = []
+        while self.inflight:
+            item = self.inflight[0]
+            if block:
+                item["event"].synchronize()
+            elif not item["event"].query():
+                break
+            self.inflight.popleft()
+            t1 = self.clock()
+            for k in item["ks"]:
+                fr, idx = item["out"][k]
+                tok = item["tokens"].get(k)
+                if tok is not None:
+                    # speech: the B frames' descriptors; a silent batch or a session whose context is still filling: B (None, idx, audio_frames[2i:2i+2])
+                    # tuples as the reference puts them (musereal.py:82-86, lipreal.py:104) -- ONE message either way, on slots reserved before the step
+                    # started, so nothing here can block the scheduler thread
+                    self.rings[k].commit_batch(tok, item["audio"][k])
+                    t1 = self.clock()
+                done.append((k, fr, idx, t1 - item["arrival"][k]))
+            self.busy_s += max(t1 - max(item["t0"], self._busy_until), 0.0)      # union of the steps' [launch, done] intervals
+            self._busy_until = max(self._busy_until, t1)
+        return done
+
+    def pending(self):
+        """Sessions whose oldest batch can be picked now.  A session deferred because its ring was full is left out until the ring reports B free slots or a
+        back-off of a quarter period has passed (it otherwise sits at the head of the order with an arrival time in the past, next_due() lies in the
+        past, the serving loop spins a host core on run_once, and its age makes every other session's step launch partly filled)."""
+        p = super().pending()
+        if self._deferred:
+            now, B = self.clock(), self.batcher.batch_size
+            for k in list(self._deferred):
+                if k not in p:
+                    del self._deferred[k]
+                elif self.rings[k].free_slots() >= B or now >= self._deferred[k]:
+                    del self._deferred[k]                            # (a new episode is counted if it is deferred again)
+                else:
+                    del p[k]
+        return p
+
+    def next_due(self):
+        """when run_once would next act on what is QUEUED (None: nothing queued).  Steps in flight do not enter: idle_wait() wakes the loop when one completes."""
+        t = super().next_due()
+        if self._deferred:
+            t_def = min(self._deferred.values())
+            t = t_def if t is None else min(t, t_def)
+        return t
+
+    def run_once(self, now=None):
+        now = self.clock() if now is None else now
+        done = self._retire()
+        if len(self.inflight) >= self.depth:
+            return done
+        ks = pick_sessions(self.pending(), now, self.capacity, self.hold)
+        if not ks:
+            return done
+        dev = self.batcher.device
+        # Ring slots for every picked session are taken BEFORE anything irreversible happens (queue entries popped, frame indices and ASR state advanced): a
+        # session whose consumer is behind is DEFERRED -- its batch stays at the head of its queue and is picked again later -- and the other sessions go ahead;
+        # the reference's loop likewise back-pressures only the one session's queue.
+        reserved = {}
+        if self.rings is not None:
+            B = self.batcher.batch_size
+            pend = self.pending()
+            ok = []
+            try:
+                for k in sorted(pend, key=lambda k_: (pend[k_], k_)):     # oldest first; a waiting session takes the place of one that has to be deferred
+                    if len(ok) == len(ks):
+                        break
+                    sl = self.rings[k].try_reserve(B)                     # (silent batches too: their B (None, idx, audio) tuples take B of the ring's places)
+                    if sl is None:
+                        self.ring_full += 1
+                        self._deferred[k] = now + self.period / 4
+                        continue
+                    reserved[k] = sl
+                    ok.append(k)
+            except BaseException:
+                for k in list(reserved):                                  # a ring that raised (closed, torn down) must not leave the others' places open
+                    self.rings[k].unreserve(reserved[k])
+                raise
+            ks = ok
+            if not ks:
+                return done
+        # Everything from here to the last begin_batch sits in ONE try: the rings publish in begin order, so a reservation left open by an exception anywhere
+        # on the way (the queue pop, the H2D copy, the audio stage, the step, a begin_batch) would wedge its ring for good -- every later batch queued behind
+        # an entry that never completes.  On any exception the reservations go back and the popped batches return to the HEAD of their queues.
+        arrival, audio, wins, tokens, popped, advanced = {}, {}, {}, {}, [], set()
+        try:
+            for k in ks:
+                item = self.queues[k].popleft()
+                popped.append((k, item))
+                arrival[k], (wins[k], audio[k]) = item[:2]
+                advanced.update([k] * (len(item) > 2))
+            t0 = self.clock()
+            chunks = self._audio_stage(ks, wins, dev, advanced)
+            out = self.batcher.step(chunks, only=ks)
+            ev = torch.cuda.Event()
+            if self.rings is not None:
+                cur = torch.cuda.current_stream(dev)
+                if self.copy_stream is not None:
+                    self.copy_stream.wait_stream(cur)
+                for k in ks:
+                    fr, idx = out[k]
+                    tokens[k] = self.rings[k].begin_batch(fr, idx, stream=self.copy_stream, reserved=reserved.pop(k))   # (fr None: B silent frames)
+                    if fr is not None and self.copy_stream is not None:
+                        fr.record_stream(self.copy_stream)
+                ev.record(self.copy_stream if self.copy_stream is not None else cur)
+        except BaseException:
+            # nothing of this step is published: tokens already begun and reservations not yet used go back (the rings publish in begin order whatever order
+            # this happens in)
+            for k in list(tokens):
+                self.rings[k].abort_batch(tokens[k])
+            for k in list(reserved):
+                self.rings[k].unreserve(reserved[k])
+            for k, item in reversed(popped):                       # the batches of this step are not lost: they are picked again
+                self.queues[k].appendleft(item[:2] + (True,) if k in advanced else item)
+            raise
+        if self.rings is None:
+            ev.record(torch.cuda.current_stream(dev))
+        self.inflight.append({"ks": ks, "out": out, "tokens": tokens, "audio": audio, "arrival": arrival, "event": ev, "t0": t0})
+        self._start_waiter()
+        self._evq.put(ev)
+        self.steps += 1
+        self.sessions_served += len(ks)
+        return done
+
+    def _audio_stage(self, ks, wins, dev, advanced=None):
+        """The audio front end of one step: wins[k] is the payload submit() queued for session k.  Returns the batcher's per-session input list.
+        ADVANCE ONCE: a batch whose step failed returns to the HEAD of its session's queue marked as advanced (`advanced`: those sessions) -- its session's audio
+        state (Wav2Lip's window, ER-NeRF's features) has moved on for it already and must not move again.  No other batch of that session can be picked in between
+        (a session's batches are served in queue order), so the state it meets on the retry is still its own.  (MuseTalk's window slides at submit(), on arrival.)"""
+        advanced = set() if advanced is None else advanced
+        todo = sorted(k for k in ks if k not in advanced)
+        if todo:
+            self._advance(todo, wins)
+            advanced.update(todo)
+        return self._inputs(ks, wins, dev)
+
+    def _advance(self, ks, payloads):
+        """move the audio state of sessions ks (sorted) on by their batches; once per batch, when it is first picked.  What it computes is kept in the payload"""
+
+    def _inputs(self, ks, payloads, dev):
+        """the batcher's input list (None for every session that is silent or not picked); runs on every try of a batch.  Here: the payload is the input"""
+        return [payloads.get(k) for k in range(len(self.queues))]
+
+    def drain(self):
+        """Waits for everything in flight (end of a run)."""
+        return self._retire(block=True)

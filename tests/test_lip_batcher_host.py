@@ -4,7 +4,6 @@ C ABI of the two entry points underneath (header, exports, ctypes table, argumen
 import ctypes as C
 import os
 import re
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 
 from conftest import ROOT
 from mere_fusion_amd import lip_driver as D
+from serving_fakes import FakeBatcher, FakeRing, fake_cuda_events
 
 B = 2
 COUNTS = (3, 4, 5)
@@ -170,21 +170,6 @@ def test_window_pool_slides_like_the_host_frontend():
         pool.push([0, 0], [pool.host_block([np.zeros(320, np.float32)] * (2 * B))] * 2)
 
 
-class FakeBatcher:
-    def __init__(self, n, cap, device="cpu"):
-        self.sessions, self.max_sessions_per_step, self.batch_size, self.device = [None] * n, cap, B, torch.device(device)
-        self.steps, self.index = [], [0] * n
-
-    def step(self, chunks, only=None):
-        self.steps.append((sorted(only), [None if c is None else "mel" for c in chunks]))
-        out = [None] * len(self.sessions)
-        for k in only:
-            idx = [self.index[k], self.index[k] + 1]
-            self.index[k] += B
-            out[k] = (None if chunks[k] is None else torch.full((B, 4, 4, 3), float(k)), idx)
-        return out
-
-
 def test_session_scheduler_serves_in_arrival_order_on_an_injected_clock():
     now = [0.0]
     bat = FakeBatcher(3, 2)
@@ -207,44 +192,11 @@ def test_session_scheduler_serves_in_arrival_order_on_an_injected_clock():
     assert sch.steps == 2 and sch.sessions_served == 4 and sch.backlog() == 0 and sch.next_due() is None
 
 
-class FakeRing:
-    def __init__(self, places):
-        self.places, self.taken, self.msgs = places, 0, []
-
-    def free_slots(self):
-        return self.places - self.taken
-
-    def try_reserve(self, n):
-        if self.free_slots() < n:
-            return None
-        self.taken += n
-        return {"n": n}
-
-    def unreserve(self, tok):
-        self.taken -= tok["n"]
-
-    def begin_batch(self, fr, idx, stream=None, reserved=None):
-        reserved.update(fr=fr, idx=idx)
-        return reserved
-
-    def abort_batch(self, tok):
-        self.taken -= tok["n"]
-
-    def commit_batch(self, tok, audio):
-        self.msgs += [(None if tok["fr"] is None else tok["fr"][i], tok["idx"][i], audio[2 * i:2 * i + 2]) for i in range(len(tok["idx"]))]
-
-    def get(self):
-        self.taken -= 1
-        return self.msgs.pop(0)
-
-
 def test_end_to_end_scheduler_defers_a_full_ring_and_offers_it_again(monkeypatch):
     """Host logic of LipEndToEndScheduler with fake rings and a fake batcher: a session whose ring reports no room is deferred (one episode in `ring_full`) while
     the other is served, its window does NOT slide for the deferred batch, and it is served -- in order -- once its consumer has read.  Silent batches deliver B
     (None, idx, audio) tuples; the waiter thread exists only after the first step."""
-    ev = SimpleNamespace(record=lambda *_: None, query=lambda: True, synchronize=lambda: None)
-    monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: ev)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+    fake_cuda_events(monkeypatch)
     now = [0.0]
     bat = FakeBatcher(2, 2)
     pool = D.LipWindowPool(2, B, stride_left=1, stride_right=1, device="cpu")
@@ -289,9 +241,7 @@ def test_end_to_end_scheduler_defers_a_full_ring_and_offers_it_again(monkeypatch
 
 
 def test_a_failed_step_does_not_slide_the_window_twice(monkeypatch):
-    ev = SimpleNamespace(record=lambda *_: None, query=lambda: True, synchronize=lambda: None)
-    monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: ev)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+    fake_cuda_events(monkeypatch)
     bat = FakeBatcher(1, 1)
     pool = D.LipWindowPool(1, B, stride_left=1, stride_right=1, device="cpu")
     pool.mel = lambda wav: torch.zeros(len(wav) * B, 1, 80, 16)

@@ -6,6 +6,7 @@ import torch
 from mere_fusion_amd import muse_driver as D
 from mere_fusion_amd import weights as W
 from oracle import glue_ref
+from serving_fakes import FakeBatcher, FakeRing, fake_cuda_events
 
 
 def test_chunk_rows_match_survey_8c():
@@ -364,23 +365,12 @@ def test_end_to_end_scheduler_leaves_a_deferred_session_out_until_its_ring_has_r
     """ADVICE r04 (host logic only, no device): a session deferred because its ring was full must not sit at the head of the order with an arrival time in the
     past -- next_due() would lie in the past and the serving loop would spin on run_once -- it is offered again when its ring reports B free slots or after a
     quarter period."""
-    from collections import deque
-    from types import SimpleNamespace
-
-    class Ring:
-        def __init__(self, free):
-            self.free = free
-
-        def free_slots(self):
-            return self.free
-
     now = [1.0]
-    sch = D.EndToEndScheduler.__new__(D.EndToEndScheduler)          # (the constructor needs a device for its copy stream; the policy under test does not)
-    sch.queues = [deque([(0.2, ("win", []))]), deque([(0.9, ("win", []))])]
-    sch.capacity, sch.hold, sch.period, sch.clock = 2, 0.08, 0.32, (lambda: now[0])
-    sch.batcher = SimpleNamespace(batch_size=8)
-    sch.rings = [Ring(0), Ring(16)]
-    sch.inflight, sch._deferred = deque(), {0: 1.05}                # session 0 was deferred at t = 0.97 (+ period / 4)
+    sch = D.EndToEndScheduler(FakeBatcher(2, 2, batch_size=8), [None, None], None, rings=[FakeRing(0), FakeRing(16)], clock=lambda: now[0], single_stream=True)
+    assert (sch.capacity, sch.hold, sch.period) == (2, pytest.approx(0.08), pytest.approx(0.32))
+    D.PipelinedScheduler.submit(sch, 0, "win", 0.2)
+    D.PipelinedScheduler.submit(sch, 1, "win", 0.9)
+    sch._deferred = {0: 1.05}                                       # session 0 was deferred at t = 0.97 (+ period / 4)
     assert sch.pending() == {1: 0.9}                                # the stalled session does not age the order ...
     assert abs(sch.next_due() - 0.98) < 1e-9 or sch.next_due() == 0.98   # ... session 1's own hold decides (0.9 + 0.08), not a time in the past
     sch.queues[1].clear()
@@ -388,7 +378,7 @@ def test_end_to_end_scheduler_leaves_a_deferred_session_out_until_its_ring_has_r
     now[0] = 1.06
     assert sch.pending() == {0: 0.2} and 0 not in sch._deferred     # back-off over: offered again (and counted as a new episode if still full)
     sch._deferred = {0: 9.0}
-    sch.rings[0].free = 8
+    sch.rings[0].places = 8
     assert sch.pending() == {0: 0.2}                                # ... or as soon as the consumer has freed a batch's worth of slots
 
 
@@ -444,49 +434,17 @@ def test_hip_end_to_end_scheduler_silent_batches_with_a_stalled_consumer_never_b
         r.close()
 
 
-def test_end_to_end_scheduler_returns_reservations_and_batches_when_a_step_fails():
+def test_end_to_end_scheduler_returns_reservations_and_batches_when_a_step_fails(monkeypatch):
     """ADVICE r05 (host logic only): the rings publish in begin order, so a reservation leaked by an exception between try_reserve and begin_batch -- the queue
     pop, the Whisper stage, the step -- would wedge that ring for good.  Whatever raises, every reservation goes back and the popped batches return to the head
     of their queues."""
-    from collections import deque
-    from types import SimpleNamespace
-    import queue as _q
-    import threading
-
-    class Ring:
-        def __init__(self):
-            self.open, self.begun, self.aborted = [], [], []
-
-        def free_slots(self):
-            return 16
-
-        def try_reserve(self, n):
-            tok = object()
-            self.open.append(tok)
-            return tok
-
-        def unreserve(self, tok):
-            self.open.remove(tok)
-
-        def begin_batch(self, fr, idx, stream=None, reserved=None):
-            self.open.remove(reserved)
-            self.begun.append(reserved)
-            return reserved
-
-        def abort_batch(self, tok):
-            self.aborted.append(tok)
-
     def make(step, fixed_chunks):
-        sch = D.EndToEndScheduler.__new__(D.EndToEndScheduler)
-        sch.queues = [deque([(0.1, ("win0", ["a0"])), (0.5, ("win0b", ["a0b"]))]), deque([(0.2, ("win1", ["a1"]))])]
-        sch.capacity, sch.hold, sch.period, sch.clock, sch.depth = 2, 0.0, 0.32, (lambda: 1.0), 2
-        sch.batcher = SimpleNamespace(batch_size=8, device="cpu", step=step)
-        sch.rings = [Ring(), Ring()]
-        sch.inflight, sch._deferred, sch.ring_full, sch.copy_stream, sch.asr_stream = deque(), {}, 0, None, None
-        sch.fixed_chunks, sch.frontends, sch.audio_processor = fixed_chunks, [None, None], None
-        sch._evq, sch._wake, sch._waiter, sch.waiter_errors = _q.SimpleQueue(), threading.Event(), None, []
-        sch.steps = sch.sessions_served = 0
-        sch.busy_s, sch._busy_until = 0.0, 0.0
+        bat = FakeBatcher(2, 2, batch_size=8)
+        bat.step = step
+        sch = D.EndToEndScheduler(bat, [None, None], None, rings=[FakeRing(16), FakeRing(16)], period_s=0.32, hold_s=0.0, clock=lambda: 1.0,
+                                  fixed_chunks=fixed_chunks, single_stream=True)
+        for k, t, win, audio in ((0, 0.1, "win0", ["a0"]), (0, 0.5, "win0b", ["a0b"]), (1, 0.2, "win1", ["a1"])):
+            D.PipelinedScheduler.submit(sch, k, win, t, audio)
         return sch
 
     def boom(chunks, only=None):
@@ -511,14 +469,8 @@ def test_end_to_end_scheduler_returns_reservations_and_batches_when_a_step_fails
         sch.rings[1].unreserve(reserved)                                             # (FrameRing.begin_batch returns its reservation itself when it fails)
         raise RuntimeError("ring torn down")
     sch.rings[1].begin_batch = bad_begin
-    import torch
-    real_event, real_cur = torch.cuda.Event, torch.cuda.current_stream
-    torch.cuda.Event = lambda *a, **k: SimpleNamespace(record=lambda *_: None, query=lambda: True, synchronize=lambda: None)
-    torch.cuda.current_stream = lambda *a, **k: None
-    try:
-        with pytest.raises(RuntimeError, match="ring torn down"):
-            sch.run_once(now=1.0)
-    finally:
-        torch.cuda.Event, torch.cuda.current_stream = real_event, real_cur
+    fake_cuda_events(monkeypatch)
+    with pytest.raises(RuntimeError, match="ring torn down"):
+        sch.run_once(now=1.0)
     assert sch.rings[0].aborted == sch.rings[0].begun and len(sch.rings[0].aborted) == 1 and not sch.rings[1].open
     assert sch._waiter is None                                                       # no step succeeded: no waiter thread was ever started

@@ -13,6 +13,7 @@ import torch
 
 from conftest import ROOT
 import nerf_serving_util as U
+from serving_fakes import FakeRing, fake_cuda_events
 
 B = 4
 
@@ -242,42 +243,9 @@ def test_batcher_refusals_come_before_any_state_moves():
 
 
 # ---- the schedulers ------------------------------------------------------------------------------------------------------------------------
-class FakeRing:
-    def __init__(self, places):
-        self.places, self.taken, self.msgs = places, 0, []
-
-    def free_slots(self):
-        return self.places - self.taken
-
-    def try_reserve(self, n):
-        if self.free_slots() < n:
-            return None
-        self.taken += n
-        return {"n": n}
-
-    def unreserve(self, tok):
-        self.taken -= tok["n"]
-
-    def begin_batch(self, fr, idx, stream=None, reserved=None):
-        reserved.update(fr=fr, idx=idx)
-        return reserved
-
-    def abort_batch(self, tok):
-        self.taken -= tok["n"]
-
-    def commit_batch(self, tok, audio):
-        self.msgs += [(tok["fr"][i], tok["idx"][i], audio[2 * i:2 * i + 2]) for i in range(len(tok["idx"]))]
-
-    def get(self):
-        self.taken -= 1
-        return self.msgs.pop(0)
-
-
 def _scheduler(monkeypatch, n, rings, clock):
     from mere_fusion_amd.nerf_serving import NerfBatcher, NerfEndToEndScheduler, NerfFeaturePool
-    ev = SimpleNamespace(record=lambda *_: None, query=lambda: True, synchronize=lambda: None)
-    monkeypatch.setattr(torch.cuda, "Event", lambda *a, **k: ev)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: None)
+    fake_cuda_events(monkeypatch)
     pool = NerfFeaturePool(n, U.StubNet(3, "cpu"), 3, device="cpu")
     pool.warm_up()
     ss = [FakeSession(FakeModel(), 10 * k) for k in range(n)]
