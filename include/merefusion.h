@@ -238,6 +238,25 @@ int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_rows_geom* gx,
 /* mf_attention_forward's contract on the five-launch path (pack K, GEMM, row softmax, pack V^T, GEMM) the VAE mid-block runs: any head_dim % 8 == 0. */
 int mf_attention_composite_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk, int heads, int head_dim,
                                    int precision, float* y_full, void* stream);
+/* The producers of the MF_PREC_F16Q activation format, one call each: the bytes a convolution of that precision reads.  Per pixel and 32-channel block the
+ * first plane holds 32 f16 words and the second 64 bytes [q6(v - f16(v)) | q6(f16(v))], each half 24 bytes of e2m3 codes (channel t of the block in bits
+ * [6t, 6t + 6)), one E8M0 scale byte 127 + floor(log2 max) - 2 and 7 zero bytes.
+ * x: device fp32 NCHW [batch][gx->c][gx->h][gx->w].  The destination has dst_c channels (a multiple of 32) and its own halo.
+ *   mode 0: mf_conv2d_forward's software encoder straight from x (gx->cbuf, coff, halo unused); dst_c >= gx->c, the channels past gx->c encode zero.
+ *   mode 1: x is loaded into the slice [coff, coff + c) of a bf16x3 buffer of geometry gx; v = x * scale[b][c] + shift[b][c], SiLU when `silu`, times post[c]
+ *           when `post` is not null (powers of two) -- the conversion kernel of the VAE decoder, chosen by the map size as a network's call would.
+ *   mode 2: GroupNorm + SiLU [* post] with the affine formed inside the conversion kernel from the statistics (maps of a multiple of 64 pixels only).
+ *   mode 3: the same through the statistics + affine launch and the array form of mode 1.
+ * Modes 1 to 3 need dst_c == gx->c and coff % 8 == 0.  gamma, beta, post: device fp32 [c]; scale, shift: device fp32 [batch][c].
+ * Both buffers are filled with the words MF_ACT_Q_POISON_HI / _LO first.  dst_hi, dst_lo: device, batch * (h + 2*dst_halo) * (w + 2*dst_halo) * dst_c + 64
+ * 16-bit words each -- the whole padded destination planes with the allocation's tail.  src_full (optional, modes 1 to 3): the whole source buffer with its
+ * tail, batch * (h + 2*halo) * (w + 2*halo) * cbuf + 64 fp32 values (hi + lo; MF_NN_POISON_X3 where nothing was loaded).  Synchronises the stream; nothing is
+ * written to the outputs when the call fails. */
+#define MF_ACT_Q_POISON_HI 0xC49A
+#define MF_ACT_Q_POISON_LO 0x3F20
+int mf_act_q_encode(const float* x, const mf_rows_geom* gx, int batch, int dst_c, int dst_halo, int mode, int silu, const float* scale, const float* shift,
+                    const float* post, const float* gamma, const float* beta, int groups, float eps, uint16_t* dst_hi, uint16_t* dst_lo, float* src_full,
+                    void* stream);
 
 /* ---- MuseTalk Whisper audio features (H3) -------------------------------------------------- */
 typedef struct mf_whisper mf_whisper;

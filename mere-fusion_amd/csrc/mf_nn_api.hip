@@ -2,7 +2,9 @@
 // tensors in and out, every op launched exactly as the model builders launch it.  Each call owns its buffers: they are filled with a fixed finite
 // poison value first (MF_NN_POISON_*), the input view is loaded over it, and `y_full` hands the whole padded output buffer back, so a test sees
 // every element an op wrote outside its view (halo ring, neighbouring channels of a wider buffer, tokens past a prefix).
+// mf_act_q_encode is the same kind of seam for the producers of the f16 + FP6-block activation format (mf_aux.hip): it hands back the raw planes.
 #include "mf_nn.h"
+#include "mf_aux.h"
 #include <cmath>
 
 namespace {
@@ -50,13 +52,24 @@ struct PBuf {
     int alloc(const mf_rows_geom& g, int batch, bool x3, hipStream_t s) { return alloc(g.cbuf, g.h, g.w, g.halo, batch, x3, s); }
     ActView view(const mf_rows_geom& g) const { return ActView{&b, g.coff, g.c}; }
     ActView all() const { return ActView{&b, 0, b.C}; }
-    int full(float* dst, hipStream_t s) const {      // [batch][Hp][Wp][C] as fp32 (hi + lo), or nothing
+    int full(float* dst, hipStream_t s, int64_t tail = 0) const {      // [batch][Hp][Wp][C] (+ `tail` elements of the allocation's pad) as fp32 (hi + lo), or nothing
         if (!dst) return MF_OK;
-        hipLaunchKernelGGL(k_planes_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.hi, b.lo, dst, n);
+        hipLaunchKernelGGL(k_planes_to_f32, dim3((unsigned)((n + tail + 255) / 256)), dim3(256), 0, s, b.hi, b.lo, dst, n + tail);
         MF_HIP(hipGetLastError());
         return MF_OK;
     }
 };
+
+// fp32 NCHW [batch][C][P] -> the [batch][P][C] rows mf_rows_from_f32 reads
+__global__ __launch_bounds__(256) void k_nchw_to_rows_f32(const float* __restrict__ src, float* __restrict__ dst, int C, int P, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    const int64_t r = i / C;
+    const int p = (int)(r % P);
+    const int64_t b = r / P;
+    dst[i] = src[(b * C + c) * P + p];
+}
 
 struct DevMem {
     void* p = nullptr;
@@ -203,6 +216,56 @@ extern "C" int mf_attention_composite_forward(const float* q, const float* k, co
     if ((rc = mf_attention_composite(&ps.p, &pv.p, &sc.b, &pm.b, bq.all(), bk.all(), bv.all(), bo.all(), heads, batch, precision, s))) return rc;
     if ((rc = mf_rows_to_f32(bo.all(), out, batch, s))) return rc;
     if ((rc = bo.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_act_q_encode(const float* x, const mf_rows_geom* gx, int batch, int dst_c, int dst_halo, int mode, int silu, const float* scale, const float* shift,
+                               const float* post, const float* gamma, const float* beta, int groups, float eps, uint16_t* dst_hi, uint16_t* dst_lo, float* src_full,
+                               void* stream) {
+    MF_REQUIRE(x && dst_hi && dst_lo && geom_ok(gx) && batch > 0, "act_q_encode: null argument or bad geometry");
+    MF_REQUIRE(mode >= 0 && mode <= 3, "act_q_encode: unknown mode %d", mode);
+    MF_REQUIRE(dst_halo >= 0 && dst_c >= gx->c && dst_c % 32 == 0, "act_q_encode: a destination of %d channels (halo %d) for %d", dst_c, dst_halo, gx->c);
+    MF_REQUIRE(mode == 0 || (dst_c == gx->c && gx->coff % 8 == 0 && gx->cbuf % 8 == 0), "act_q_encode: the producers write whole 32-channel blocks of a slice at a multiple of 8");
+    MF_REQUIRE(mode != 1 || (scale && shift), "act_q_encode: mode 1 takes scale and shift");
+    MF_REQUIRE(mode < 2 || (gamma && beta && groups > 0 && groups <= 64 && gx->c % groups == 0), "act_q_encode: the GroupNorm modes take gamma, beta and a group count that divides C");
+    MF_REQUIRE((int64_t)batch * ((int64_t)(gx->h + 2 * gx->halo) * (gx->w + 2 * gx->halo) * gx->cbuf) < ((int64_t)1 << 31) &&
+               (int64_t)batch * ((int64_t)(gx->h + 2 * dst_halo) * (gx->w + 2 * dst_halo) * dst_c) < ((int64_t)1 << 31), "act_q_encode: tensors of 2^31 elements or more");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    PBuf bx, bq;
+    DevMem rows, aff;
+    if ((rc = bq.alloc(dst_c, gx->h, gx->w, dst_halo, batch, true, s))) return rc;
+    if (mode == 0) {
+        if ((rc = mf_nchw_to_act_q(x, gx->c, bq.b, batch, s))) return rc;
+    } else {
+        const int P = gx->h * gx->w, ns = batch * groups * 2;
+        const int64_t total = (int64_t)batch * P * gx->c;
+        if ((rc = bx.alloc(*gx, batch, true, s)) || (rc = rows.alloc((size_t)total * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(k_nchw_to_rows_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, (float*)rows.p, gx->c, P, total);
+        MF_HIP(hipGetLastError());
+        if ((rc = mf_rows_from_f32((const float*)rows.p, nullptr, bx.view(*gx), batch, s))) return rc;
+        if (mode == 1) {
+            if ((rc = mf_affine_silu_to_act_q(bx.view(*gx), scale, shift, silu, bq.b, batch, s, post))) return rc;
+        } else {
+            // the statistics and the [batch][C] affine arrays a network keeps next to its activations (mf_musetalk.hip gn_silu_to_q)
+            if ((rc = aff.alloc((size_t)ns * sizeof(double) + (size_t)2 * batch * gx->c * sizeof(float)))) return rc;
+            double* st = (double*)aff.p;
+            float* sc = (float*)(st + ns);
+            float* sh = sc + (size_t)batch * gx->c;
+            if ((rc = mf_zero_f64(st, ns, s))) return rc;
+            if (mode == 2) {
+                if ((rc = mf_groupnorm_stats(bx.view(*gx), groups, st, batch, s))) return rc;
+                if ((rc = mf_affine_silu_to_act_q(bx.view(*gx), sc, sh, 1, bq.b, batch, s, post, st, gamma, beta, groups, eps))) return rc;
+            } else {
+                if ((rc = mf_groupnorm_affine(bx.view(*gx), gamma, beta, groups, eps, st, sc, sh, batch, s, false))) return rc;
+                if ((rc = mf_affine_silu_to_act_q(bx.view(*gx), sc, sh, 1, bq.b, batch, s, post))) return rc;
+            }
+        }
+        if ((rc = bx.full(src_full, s, 64))) return rc;
+    }
+    MF_HIP(hipMemcpyAsync(dst_hi, bq.b.hi, (size_t)(bq.n + 64) * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+    MF_HIP(hipMemcpyAsync(dst_lo, bq.b.lo, (size_t)(bq.n + 64) * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
     MF_HIP(hipStreamSynchronize(s));
     return MF_OK;
 }
