@@ -10,7 +10,7 @@
 // reference's layouts allow it, no MFMA.  The file is compiled with floating-point contraction OFF so that +,-,*,/ round
 // exactly as written (the CPU restatement the parity tests compare against is built the same way); divisions are the
 // correctly rounded default of hipcc.
-#include "mf_common.h"
+#include "mf_nerf_host.h"
 #include "mf_nerf_grid.h"
 #include "mf_nerf_march.h"
 #include "mf_nerf_frame.h"
@@ -528,14 +528,7 @@ extern "C" int mf_grid_encode_forward(const float* inputs, const float* embeddin
     MF_REQUIRE(gridtype <= 1, "grid_encode_forward: gridtype %u (0 hash, 1 tiled)", gridtype);
     if (B == 0) return MF_OK;
     GridLevels lv{};
-    for (uint32_t l = 0; l < L; ++l) {
-        MF_REQUIRE(offsets_host[l + 1] > offsets_host[l] && offsets_host[l] >= 0, "grid_encode_forward: offsets must increase");
-        const float scale = exp2f((float)l * S) * (float)H - 1.0f;              // gridencoder.cu:123
-        lv.scale[l] = scale;
-        lv.resolution[l] = (uint32_t)std::ceil(scale) + 1;                      // gridencoder.cu:124
-        lv.offset[l] = (uint32_t)offsets_host[l];
-        lv.hashmap_size[l] = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
-    }
+    if (const int rc = mf_grid_levels(lv, offsets_host, L, S, H)) return rc;
     const dim3 grid(blocks(B), L), block(NT);
     hipStream_t s = (hipStream_t)stream;
 #define MF_GCASE(DD, CC)                                                                                                   \
@@ -590,34 +583,27 @@ extern "C" int mf_nerf_resize_frame(const float* image, const float* depth, int 
     return MF_OK;
 }
 
-// ---- launchers of the device-controlled loop pieces (used by mf_nerf_head_render, mf_nerf_net.hip) -----------------------------
-int mf_nerf_loop_init(int* ctl, int N, int max_steps, int* alive, float* rays_t, float* nears, float* weights_sum, float* depth, float* image,
-                      float* amb_aud_sum, float* amb_eye_sum, float* unc_sum, hipStream_t s, const float* rays_o, const float* rays_d, const float* aabb, float min_near,
-                      float* fars) {
-    hipLaunchKernelGGL(k_loop_init, dim3(blocks(N)), dim3(NT), 0, s, ctl, N, max_steps, alive, rays_t, nears, weights_sum, depth, image, amb_aud_sum, amb_eye_sum,
-                       unc_sum, rays_o, rays_d, aabb, min_near, fars);
+// ---- launchers of the device-controlled loop pieces (mf_nerf_host.h; used by mf_nerf_head_render, mf_nerf_head.hip) ----------------------------
+int mf_nerf_loop_init(const NerfLoop& l, const NerfRaySums& r, float* nears, const float* aabb, float min_near, hipStream_t s) {
+    hipLaunchKernelGGL(k_loop_init, dim3(blocks(l.N)), dim3(NT), 0, s, l.ctl, l.N, l.max_steps, l.alive[0], l.rays_t, nears, r.wsum, r.depth, r.image, r.aasum,
+                       r.aesum, r.unsum, l.rays_o, l.rays_d, aabb, min_near, l.fars);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }
-int mf_nerf_loop_round(int* ctl, int N, int max_steps, const int* alive_in, int* alive_out, float* rays_t, const float* rays_o, const float* rays_d,
-                       float bound, float dt_gamma, uint32_t cascades, uint32_t grid_size, const uint8_t* bitfield, const float* fars,
-                       float* xyzs, float* dirs, float* deltas, int phase, float T_thresh, const float* sigmas, const float* rgbs, const float* amb_aud,
-                       const float* amb_eye, const float* unc, float* weights_sum, float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum,
-                       float* unc_sum, hipStream_t s) {
-    if (phase == 0)            // march (the round's n_alive / n_step were set by k_loop_init or the previous round's tail)
-    {
-        const char* e = getenv("MF_NERF_MARCH");                                 // "generic" forces the reference-shaped index arithmetic (tests)
-        const bool fast = cascades == 1 && (grid_size & (grid_size - 1)) == 0 && grid_size <= 128 && !(e && !strcmp(e, "generic"));   // 128: k_loop_march's spread table
-        if (fast)
-            hipLaunchKernelGGL(k_loop_march<true>, dim3(blocks(N)), dim3(NT), 0, s, (const int*)ctl, alive_in, rays_t, rays_o, rays_d, bound, dt_gamma,
-                               (uint32_t)max_steps, cascades, grid_size, bitfield, fars, xyzs, dirs, deltas);
-        else
-            hipLaunchKernelGGL(k_loop_march<false>, dim3(blocks(N)), dim3(NT), 0, s, (const int*)ctl, alive_in, rays_t, rays_o, rays_d, bound, dt_gamma,
-                               (uint32_t)max_steps, cascades, grid_size, bitfield, fars, xyzs, dirs, deltas);
-    }
-    else                       // composite + compaction + head of the next round
-        hipLaunchKernelGGL(k_loop_composite, dim3((unsigned)((N + CT - 1) / CT)), dim3(CT), 0, s, ctl, N, max_steps, T_thresh, alive_in, alive_out, rays_t, sigmas, rgbs, deltas,
-                           amb_aud, amb_eye, unc, weights_sum, depth, image, amb_aud_sum, amb_eye_sum, unc_sum);
+// march (the round's n_alive / n_step were set by k_loop_init or the previous round's tail)
+int mf_nerf_loop_march(const NerfLoop& l, int round, float bound, hipStream_t s) {
+    const char* e = getenv("MF_NERF_MARCH");                                 // "generic" forces the reference-shaped index arithmetic (tests); read per call
+    const bool fast = l.cascades == 1 && (l.grid_size & (l.grid_size - 1)) == 0 && l.grid_size <= 128 && !(e && !strcmp(e, "generic"));   // 128: k_loop_march's spread table
+    const auto kernel = fast ? k_loop_march<true> : k_loop_march<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks(l.N)), dim3(NT), 0, s, l.ctl, l.alive[round & 1], l.rays_t, l.rays_o, l.rays_d, bound,
+                       l.dt_gamma, (uint32_t)l.max_steps, l.cascades, l.grid_size, l.bitfield, l.fars, l.xyzs, l.dirs, l.deltas);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+int mf_nerf_loop_composite(const NerfLoop& l, int round, const NerfFieldOut& f, const NerfRaySums& r, hipStream_t s) {
+    hipLaunchKernelGGL(k_loop_composite, dim3((unsigned)((l.N + CT - 1) / CT)), dim3(CT), 0, s, l.ctl, l.N, l.max_steps, l.T_thresh, l.alive[round & 1],
+                       l.alive[(round + 1) & 1], l.rays_t, f.sigmas, f.rgbs, l.deltas, f.amb_aud, f.amb_eye,
+                       f.unc, r.wsum, r.depth, r.image, r.aasum, r.aesum, r.unsum);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

@@ -2,7 +2,8 @@
 // k_density_sweep (mf_nerf_occupancy.hip).  One copy of the gathers, the MFMA layer chain and the weight staging; what the layout is and why is told at the top of
 // mf_nerf_fused.hip.
 #pragma once
-#include "mf_nn.h"
+#include "mf_nerf_host.h"
+#include "mf_nerf_grid.h"
 #include "mf_nerf_march.h"
 #include <cmath>
 #include <algorithm>
@@ -427,22 +428,19 @@ __device__ __forceinline__ void field_stage_weights(const FusedArgs& a, char* sm
     __syncthreads();
 }
 
-static void fused_args(FusedArgs& a, const bf16_t* packed, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float bound, const float* xyzs,
-                       const float* dirs, const float* enc_a, const float* ind, int n_ind, float eye, int has_eye, int M, float* sigmas, float* rgbs, float* amb_aud,
-                       float* amb_eye, float* unc, const int* M_dev, float sigma_scale, const float* eye_dev, const float* deltas) {
-    a.M_dev = M_dev; a.sigma_scale = sigma_scale; a.eye_dev = eye_dev; a.deltas = deltas;
-    a.xyzs = xyzs; a.dirs = dirs; a.enc_a = enc_a; a.ind = ind; a.w = packed;
-    for (int p = 0; p < 3; ++p) a.emb[p] = emb[p];
-    for (int l = 0; l < NLEV; ++l) {
-        const float scale = exp2f((float)l * log2_pls) * (float)base_res - 1.0f;      // gridencoder.cu:123-124
-        a.scale[l] = scale;
-        a.resolution[l] = (uint32_t)std::ceil(scale) + 1;
-        a.offset[l] = (uint32_t)offsets[l];
-        a.hashmap_size[l] = (uint32_t)(offsets[l + 1] - offsets[l]);
-    }
-    a.bound = bound; a.eye = eye; a.n_ind = n_ind; a.has_eye = has_eye; a.M = M;
+// the kernel arguments for M samples at xyzs / dirs (M_dev: their count on the device, deltas: see FusedArgs)
+static int fused_args(FusedArgs& a, const NerfFieldConsts& f, const NerfFrameInputs& in, const float* xyzs, const float* dirs, int M, const NerfFieldOut& out,
+                      const int* M_dev = nullptr, const float* deltas = nullptr) {
+    a.M_dev = M_dev; a.sigma_scale = in.sigma_scale; a.eye_dev = in.eye_dev; a.deltas = deltas;
+    a.xyzs = xyzs; a.dirs = dirs; a.enc_a = in.enc_a; a.ind = in.ind; a.w = f.packed;
+    for (int p = 0; p < 3; ++p) a.emb[p] = f.emb[p];
+    GridLevels lv;
+    if (const int rc = mf_grid_levels(lv, f.offsets, NLEV, f.log2_pls, (uint32_t)f.base_res)) return rc;
+    for (int l = 0; l < NLEV; ++l) { a.scale[l] = lv.scale[l]; a.resolution[l] = lv.resolution[l]; a.offset[l] = lv.offset[l]; a.hashmap_size[l] = lv.hashmap_size[l]; }
+    a.bound = f.bound; a.eye = in.eye; a.n_ind = f.n_ind; a.has_eye = f.has_eye; a.M = M;
     a.ntiles = (M + TILE - 1) / TILE;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.amb_aud = amb_aud; a.amb_eye = amb_eye; a.unc = unc;
+    a.sigmas = out.sigmas; a.rgbs = out.rgbs; a.amb_aud = out.amb_aud; a.amb_eye = out.amb_eye; a.unc = out.unc;
+    return MF_OK;
 }
 
 template <typename K>

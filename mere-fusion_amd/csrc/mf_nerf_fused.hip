@@ -254,50 +254,39 @@ int mf_nerf_fused_pack(const float* const w[9], int n_ind, bool has_eye, bool x3
     return MF_OK;
 }
 
-
-int mf_nerf_fused_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float bound,
-                         const float* xyzs, const float* dirs, const float* enc_a, const float* ind, int n_ind, float eye, int has_eye, int M,
-                         float* sigmas, float* rgbs, float* amb_aud, float* amb_eye, float* unc, hipStream_t s, const int* M_dev, float sigma_scale, const float* eye_dev,
-                         const float* deltas) {
+int mf_nerf_fused_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const float* xyzs, const float* dirs, int M, const NerfFieldOut& out, hipStream_t s,
+                         const NerfLoop* round) {
     FusedArgs a{};
-    fused_args(a, packed, emb, offsets, log2_pls, base_res, bound, xyzs, dirs, enc_a, ind, n_ind, eye, has_eye, M, sigmas, rgbs, amb_aud, amb_eye, unc, M_dev, sigma_scale, eye_dev,
-               deltas);
-    const size_t lds = (size_t)NFRAG * (x3 ? 2 : 1) * 1024;
-    static bool attr_done[2] = {false, false};
     int rc;
-    if ((rc = x3 ? fused_lds_attr(k_nerf_field_fused<true>, attr_done[1], lds) : fused_lds_attr(k_nerf_field_fused<false>, attr_done[0], lds))) return rc;
+    if ((rc = fused_args(a, f, in, xyzs, dirs, M, out, round ? round->ctl + 3 : nullptr, round ? round->skip_deltas() : nullptr))) return rc;
+    const size_t lds = (size_t)NFRAG * (f.x3 ? 2 : 1) * 1024;
+    static bool attr_done[2] = {false, false};
+    if ((rc = f.x3 ? fused_lds_attr(k_nerf_field_fused<true>, attr_done[1], lds) : fused_lds_attr(k_nerf_field_fused<false>, attr_done[0], lds))) return rc;
     const int grid = std::min(a.ntiles, 256);
-    if (x3) hipLaunchKernelGGL(k_nerf_field_fused<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a);
+    if (f.x3) hipLaunchKernelGGL(k_nerf_field_fused<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a);
     else hipLaunchKernelGGL(k_nerf_field_fused<false>, dim3(grid), dim3(NWAVE * 64), lds, s, a);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }
 
-// the render loop's tail (k_loop_tail): the rounds after the `rounds_launched` that mf_nerf_head_render enqueued as launches, in one launch
-int mf_nerf_tail_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float bound, const float* enc_a,
-                        const float* ind, int n_ind, float eye, int has_eye, float sigma_scale, const float* eye_dev, float* sigmas, float* rgbs, float* amb_aud,
-                        float* amb_eye, float* unc, int* ctl, int N, int max_steps, int rounds_launched, float T_thresh, float dt_gamma, uint32_t cascades,
-                        uint32_t grid_size, int* alive0, int* alive1, float* rays_t, const float* rays_o, const float* rays_d, const float* fars,
-                        const uint8_t* bitfield, float* xyzs, float* dirs, float* deltas, float* wsum, float* depth, float* image, float* aasum, float* aesum,
-                        float* unsum, hipStream_t s) {
+int mf_nerf_tail_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const NerfFieldOut& out, const NerfLoop& l, const NerfRaySums& r, int rounds_launched,
+                        hipStream_t s) {
     FusedArgs a{};
-    const char* skip = getenv("MF_NERF_SKIP_EMPTY");
-    fused_args(a, packed, emb, offsets, log2_pls, base_res, bound, xyzs, dirs, enc_a, ind, n_ind, eye, has_eye, N, sigmas, rgbs, amb_aud, amb_eye, unc, nullptr, sigma_scale, eye_dev,
-               skip && skip[0] == '0' ? nullptr : deltas);
-    TailArgs t{};
-    t.ctl = ctl; t.N = N; t.max_steps = max_steps; t.first_parity = rounds_launched & 1; t.T_thresh = T_thresh; t.dt_gamma = dt_gamma; t.C = cascades; t.H = grid_size;
-    t.alive0 = alive0; t.alive1 = alive1; t.rays_t = rays_t; t.rays_o = rays_o; t.rays_d = rays_d; t.fars = fars; t.grid = bitfield;
-    t.xyzs = xyzs; t.dirs = dirs; t.deltas = deltas; t.wsum = wsum; t.depth = depth; t.image = image; t.aasum = aasum; t.aesum = aesum; t.unsum = unsum;
-    const size_t lds = (size_t)NFRAG * (x3 ? 2 : 1) * 1024;
-    static bool attr_done[2] = {false, false};
     int rc;
-    if ((rc = x3 ? fused_lds_attr(k_loop_tail<true>, attr_done[1], lds) : fused_lds_attr(k_loop_tail<false>, attr_done[0], lds))) return rc;
+    if ((rc = fused_args(a, f, in, l.xyzs, l.dirs, l.N, out, nullptr, l.skip_deltas()))) return rc;
+    TailArgs t{};
+    t.ctl = l.ctl; t.N = l.N; t.max_steps = l.max_steps; t.first_parity = rounds_launched & 1; t.T_thresh = l.T_thresh; t.dt_gamma = l.dt_gamma; t.C = l.cascades;
+    t.H = l.grid_size; t.alive0 = l.alive[0]; t.alive1 = l.alive[1]; t.rays_t = l.rays_t; t.rays_o = l.rays_o; t.rays_d = l.rays_d; t.fars = l.fars; t.grid = l.bitfield;
+    t.xyzs = l.xyzs; t.dirs = l.dirs; t.deltas = l.deltas; t.wsum = r.wsum; t.depth = r.depth; t.image = r.image; t.aasum = r.aasum; t.aesum = r.aesum; t.unsum = r.unsum;
+    const size_t lds = (size_t)NFRAG * (f.x3 ? 2 : 1) * 1024;
+    static bool attr_done[2] = {false, false};
+    if ((rc = f.x3 ? fused_lds_attr(k_loop_tail<true>, attr_done[1], lds) : fused_lds_attr(k_loop_tail<false>, attr_done[0], lds))) return rc;
     // workgroups: 64 (one per 512 rays if the frame has fewer).  When the loop has ended -- the usual case -- each of them reads three words and leaves, and the
     // launch costs what its waves cost to start: 4.9 us with 256 workgroups of 16 waves, a quarter of that with 64; when it has not, the late rounds the tail is
     // there for have a few ten thousand rays at most (a 512 x 512 frame's fifth round: 30 k)
-    const char* e = getenv("MF_NERF_TAIL_WGS");
-    const int grid = std::min(std::max(1, (N + TAIL_RC - 1) / TAIL_RC), e && atoi(e) > 0 ? std::min(atoi(e), 256) : 64);
-    if (x3) hipLaunchKernelGGL(k_loop_tail<true>, dim3(grid), dim3(TAIL_NW * 64), lds, s, a, t);
+    const char* e = getenv("MF_NERF_TAIL_WGS");                                  // read per call (A/B)
+    const int grid = std::min(std::max(1, (l.N + TAIL_RC - 1) / TAIL_RC), e && atoi(e) > 0 ? std::min(atoi(e), 256) : 64);
+    if (f.x3) hipLaunchKernelGGL(k_loop_tail<true>, dim3(grid), dim3(TAIL_NW * 64), lds, s, a, t);
     else hipLaunchKernelGGL(k_loop_tail<false>, dim3(grid), dim3(TAIL_NW * 64), lds, s, a, t);
     MF_HIP(hipGetLastError());
     return MF_OK;

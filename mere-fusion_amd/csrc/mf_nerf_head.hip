@@ -1,0 +1,170 @@
+// ER-NeRF head render loop without host round trips: `run_cuda`'s inference branch (reference: ernerf/nerf_triplane/renderer.py:231-291) with the round
+// control (n_alive, n_step, step) kept in HBM.  Host code only: this file launches the kernels of mf_nerf.hip and mf_nerf_fused.hip through mf_nerf_host.h.
+//
+// The reference compacts `rays_alive` with a boolean mask and reads its length back on the host every round; here k_loop_init / k_loop_composite (mf_nerf.hip)
+// do both on the device, every launch has a fixed grid and exits when its round has nothing to do.  A frame needs ~5 of the max_steps = 16 rounds the
+// reference allows, so only as many rounds as the frames before needed are enqueued as launches and ONE tail launch (k_loop_tail, mf_nerf_fused.hip) stands for
+// the rest: it finds the loop ended, or runs the remaining rounds itself -- no round is ever dropped, and nothing waits for the host.  The whole frame is
+// capturable as one hipGraph.
+#include "mf_nerf_host.h"
+#include "mf_nerf_march.h"
+#include <cstdlib>
+#include <cstring>
+
+struct mf_nerf_head {
+    mf_nerf_field* field = nullptr;
+    int cap = 0;
+    std::vector<void*> dev;
+    float *aabb, *nears, *fars, *rays_t, *xyzs, *dirs, *deltas, *sig, *rgb, *aa, *ae, *un, *wsum, *aasum, *aesum, *unsum;
+    int *alive[2], *ctl;
+    const float* eye_dev = nullptr;      // mf_nerf_head_set_eye: the eye feature stays on the device
+    const float* aabb_user = nullptr;    // mf_nerf_head_set_aabb: the caller's aabb_infer (device), read instead of `aabb` below
+    // round-count feedback: two words of pinned host memory the device posts to when a frame's loop ends ([0] rounds the frame ran, [1] the tail's error flag);
+    // read without a sync, so it tells about a frame that finished some calls ago
+    volatile int* fb = nullptr;
+    int hist[4] = {0, 0, 0, 0}, hist_n = 0;
+    int fixed_rounds = -1;               // mf_nerf_head_set_rounds: >= 0 pins the launched-round count (a captured graph is keyed on it), -1 = follow the feedback
+    ~mf_nerf_head() {
+        for (void* d : dev) (void)hipFree(d);
+        if (fb) (void)hipHostFree((void*)fb);
+    }
+};
+
+constexpr int HEAD_MAX_ROUNDS = 1024;     // max_steps accepted by mf_nerf_head_render (one round per step at least: renderer.py:270); the control block holds tail tickets for as many
+
+// How many rounds of the next frame are enqueued as (march, field, composite) launches; the tail launch covers the rest.  The most rounds any of the last four
+// observed frames ran; every round (no tail) until a first frame has reported.  MF_NERF_TAIL_AFTER=<k> fixes it (tests, A/B: 0 = the tail runs the whole
+// loop, "off" = launches only, as before round 6); read per call.
+static int head_plan(mf_nerf_head* h, int max_steps) {
+    const char* e = getenv("MF_NERF_TAIL_AFTER");
+    if (e && *e) {
+        if (!strcmp(e, "off")) return max_steps;
+        const int k = atoi(e);
+        return k < 0 ? max_steps : (k < max_steps ? k : max_steps);
+    }
+    const int seen = h->fb ? h->fb[0] : 0;
+    if (seen > 0) { h->hist[h->hist_n & 3] = seen; h->hist_n++; }
+    if (h->hist_n == 0) return max_steps;
+    int m = 0;
+    for (int i = 0; i < 4; ++i) m = h->hist[i] > m ? h->hist[i] : m;
+    // no margin: a frame that needs more rounds than its predecessors runs them in the tail launch (and the next frames follow); a margin of one round was three
+    // launches per frame that found nothing to do (2 043 -> 2 068 frames/s)
+    return m < max_steps ? m : max_steps;
+}
+
+extern "C" int mf_nerf_head_create(mf_nerf_field* field, int max_rays, mf_nerf_head** out) {
+    MF_REQUIRE(field && out && max_rays > 0, "nerf_head_create: bad argument");
+    MF_REQUIRE(field->fused_w, "nerf_head_create: needs the fused field kernel (unset MF_NERF_FIELD=gemm)");
+    MF_REQUIRE(max_rays <= field->cap_batches * TW, "nerf_head_create: %d rays exceed the field's sample capacity %d", max_rays, field->cap_batches * TW);
+    *out = nullptr;
+    std::unique_ptr<mf_nerf_head> h(new mf_nerf_head());
+    h->field = field; h->cap = max_rays;
+    auto fm = [&](float** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(float))); h->dev.push_back(*p); return MF_OK; };
+    auto im = [&](int** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(int))); h->dev.push_back(*p); return MF_OK; };
+    const size_t N = (size_t)max_rays;
+    int rc;
+    if ((rc = fm(&h->aabb, 6)) || (rc = fm(&h->nears, N)) || (rc = fm(&h->fars, N)) || (rc = fm(&h->rays_t, N)) || (rc = fm(&h->xyzs, 3 * N)) ||
+        (rc = fm(&h->dirs, 3 * N)) || (rc = fm(&h->deltas, 2 * N)) || (rc = fm(&h->sig, N)) || (rc = fm(&h->rgb, 3 * N)) || (rc = fm(&h->aa, N)) ||
+        (rc = fm(&h->ae, N)) || (rc = fm(&h->un, N)) || (rc = fm(&h->wsum, N)) || (rc = fm(&h->aasum, N)) || (rc = fm(&h->aesum, N)) ||
+        (rc = fm(&h->unsum, N)) || (rc = im(&h->alive[0], N)) || (rc = im(&h->alive[1], N)) || (rc = im(&h->ctl, loop_ctl_ints(HEAD_MAX_ROUNDS))))
+        return rc;
+    MF_HIP(hipMemset(h->ctl, 0, loop_ctl_ints(HEAD_MAX_ROUNDS) * sizeof(int)));
+    {
+        int* fb = nullptr;
+        MF_HIP(hipHostMalloc((void**)&fb, 4 * sizeof(int), hipHostMallocMapped));
+        fb[0] = fb[1] = fb[2] = fb[3] = 0;
+        h->fb = fb;
+        void* fb_dev = nullptr;
+        MF_HIP(hipHostGetDevicePointer(&fb_dev, fb, 0));
+        MF_HIP(hipMemcpy(h->ctl + LOOP_CTL_FB, &fb_dev, sizeof(fb_dev), hipMemcpyHostToDevice));
+    }
+    const float b = field->cfg.bound;
+    const float aabb[6] = {-b, -b / 2, -b, b, b / 2, b};                                    // aabb_infer, renderer.py:86-89
+    MF_HIP(hipMemcpy(h->aabb, aabb, sizeof(aabb), hipMemcpyHostToDevice));
+    *out = h.release();
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_render(mf_nerf_head* h, const float* rays_o, const float* rays_d, int n_rays, const uint8_t* density_bitfield, int cascades,
+                                   int grid_size, float min_near, float dt_gamma, int max_steps, float T_thresh, float density_scale, const float* enc_a,
+                                   const float* ind_code, float eye, const float* bg_color, int bg_per_ray, float bg_const, float* image, float* depth,
+                                   float* weights_sum, uint8_t* frame_u8, void* stream) {
+    MF_REQUIRE(h && rays_o && rays_d && density_bitfield && enc_a && image && depth, "nerf_head_render: null argument");
+    MF_REQUIRE(n_rays > 0 && n_rays <= h->cap && max_steps > 0 && max_steps <= HEAD_MAX_ROUNDS, "nerf_head_render: n_rays=%d (capacity %d) max_steps=%d", n_rays, h->cap, max_steps);
+    hipStream_t s = (hipStream_t)stream;
+    const NerfFieldConsts f = h->field->consts();
+    MF_REQUIRE(f.n_ind == 0 || ind_code, "nerf_head_render: the field was built with an individual code");
+    const char* skip_env = getenv("MF_NERF_SKIP_EMPTY");                       // "0": evaluate every slot as the reference does (A/B); read per call
+    const NerfLoop loop{h->ctl, n_rays, max_steps, {h->alive[0], h->alive[1]}, h->rays_t, h->fars, rays_o, rays_d, density_bitfield, (uint32_t)cascades,
+                        (uint32_t)grid_size, dt_gamma, T_thresh, h->xyzs, h->dirs, h->deltas, !(skip_env && skip_env[0] == '0')};
+    const NerfFrameInputs in{enc_a, ind_code, eye, h->eye_dev, density_scale};
+    const NerfFieldOut out{h->sig, h->rgb, h->aa, h->ae, h->un};
+    const NerfRaySums sums{weights_sum ? weights_sum : h->wsum, depth, image, h->aasum, h->aesum, h->unsum};
+    int rc;
+    if ((rc = mf_nerf_loop_init(loop, sums, h->nears, h->aabb_user ? h->aabb_user : h->aabb, min_near, s))) return rc;
+    MF_REQUIRE(!h->fb || h->fb[1] == 0, "nerf_head_render: the tail kernel of an earlier frame gave up waiting for a round (control block error flag)");
+    const int rounds = h->fixed_rounds >= 0 ? (h->fixed_rounds < max_steps ? h->fixed_rounds : max_steps) : head_plan(h, max_steps);
+    for (int it = 0; it < rounds; ++it)
+        if ((rc = mf_nerf_loop_march(loop, it, f.bound, s)) || (rc = mf_nerf_fused_launch(f, in, loop.xyzs, loop.dirs, loop.N, out, s, &loop)) ||
+            (rc = mf_nerf_loop_composite(loop, it, out, sums, s)))
+            return rc;
+    // at least one sample per alive ray and round, so max_steps rounds always suffice (step += n_step >= 1, renderer.py:270): with every round enqueued there is no tail
+    if (rounds < max_steps && (rc = mf_nerf_tail_launch(f, in, out, loop, sums, rounds, s))) return rc;
+    if (bg_per_ray < 0) return MF_OK;                                                       // finished later by mf_nerf_head_finish
+    return mf_nerf_finish(image, depth, sums.wsum, h->nears, h->fars, bg_color, bg_per_ray, bg_const, n_rays, frame_u8, stream);
+}
+
+extern "C" int mf_nerf_head_finish(mf_nerf_head* h, int n_rays, const float* bg_color, int bg_per_ray, float bg_const, float* image, float* depth,
+                                   const float* weights_sum, uint8_t* frame_u8, void* stream) {
+    MF_REQUIRE(h && image && depth && n_rays > 0 && n_rays <= h->cap && bg_per_ray >= 0, "nerf_head_finish: bad argument");
+    return mf_nerf_finish(image, depth, weights_sum ? weights_sum : h->wsum, h->nears, h->fars, bg_color, bg_per_ray, bg_const, n_rays, frame_u8, stream);
+}
+
+extern "C" int mf_nerf_head_set_eye(mf_nerf_head* h, const float* eye_dev) {
+    MF_REQUIRE(h, "nerf_head_set_eye: null handle");
+    h->eye_dev = eye_dev;
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_set_aabb(mf_nerf_head* h, const float* aabb_dev) {
+    MF_REQUIRE(h, "nerf_head_set_aabb: null handle");
+    h->aabb_user = aabb_dev;
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_plan_rounds(mf_nerf_head* h, int max_steps, int* rounds) {
+    MF_REQUIRE(h && rounds && max_steps > 0 && max_steps <= HEAD_MAX_ROUNDS, "nerf_head_plan_rounds: bad argument");
+    *rounds = head_plan(h, max_steps);
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_set_rounds(mf_nerf_head* h, int rounds) {
+    MF_REQUIRE(h && rounds >= -1 && rounds <= HEAD_MAX_ROUNDS, "nerf_head_set_rounds: bad argument");
+    h->fixed_rounds = rounds;
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_last_rounds(mf_nerf_head* h, int* rounds, int* error_flag) {
+    MF_REQUIRE(h && h->fb, "nerf_head_last_rounds: null handle");
+    if (rounds) *rounds = h->fb[0];
+    if (error_flag) *error_flag = h->fb[1];
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_ctl_snapshot(mf_nerf_head* h, int* out, int n_ints) {
+    MF_REQUIRE(h && out && n_ints > 0 && (size_t)n_ints <= loop_ctl_ints(HEAD_MAX_ROUNDS), "nerf_head_ctl_snapshot: bad argument");
+    MF_HIP(hipMemcpy(out, h->ctl, (size_t)n_ints * sizeof(int), hipMemcpyDeviceToHost));
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_head_sums(mf_nerf_head* h, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream) {
+    MF_REQUIRE(h && n_rays > 0 && n_rays <= h->cap, "nerf_head_sums: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)n_rays * sizeof(float);
+    if (ambient_aud) MF_HIP(hipMemcpyAsync(ambient_aud, h->aasum, bytes, hipMemcpyDeviceToDevice, s));
+    if (ambient_eye) MF_HIP(hipMemcpyAsync(ambient_eye, h->aesum, bytes, hipMemcpyDeviceToDevice, s));
+    if (uncertainty) MF_HIP(hipMemcpyAsync(uncertainty, h->unsum, bytes, hipMemcpyDeviceToDevice, s));
+    return MF_OK;
+}
+
+extern "C" void mf_nerf_head_destroy(mf_nerf_head* h) { delete h; }

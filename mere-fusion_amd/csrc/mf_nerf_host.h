@@ -1,0 +1,138 @@
+// Host-side declarations shared by the ER-NeRF translation units (mf_nerf*.hip): every host function that one of them defines and another calls, the plain
+// structs that carry the argument groups between them, and the field handle the render loop reads.  The file that defines a function and every file that calls it
+// include this header, so a prototype that drifts is a compile error.  Nothing here is passed to a kernel: the launchers copy what they need into their own
+// kernel-argument structs (FusedArgs, TailArgs, TorsoFusedArgs, ...).
+#pragma once
+#include "mf_nn.h"
+#include <memory>
+#include <vector>
+
+// ---- argument groups (aggregate-initialised where they are used, passed by const&) ---------------------------------------------------------------
+struct NerfFieldConsts {                 // what a field handle holds for the fused kernels (mf_nerf_field::consts)
+    const bf16_t* packed;                // weight fragments of mf_nerf_fused_pack
+    bool x3;
+    const float* emb[3];                 // tri-plane embedding tables (xy, yz, xz)
+    const int* offsets;                  // host: num_levels + 1 level offsets
+    float log2_pls;
+    int base_res;
+    float bound;
+    int n_ind, has_eye;
+};
+struct NerfFrameInputs {                 // per frame
+    const float *enc_a, *ind;            // device: audio feature [32], individual code [n_ind] (or null)
+    float eye;
+    const float* eye_dev;                // the eye feature read on the device instead of `eye`, or null
+    float sigma_scale;                   // NeRFRenderer.density_scale (renderer.py:261)
+};
+struct NerfFieldOut { float *sigmas, *rgbs, *amb_aud, *amb_eye, *unc; };     // per sample; unc may be null
+struct NerfRaySums { float *wsum, *depth, *image, *aasum, *aesum, *unsum; };  // per ray
+struct NerfLoop {                        // the device-controlled render loop of one frame
+    int* ctl;                            // control block (mf_nerf_march.h)
+    int N, max_steps;
+    int* alive[2];                       // round r reads alive[r & 1] and appends its survivors to the other
+    float *rays_t, *fars;                // (fars: written by the init launch)
+    const float *rays_o, *rays_d;
+    const uint8_t* bitfield;
+    uint32_t cascades, grid_size;
+    float dt_gamma, T_thresh;
+    float *xyzs, *dirs, *deltas;         // the round's samples
+    bool skip_empty;                     // MF_NERF_SKIP_EMPTY, read once per frame: the field skips fragments whose slots hold no sample
+    const float* skip_deltas() const { return skip_empty ? deltas : nullptr; }    // what the field kernels get as FusedArgs::deltas
+};
+struct NerfGridBufs { float* density_grid; uint8_t* bitfield; float *tmp_grid, *xyzs_out; double *mean_density, *partials; };   // mf_nerf_density_grid_update's
+struct NerfTorsoConsts {                 // what a torso handle holds for the fused kernel
+    const float *w, *emb;                // device: the six layers' fp32 tables (mf_nerf_torso_fused_weight_count entries), the tiled grid's embedding
+    const int* offsets;                  // host: 17 level offsets
+    float log2_pls;
+    int base_res;
+    float shrink;
+    int G;                               // density_grid_torso is G x G
+};
+
+// ---- mf_nerf_fused.hip: the whole field as one kernel ---------------------------------------------------------------------------------------------
+// w: the nine [cout][cin] matrices in reference order (aud0, aud1, eye0, eye1, sig0, sig1, sig2, col0, col1; eye* may be null)
+int mf_nerf_fused_pack(const float* const w[9], int n_ind, bool has_eye, bool x3, bf16_t** dev_out);
+// round: the samples are a render-loop round's (their count is read on the device from ctl[3], empty fragments are skipped as round->skip_empty says)
+int mf_nerf_fused_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const float* xyzs, const float* dirs, int M, const NerfFieldOut& out, hipStream_t s,
+                         const NerfLoop* round = nullptr);
+// the rounds after the `rounds_launched` that were enqueued as launches, in one launch (k_loop_tail)
+int mf_nerf_tail_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const NerfFieldOut& out, const NerfLoop& loop, const NerfRaySums& sums,
+                        int rounds_launched, hipStream_t s);
+
+// ---- mf_nerf.hip: the launches of a round --------------------------------------------------------------------------------------------------------
+// init: alive[0] = 0..N-1, near / far of every ray (raymarching.cu:92-145), zeroed sums, the first round's head
+int mf_nerf_loop_init(const NerfLoop& loop, const NerfRaySums& sums, float* nears, const float* aabb, float min_near, hipStream_t s);
+int mf_nerf_loop_march(const NerfLoop& loop, int round, float bound, hipStream_t s);
+// composite + compaction + head of the next round
+int mf_nerf_loop_composite(const NerfLoop& loop, int round, const NerfFieldOut& field, const NerfRaySums& sums, hipStream_t s);
+
+// ---- mf_nerf_occupancy.hip: the occupancy-grid rebuild over the fused field's weight fragments (sweep, dilate + EMA, reduce + pack) -----------------
+int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked
+// in.sigma_scale: density_scale; f.has_eye: whether this rebuild feeds the eye feature
+int mf_nerf_occupancy_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const NerfGridBufs& g, int cascades, int grid_size, float bound, float decay,
+                             float density_thresh, const float* noise, hipStream_t s);
+
+// ---- mf_nerf_torso.hip: the whole torso branch as one fp32 kernel, and the torso grid's rebuild through the same per-point code ------------------------
+int mf_nerf_torso_fused_weight_count();
+// bias: host, [64] = the per-frame first-layer biases of the deform net | the torso net
+int mf_nerf_torso_fused_launch(const NerfTorsoConsts& t, const float* bias, const float* density, const float* bg_coords, float thresh, const float* bg,
+                               int bg_per_ray, float bg_const, int N, float* out, float* alpha_out, float* deform, hipStream_t s);
+// sweep, 5 x 5 dilate + EMA, mean; partials: G^2 / 256 doubles
+int mf_nerf_torso_grid_launch(const NerfTorsoConsts& t, const float* bias, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out,
+                              float* mean, double* partials, hipStream_t s);
+
+// ---- the handles' shared base and the field handle (defined in mf_nerf_net.hip; mf_nerf_head.hip renders through a field) ---------------------------
+constexpr int TW = 1024;                 // tokens per "image" of the token buffers
+
+// shared by the field and the torso net: token buffers of 1 x TW "images", bias-free Linears as bound 1x1-conv plans
+struct TokenNet {
+    int precision = MF_PREC_BF16X3;
+    int cap_batches = 0;
+    std::vector<std::unique_ptr<ActBuf>> bufs;
+    std::vector<std::unique_ptr<ConvPlan>> plans;
+    std::vector<void*> dev;
+
+    ~TokenNet() {
+        for (auto& p : plans) mf_conv_plan_destroy(p.get());
+        for (auto& b : bufs) mf_actbuf_free(b.get());
+        for (void* d : dev) (void)hipFree(d);
+    }
+    ActBuf* seq(int C) {
+        bufs.emplace_back(new ActBuf());
+        ActBuf* b = bufs.back().get();
+        b->C = C; b->H = 1; b->W = TW; b->halo = 0;
+        return b;
+    }
+    int alloc() {
+        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap_batches, precision); if (rc) return rc; }
+        return MF_OK;
+    }
+    // Linear(cin -> cout, bias=False) (network.py:79) as a 1x1 convolution; `w` is [cout][cin_buf] with the input-channel order of
+    // the buffer view it reads
+    int linear(ConvPlan** out, const std::vector<float>& w, int cin, int cout, int act, ActBuf* in) {
+        plans.emplace_back(new ConvPlan());
+        ConvPlan* p = plans.back().get();
+        mf_conv2d_desc d{};
+        d.cin = cin; d.cout = cout; d.kh = d.kw = 1; d.stride_h = d.stride_w = 1; d.act = act; d.in_h = 1; d.in_w = TW;
+        int rc = mf_conv_plan_create(p, d, w.data(), nullptr, nullptr, nullptr, nullptr, nullptr, precision);
+        if (rc) return rc;
+        if ((rc = mf_conv_bind(p, *in))) return rc;
+        *out = p;
+        return MF_OK;
+    }
+};
+
+struct mf_nerf_field : TokenNet {
+    mf_nerf_field_config cfg{};
+    ActBuf *SI = nullptr, *CI = nullptr, *T1 = nullptr, *AU = nullptr, *T2 = nullptr, *EY = nullptr, *S1 = nullptr, *S2 = nullptr, *C1 = nullptr, *RGB = nullptr;
+    ConvPlan *a1, *a2, *e1, *e2, *s1, *s2, *s3, *c1, *c2;
+    float* emb[3] = {nullptr, nullptr, nullptr};
+    float *coords = nullptr, *enc = nullptr, *d_enc_a = nullptr, *d_ind = nullptr;
+    bf16_t* fused_w = nullptr;      // weight fragments of k_nerf_field_fused, or null (MF_NERF_FIELD=gemm)
+    double* occ_partials = nullptr; // per-workgroup sums of mf_nerf_density_grid_update, allocated at its first call
+    size_t occ_cap = 0;
+    NerfFieldConsts consts() const {
+        return {fused_w, precision == MF_PREC_BF16X3, {emb[0], emb[1], emb[2]}, cfg.offsets, cfg.log2_per_level_scale, cfg.base_resolution, cfg.bound,
+                cfg.individual_dim, cfg.exp_eye};
+    }
+};

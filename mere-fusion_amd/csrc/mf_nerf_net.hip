@@ -1,5 +1,8 @@
-// ER-NeRF radiance field on gfx950: tri-plane hash-grid features -> audio / eye attention -> sigma MLP -> colour MLP.
+// ER-NeRF field and torso handles on gfx950 (mf_nerf_field_*, mf_nerf_density_grid_update, mf_nerf_torso_*): weights, buffers and the PER-LAYER route of both nets.
+// By default a handle runs its net as one kernel (mf_nerf_fused.hip, mf_nerf_torso.hip, through mf_nerf_host.h); the route here -- every Linear a launch -- stays for
+// A/B and as the tests' independent cross-check (MF_NERF_FIELD=gemm, MF_TORSO=gemm).  The head render loop over a field is mf_nerf_head.hip.
 //
+// The radiance field: tri-plane hash-grid features -> audio / eye attention -> sigma MLP -> colour MLP.
 // Replaces `NeRFNetwork.forward` + `density` + `encode_x` (reference: ernerf/nerf_triplane/network.py:204-219, 249-308) for the
 // inference call `self.forward(xyzs, dirs, enc_a, ind_code, eye)` of the render loop (renderer.py:260): per sample 36 grid
 // features, SH(dir), and ten bias-free Linear layers (23 184 MACs).
@@ -12,53 +15,15 @@
 //     CI [96] = [ h0 | geo_feat 64 | 0 x7 | SH 16 | ind_code 4 | 0 x4 ]             <- colour_net input  (network.py:262-269)
 // sigma_net's last layer writes its 65 outputs straight into CI[0..64]; colour_net's weight columns are permuted to that layout
 // (and zero on h0), so geo_feat is never copied.
-#include "mf_nn.h"
-#include "mf_nerf_march.h"
+#include "mf_nerf_host.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <string>
-#include <vector>
-
-extern "C" int mf_grid_encode_forward(const float* inputs, const float* embeddings, const int* offsets_host, float* outputs, uint32_t B,
-                                      uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
-                                      int out_blc, void* stream);
-
-// mf_nerf_fused.hip: the whole field as one kernel (default); the per-layer GEMM path below stays for A/B (MF_NERF_FIELD=gemm)
-int mf_nerf_fused_pack(const float* const w[9], int n_ind, bool has_eye, bool x3, bf16_t** dev_out);
-int mf_nerf_fused_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float bound,
-                         const float* xyzs, const float* dirs, const float* enc_a, const float* ind, int n_ind, float eye, int has_eye, int M,
-                         float* sigmas, float* rgbs, float* amb_aud, float* amb_eye, float* unc, hipStream_t s, const int* M_dev = nullptr,
-                         float sigma_scale = 1.f, const float* eye_dev = nullptr, const float* deltas = nullptr);
-int mf_nerf_tail_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float bound, const float* enc_a,
-                        const float* ind, int n_ind, float eye, int has_eye, float sigma_scale, const float* eye_dev, float* sigmas, float* rgbs, float* amb_aud,
-                        float* amb_eye, float* unc, int* ctl, int N, int max_steps, int rounds_launched, float T_thresh, float dt_gamma, uint32_t cascades,
-                        uint32_t grid_size, int* alive0, int* alive1, float* rays_t, const float* rays_o, const float* rays_d, const float* fars,
-                        const uint8_t* bitfield, float* xyzs, float* dirs, float* deltas, float* wsum, float* depth, float* image, float* aasum, float* aesum,
-                        float* unsum, hipStream_t s);
-
-// mf_nerf_occupancy.hip: the occupancy-grid rebuild over the fused field's weight fragments (sweep, dilate + EMA, reduce + pack)
-int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked
-int mf_nerf_occupancy_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float field_bound,
-                             int has_eye, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound, const float* enc_a, float eye,
-                             float density_scale, float decay, float density_thresh, const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density,
-                             double* partials, hipStream_t s);
-
-// mf_nerf_torso.hip: the whole torso branch as one fp32 kernel (default); the GEMM chain below stays for A/B (MF_TORSO=gemm)
-int mf_nerf_torso_fused_weight_count();
-int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls,
-                               int base_res, const float* density, int G, const float* bg_coords, float shrink, float thresh, const float* bg,
-                               int bg_per_ray, float bg_const, int N, float* out, float* alpha_out, float* deform, hipStream_t s);
-// ... and the torso grid's rebuild through the same per-point code: sweep, 5 x 5 dilate + EMA, mean
-int mf_nerf_torso_grid_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
-                              float shrink, int G, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out, float* mean,
-                              double* partials, hipStream_t s);
 
 namespace {
 
-constexpr int TW = 1024;          // tokens per "image" of the token buffers
 constexpr int ENC = 36, AUD = 32, GEO = 64, SHD = 16;
 constexpr int SI_C = 72, CI_C = 96, CI_SH = 72, CI_IND = 88;
 
@@ -164,55 +129,6 @@ __global__ __launch_bounds__(256) void k_nf_out(const bf16_t* __restrict__ ci_hi
 }
 
 }  // namespace
-
-// shared by the field and the torso net: token buffers of 1 x TW "images", bias-free Linears as bound 1x1-conv plans
-struct TokenNet {
-    int precision = MF_PREC_BF16X3;
-    int cap_batches = 0;
-    std::vector<std::unique_ptr<ActBuf>> bufs;
-    std::vector<std::unique_ptr<ConvPlan>> plans;
-    std::vector<void*> dev;
-
-    ~TokenNet() {
-        for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) mf_actbuf_free(b.get());
-        for (void* d : dev) (void)hipFree(d);
-    }
-    ActBuf* seq(int C) {
-        bufs.emplace_back(new ActBuf());
-        ActBuf* b = bufs.back().get();
-        b->C = C; b->H = 1; b->W = TW; b->halo = 0;
-        return b;
-    }
-    int alloc() {
-        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap_batches, precision); if (rc) return rc; }
-        return MF_OK;
-    }
-    // Linear(cin -> cout, bias=False) (network.py:79) as a 1x1 convolution; `w` is [cout][cin_buf] with the input-channel order of
-    // the buffer view it reads
-    int linear(ConvPlan** out, const std::vector<float>& w, int cin, int cout, int act, ActBuf* in) {
-        plans.emplace_back(new ConvPlan());
-        ConvPlan* p = plans.back().get();
-        mf_conv2d_desc d{};
-        d.cin = cin; d.cout = cout; d.kh = d.kw = 1; d.stride_h = d.stride_w = 1; d.act = act; d.in_h = 1; d.in_w = TW;
-        int rc = mf_conv_plan_create(p, d, w.data(), nullptr, nullptr, nullptr, nullptr, nullptr, precision);
-        if (rc) return rc;
-        if ((rc = mf_conv_bind(p, *in))) return rc;
-        *out = p;
-        return MF_OK;
-    }
-};
-
-struct mf_nerf_field : TokenNet {
-    mf_nerf_field_config cfg{};
-    ActBuf *SI = nullptr, *CI = nullptr, *T1 = nullptr, *AU = nullptr, *T2 = nullptr, *EY = nullptr, *S1 = nullptr, *S2 = nullptr, *C1 = nullptr, *RGB = nullptr;
-    ConvPlan *a1, *a2, *e1, *e2, *s1, *s2, *s3, *c1, *c2;
-    float* emb[3] = {nullptr, nullptr, nullptr};
-    float *coords = nullptr, *enc = nullptr, *d_enc_a = nullptr, *d_ind = nullptr;
-    bf16_t* fused_w = nullptr;      // weight fragments of k_nerf_field_fused, or null (MF_NERF_FIELD=gemm)
-    double* occ_partials = nullptr; // per-workgroup sums of mf_nerf_density_grid_update, allocated at its first call
-    size_t occ_cap = 0;
-};
 
 static const mf_tensor* nf_find(const std::map<std::string, const mf_tensor*>& sd, const std::string& k, int64_t r, int64_t c) {
     auto it = sd.find(k);
@@ -331,10 +247,11 @@ extern "C" int mf_nerf_density_grid_update(mf_nerf_field* h, float* density_grid
         h->dev.push_back(p);
         h->occ_partials = p; h->occ_cap = need;
     }
-    const mf_nerf_field_config& c = h->cfg;
-    return mf_nerf_occupancy_launch(h->fused_w, h->precision == MF_PREC_BF16X3, h->emb, c.offsets, c.log2_per_level_scale, c.base_resolution, c.bound,
-                                    use_eye ? 1 : 0, density_grid, density_bitfield, cascades, grid_size, bound, enc_a, eye, density_scale, decay, density_thresh,
-                                    noise, tmp_grid, xyzs_out, mean_density, h->occ_partials, (hipStream_t)stream);
+    NerfFieldConsts f = h->consts();
+    f.n_ind = 0; f.has_eye = use_eye ? 1 : 0;                                   // the density half: no individual code; the eye feature only when the caller feeds it
+    return mf_nerf_occupancy_launch(f, NerfFrameInputs{enc_a, nullptr, eye, nullptr, density_scale},
+                                    NerfGridBufs{density_grid, density_bitfield, tmp_grid, xyzs_out, mean_density, h->occ_partials}, cascades, grid_size, bound, decay,
+                                    density_thresh, noise, (hipStream_t)stream);
 }
 
 extern "C" int mf_nerf_field_forward(mf_nerf_field* h, const float* xyzs, const float* dirs, const float* enc_a, const float* ind_code,
@@ -350,8 +267,7 @@ extern "C" int mf_nerf_field_forward(mf_nerf_field* h, const float* xyzs, const 
     const bool x3 = h->precision == MF_PREC_BF16X3;
     const mf_nerf_field_config& c = h->cfg;
     if (h->fused_w)
-        return mf_nerf_fused_launch(h->fused_w, x3, h->emb, c.offsets, c.log2_per_level_scale, c.base_resolution, c.bound, xyzs, dirs, enc_a, ind_code,
-                                    c.individual_dim, eye, c.exp_eye, M, sigmas, rgbs, amb_aud, amb_eye, uncertainty, s);
+        return mf_nerf_fused_launch(h->consts(), NerfFrameInputs{enc_a, ind_code, eye, nullptr, 1.f}, xyzs, dirs, M, NerfFieldOut{sigmas, rgbs, amb_aud, amb_eye, uncertainty}, s);
     MF_HIP(hipMemcpyAsync(h->d_enc_a, enc_a, AUD * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (c.individual_dim) MF_HIP(hipMemcpyAsync(h->d_ind, ind_code, c.individual_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_nf_prep, dim3(gb), dim3(256), 0, s, xyzs, dirs, h->d_ind, c.individual_dim, c.bound, M, h->coords, h->CI->hi, h->CI->lo);
@@ -482,7 +398,8 @@ struct mf_nerf_torso : TokenNet {
     const float* grid = nullptr;               // mf_nerf_torso_set_grid / _grid_update: the caller's density_grid_torso, borrowed; null = `density`, the copy of creation
     double* grid_partials = nullptr;           // per-workgroup sums of mf_nerf_torso_grid_update (grid_size^2 / 256 <= 64 at the sizes served)
     const float* sampled() const { return grid ? grid : density; }
-    void frame_bias(const float* frame_consts_host, float* bd, float* bt) const;
+    NerfTorsoConsts consts() const { return {wf, emb, cfg.offsets, cfg.log2_per_level_scale, cfg.base_resolution, cfg.torso_shrink, cfg.grid_size}; }
+    void frame_bias(const float* frame_consts_host, float* bias) const;      // bias [64]: deform net | torso net
 };
 
 extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_tensor* weights, int n_weights, int precision, int max_pixels,
@@ -584,7 +501,7 @@ extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_te
 }
 
 // per-frame biases of the two first layers: W[:, constant columns] . [freq(wrapped anchors) | individual code]
-void mf_nerf_torso::frame_bias(const float* frame_consts_host, float* bd, float* bt) const {
+void mf_nerf_torso::frame_bias(const float* frame_consts_host, float* bias) const {
     const int ncst = 42 + cfg.individual_dim;
     for (int o = 0; o < 32; ++o) {
         double a = 0, b = 0;
@@ -592,7 +509,7 @@ void mf_nerf_torso::frame_bias(const float* frame_consts_host, float* bd, float*
             a += (double)wd_const[(size_t)o * NCONST + i] * frame_consts_host[i];
             b += (double)wt_const[(size_t)o * NCONST + i] * frame_consts_host[i];
         }
-        bd[o] = (float)a; bt[o] = (float)b;
+        bias[o] = (float)a; bias[32 + o] = (float)b;
     }
 }
 
@@ -613,12 +530,9 @@ extern "C" int mf_nerf_torso_forward(mf_nerf_torso* h, const float* bg_coords, c
     hipStream_t s = (hipStream_t)stream;
     const int N = n_pixels, nb = (N + TW - 1) / TW, gb = (N + 255) / 256;
     FrameBias fb;
-    float *bd = fb.v, *bt = fb.v + 32;
-    h->frame_bias(frame_consts_host, bd, bt);
+    h->frame_bias(frame_consts_host, fb.v);
     if (h->fused)
-        return mf_nerf_torso_fused_launch(h->wf, bd, bt, h->emb, h->cfg.offsets, h->cfg.log2_per_level_scale, h->cfg.base_resolution, h->sampled(),
-                                          h->cfg.grid_size, bg_coords, h->cfg.torso_shrink, density_thresh, bg_color, bg_per_ray, bg_const, N, bg_out,
-                                          torso_alpha, deform, s);
+        return mf_nerf_torso_fused_launch(h->consts(), fb.v, h->sampled(), bg_coords, density_thresh, bg_color, bg_per_ray, bg_const, N, bg_out, torso_alpha, deform, s);
     hipLaunchKernelGGL(k_torso_bias, dim3(1), dim3(64), 0, s, fb, h->d1->bias, h->t1->bias);   // by value: no staging copy, no host sync
     hipLaunchKernelGGL(k_torso_prep, dim3((unsigned)(((int64_t)N * TX_C + 255) / 256)), dim3(256), 0, s, bg_coords, h->cfg.torso_shrink, N, h->xs,
                        h->TX->hi, h->TX->lo, h->TH->hi, h->TH->lo);
@@ -658,216 +572,11 @@ extern "C" int mf_nerf_torso_grid_update(mf_nerf_torso* h, const float* frame_co
     size_t unused = 0;
     int rc;
     if ((rc = mf_nerf_occupancy_shape("nerf_torso_grid_update", 1, h->cfg.grid_size, &unused))) return rc;
-    float bd[32], bt[32];
-    h->frame_bias(frame_consts_host, bd, bt);
-    if ((rc = mf_nerf_torso_grid_launch(h->wf, bd, bt, h->emb, h->cfg.offsets, h->cfg.log2_per_level_scale, h->cfg.base_resolution, h->cfg.torso_shrink,
-                                        h->cfg.grid_size, noise, decay, density_grid, raw_grid, xys_out, mean, h->grid_partials, (hipStream_t)stream)))
-        return rc;
+    float bias[64];
+    h->frame_bias(frame_consts_host, bias);
+    if ((rc = mf_nerf_torso_grid_launch(h->consts(), bias, noise, decay, density_grid, raw_grid, xys_out, mean, h->grid_partials, (hipStream_t)stream))) return rc;
     h->grid = density_grid;
     return MF_OK;
 }
 
 extern "C" void mf_nerf_torso_destroy(mf_nerf_torso* h) { delete h; }
-
-// =========================================================================================================================
-// Head render loop without host round trips: `run_cuda`'s inference branch (renderer.py:231-291) with the round control
-// (n_alive, n_step, step) kept in HBM.  The reference compacts `rays_alive` with a boolean mask and reads its length back on the
-// host every round; here k_loop_ctl / k_loop_compact (mf_nerf.hip) do both on the device, every launch has a fixed grid and
-// exits when its round has nothing to do.  A frame needs ~5 of the max_steps = 16 rounds the reference allows, so only as many rounds as the frames before
-// needed (+ 1) are enqueued as launches and ONE tail launch (k_loop_tail, mf_nerf_fused.hip) stands for the rest: it finds the loop ended, or runs the
-// remaining rounds itself -- no round is ever dropped, and nothing waits for the host.  The whole frame is capturable as one hipGraph.
-// =========================================================================================================================
-extern "C" int mf_near_far_from_aabb(const float* rays_o, const float* rays_d, const float* aabb, uint32_t n_rays, float min_near, float* nears,
-                                     float* fars, void* stream);
-extern "C" int mf_nerf_finish(float* image, float* depth, const float* weights_sum, const float* nears, const float* fars, const float* bg_color,
-                              int bg_per_ray, float bg_const, uint32_t n_rays, uint8_t* frame_u8, void* stream);
-int mf_nerf_loop_init(int* ctl, int N, int max_steps, int* alive, float* rays_t, float* nears, float* weights_sum, float* depth, float* image,
-                      float* amb_aud_sum, float* amb_eye_sum, float* unc_sum, hipStream_t s, const float* rays_o, const float* rays_d, const float* aabb, float min_near,
-                      float* fars);
-int mf_nerf_loop_round(int* ctl, int N, int max_steps, const int* alive_in, int* alive_out, float* rays_t, const float* rays_o, const float* rays_d,
-                       float bound, float dt_gamma, uint32_t cascades, uint32_t grid_size, const uint8_t* bitfield, const float* fars,
-                       float* xyzs, float* dirs, float* deltas, int phase, float T_thresh, const float* sigmas, const float* rgbs, const float* amb_aud,
-                       const float* amb_eye, const float* unc, float* weights_sum, float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum,
-                       float* unc_sum, hipStream_t s);
-
-struct mf_nerf_head {
-    mf_nerf_field* field = nullptr;
-    int cap = 0;
-    std::vector<void*> dev;
-    float *aabb, *nears, *fars, *rays_t, *xyzs, *dirs, *deltas, *sig, *rgb, *aa, *ae, *un, *wsum, *aasum, *aesum, *unsum;
-    int *alive[2], *ctl;
-    const float* eye_dev = nullptr;      // mf_nerf_head_set_eye: the eye feature stays on the device
-    const float* aabb_user = nullptr;    // mf_nerf_head_set_aabb: the caller's aabb_infer (device), read instead of `aabb` below
-    // round-count feedback: two words of pinned host memory the device posts to when a frame's loop ends ([0] rounds the frame ran, [1] the tail's error flag);
-    // read without a sync, so it tells about a frame that finished some calls ago
-    volatile int* fb = nullptr;
-    int ctl_rounds = 0;                  // the control block holds tail tickets for this many rounds
-    int hist[4] = {0, 0, 0, 0}, hist_n = 0;
-    int fixed_rounds = -1;               // mf_nerf_head_set_rounds: >= 0 pins the launched-round count (a captured graph is keyed on it), -1 = follow the feedback
-    ~mf_nerf_head() {
-        for (void* d : dev) (void)hipFree(d);
-        if (fb) (void)hipHostFree((void*)fb);
-    }
-};
-
-constexpr int HEAD_MAX_ROUNDS = 1024;     // max_steps accepted by mf_nerf_head_render (one round per step at least: renderer.py:270)
-
-// How many rounds of the next frame are enqueued as (march, field, composite) launches; the tail launch covers the rest.  The most rounds any of the last four
-// observed frames ran; every round (no tail) until a first frame has reported.  MF_NERF_TAIL_AFTER=<k> fixes it (tests, A/B: 0 = the tail runs the whole
-// loop, "off" = launches only, as before round 6).
-static int head_plan(mf_nerf_head* h, int max_steps) {
-    const char* e = getenv("MF_NERF_TAIL_AFTER");
-    if (e && *e) {
-        if (!strcmp(e, "off")) return max_steps;
-        const int k = atoi(e);
-        return k < 0 ? max_steps : (k < max_steps ? k : max_steps);
-    }
-    const int seen = h->fb ? h->fb[0] : 0;
-    if (seen > 0) { h->hist[h->hist_n & 3] = seen; h->hist_n++; }
-    if (h->hist_n == 0) return max_steps;
-    int m = 0;
-    for (int i = 0; i < 4; ++i) m = h->hist[i] > m ? h->hist[i] : m;
-    // no margin: a frame that needs more rounds than its predecessors runs them in the tail launch (and the next frames follow); a margin of one round was three
-    // launches per frame that found nothing to do (2 043 -> 2 068 frames/s)
-    return m < max_steps ? m : max_steps;
-}
-
-extern "C" int mf_nerf_head_create(mf_nerf_field* field, int max_rays, mf_nerf_head** out) {
-    MF_REQUIRE(field && out && max_rays > 0, "nerf_head_create: bad argument");
-    MF_REQUIRE(field->fused_w, "nerf_head_create: needs the fused field kernel (unset MF_NERF_FIELD=gemm)");
-    MF_REQUIRE(max_rays <= field->cap_batches * TW, "nerf_head_create: %d rays exceed the field's sample capacity %d", max_rays, field->cap_batches * TW);
-    *out = nullptr;
-    std::unique_ptr<mf_nerf_head> h(new mf_nerf_head());
-    h->field = field; h->cap = max_rays;
-    auto fm = [&](float** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(float))); h->dev.push_back(*p); return MF_OK; };
-    auto im = [&](int** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(int))); h->dev.push_back(*p); return MF_OK; };
-    const size_t N = (size_t)max_rays;
-    int rc;
-    if ((rc = fm(&h->aabb, 6)) || (rc = fm(&h->nears, N)) || (rc = fm(&h->fars, N)) || (rc = fm(&h->rays_t, N)) || (rc = fm(&h->xyzs, 3 * N)) ||
-        (rc = fm(&h->dirs, 3 * N)) || (rc = fm(&h->deltas, 2 * N)) || (rc = fm(&h->sig, N)) || (rc = fm(&h->rgb, 3 * N)) || (rc = fm(&h->aa, N)) ||
-        (rc = fm(&h->ae, N)) || (rc = fm(&h->un, N)) || (rc = fm(&h->wsum, N)) || (rc = fm(&h->aasum, N)) || (rc = fm(&h->aesum, N)) ||
-        (rc = fm(&h->unsum, N)) || (rc = im(&h->alive[0], N)) || (rc = im(&h->alive[1], N)) ||
-        (rc = im(&h->ctl, (size_t)LOOP_CTL_TAIL + (size_t)LOOP_TAIL_ARRAYS * (HEAD_MAX_ROUNDS + 1))))
-        return rc;
-    h->ctl_rounds = HEAD_MAX_ROUNDS;
-    MF_HIP(hipMemset(h->ctl, 0, ((size_t)LOOP_CTL_TAIL + (size_t)LOOP_TAIL_ARRAYS * (HEAD_MAX_ROUNDS + 1)) * sizeof(int)));
-    {
-        int* fb = nullptr;
-        MF_HIP(hipHostMalloc((void**)&fb, 4 * sizeof(int), hipHostMallocMapped));
-        fb[0] = fb[1] = fb[2] = fb[3] = 0;
-        h->fb = fb;
-        void* fb_dev = nullptr;
-        MF_HIP(hipHostGetDevicePointer(&fb_dev, fb, 0));
-        MF_HIP(hipMemcpy(h->ctl + LOOP_CTL_FB, &fb_dev, sizeof(fb_dev), hipMemcpyHostToDevice));
-    }
-    const float b = field->cfg.bound;
-    const float aabb[6] = {-b, -b / 2, -b, b, b / 2, b};                                    // aabb_infer, renderer.py:86-89
-    MF_HIP(hipMemcpy(h->aabb, aabb, sizeof(aabb), hipMemcpyHostToDevice));
-    *out = h.release();
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_render(mf_nerf_head* h, const float* rays_o, const float* rays_d, int n_rays, const uint8_t* density_bitfield, int cascades,
-                                   int grid_size, float min_near, float dt_gamma, int max_steps, float T_thresh, float density_scale, const float* enc_a,
-                                   const float* ind_code, float eye, const float* bg_color, int bg_per_ray, float bg_const, float* image, float* depth,
-                                   float* weights_sum, uint8_t* frame_u8, void* stream) {
-    MF_REQUIRE(h && rays_o && rays_d && density_bitfield && enc_a && image && depth, "nerf_head_render: null argument");
-    MF_REQUIRE(n_rays > 0 && n_rays <= h->cap && max_steps > 0 && max_steps <= HEAD_MAX_ROUNDS, "nerf_head_render: n_rays=%d (capacity %d) max_steps=%d", n_rays, h->cap, max_steps);
-    hipStream_t s = (hipStream_t)stream;
-    mf_nerf_field* f = h->field;
-    const mf_nerf_field_config& c = f->cfg;
-    MF_REQUIRE(c.individual_dim == 0 || ind_code, "nerf_head_render: the field was built with an individual code");
-    const int N = n_rays;
-    float* ws = weights_sum ? weights_sum : h->wsum;
-    int rc;
-    // near / far (raymarching.cu:92-145) inside the loop's init launch
-    if ((rc = mf_nerf_loop_init(h->ctl, N, max_steps, h->alive[0], h->rays_t, h->nears, ws, depth, image, h->aasum, h->aesum, h->unsum, s, rays_o, rays_d,
-                                h->aabb_user ? h->aabb_user : h->aabb, min_near, h->fars)))
-        return rc;
-    const bool x3 = f->precision == MF_PREC_BF16X3;
-    // at least one sample per alive ray and round, so max_steps rounds always suffice (step += n_step >= 1, renderer.py:270)
-    MF_REQUIRE(!h->fb || h->fb[1] == 0, "nerf_head_render: the tail kernel of an earlier frame gave up waiting for a round (control block error flag)");
-    const int rounds = h->fixed_rounds >= 0 ? (h->fixed_rounds < max_steps ? h->fixed_rounds : max_steps) : head_plan(h, max_steps);
-    const char* skip_env = getenv("MF_NERF_SKIP_EMPTY");                       // "0": evaluate every slot as the reference does (A/B)
-    const bool skip_empty = !(skip_env && skip_env[0] == '0');
-    for (int it = 0; it < rounds; ++it) {
-        int* a_in = h->alive[it & 1];
-        int* a_out = h->alive[(it + 1) & 1];
-        if ((rc = mf_nerf_loop_round(h->ctl, N, max_steps, a_in, a_out, h->rays_t, rays_o, rays_d, c.bound, dt_gamma, cascades, grid_size, density_bitfield,
-                                     h->fars, h->xyzs, h->dirs, h->deltas, 0, T_thresh, nullptr, nullptr, nullptr, nullptr, nullptr, ws, depth, image,
-                                     h->aasum, h->aesum, h->unsum, s)))
-            return rc;
-        if ((rc = mf_nerf_fused_launch(f->fused_w, x3, f->emb, c.offsets, c.log2_per_level_scale, c.base_resolution, c.bound, h->xyzs, h->dirs, enc_a, ind_code,
-                                       c.individual_dim, eye, c.exp_eye, N, h->sig, h->rgb, h->aa, h->ae, h->un, s, h->ctl + 3, density_scale, h->eye_dev,
-                                       skip_empty ? h->deltas : nullptr)))
-            return rc;
-        if ((rc = mf_nerf_loop_round(h->ctl, N, max_steps, a_in, a_out, h->rays_t, rays_o, rays_d, c.bound, dt_gamma, cascades, grid_size, density_bitfield,
-                                     h->fars, h->xyzs, h->dirs, h->deltas, 1, T_thresh, h->sig, h->rgb, h->aa, h->ae, h->un, ws, depth, image,
-                                     h->aasum, h->aesum, h->unsum, s)))
-            return rc;
-    }
-    // at least one sample per alive ray and round, so max_steps rounds always suffice (step += n_step >= 1, renderer.py:270): with every round enqueued there is no tail
-    if (rounds < max_steps &&
-        (rc = mf_nerf_tail_launch(f->fused_w, x3, f->emb, c.offsets, c.log2_per_level_scale, c.base_resolution, c.bound, enc_a, ind_code, c.individual_dim, eye, c.exp_eye,
-                                  density_scale, h->eye_dev, h->sig, h->rgb, h->aa, h->ae, h->un, h->ctl, N, max_steps, rounds, T_thresh, dt_gamma, cascades, grid_size,
-                                  h->alive[0], h->alive[1], h->rays_t, rays_o, rays_d, h->fars, density_bitfield, h->xyzs, h->dirs, h->deltas, ws, depth, image,
-                                  h->aasum, h->aesum, h->unsum, s)))
-        return rc;
-    if (bg_per_ray < 0) return MF_OK;                                                       // finished later by mf_nerf_head_finish
-    return mf_nerf_finish(image, depth, ws, h->nears, h->fars, bg_color, bg_per_ray, bg_const, N, frame_u8, stream);
-}
-
-extern "C" int mf_nerf_head_finish(mf_nerf_head* h, int n_rays, const float* bg_color, int bg_per_ray, float bg_const, float* image, float* depth,
-                                   const float* weights_sum, uint8_t* frame_u8, void* stream) {
-    MF_REQUIRE(h && image && depth && n_rays > 0 && n_rays <= h->cap && bg_per_ray >= 0, "nerf_head_finish: bad argument");
-    return mf_nerf_finish(image, depth, weights_sum ? weights_sum : h->wsum, h->nears, h->fars, bg_color, bg_per_ray, bg_const, n_rays, frame_u8, stream);
-}
-
-extern "C" int mf_nerf_head_set_eye(mf_nerf_head* h, const float* eye_dev) {
-    MF_REQUIRE(h, "nerf_head_set_eye: null handle");
-    h->eye_dev = eye_dev;
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_set_aabb(mf_nerf_head* h, const float* aabb_dev) {
-    MF_REQUIRE(h, "nerf_head_set_aabb: null handle");
-    h->aabb_user = aabb_dev;
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_plan_rounds(mf_nerf_head* h, int max_steps, int* rounds) {
-    MF_REQUIRE(h && rounds && max_steps > 0 && max_steps <= HEAD_MAX_ROUNDS, "nerf_head_plan_rounds: bad argument");
-    *rounds = head_plan(h, max_steps);
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_set_rounds(mf_nerf_head* h, int rounds) {
-    MF_REQUIRE(h && rounds >= -1 && rounds <= HEAD_MAX_ROUNDS, "nerf_head_set_rounds: bad argument");
-    h->fixed_rounds = rounds;
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_last_rounds(mf_nerf_head* h, int* rounds, int* error_flag) {
-    MF_REQUIRE(h && h->fb, "nerf_head_last_rounds: null handle");
-    if (rounds) *rounds = h->fb[0];
-    if (error_flag) *error_flag = h->fb[1];
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_ctl_snapshot(mf_nerf_head* h, int* out, int n_ints) {
-    MF_REQUIRE(h && out && n_ints > 0 && (size_t)n_ints <= (size_t)LOOP_CTL_TAIL + (size_t)LOOP_TAIL_ARRAYS * (HEAD_MAX_ROUNDS + 1), "nerf_head_ctl_snapshot: bad argument");
-    MF_HIP(hipMemcpy(out, h->ctl, (size_t)n_ints * sizeof(int), hipMemcpyDeviceToHost));
-    return MF_OK;
-}
-
-extern "C" int mf_nerf_head_sums(mf_nerf_head* h, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream) {
-    MF_REQUIRE(h && n_rays > 0 && n_rays <= h->cap, "nerf_head_sums: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)n_rays * sizeof(float);
-    if (ambient_aud) MF_HIP(hipMemcpyAsync(ambient_aud, h->aasum, bytes, hipMemcpyDeviceToDevice, s));
-    if (ambient_eye) MF_HIP(hipMemcpyAsync(ambient_eye, h->aesum, bytes, hipMemcpyDeviceToDevice, s));
-    if (uncertainty) MF_HIP(hipMemcpyAsync(uncertainty, h->unsum, bytes, hipMemcpyDeviceToDevice, s));
-    return MF_OK;
-}
-
-extern "C" void mf_nerf_head_destroy(mf_nerf_head* h) { delete h; }

@@ -290,36 +290,33 @@ int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_
     return MF_OK;
 }
 
-int mf_nerf_occupancy_launch(const bf16_t* packed, bool x3, const float* const emb[3], const int* offsets, float log2_pls, int base_res, float field_bound,
-                             int has_eye, float* density_grid, uint8_t* density_bitfield, int cascades, int grid_size, float bound, const float* enc_a, float eye,
-                             float density_scale, float decay, float density_thresh, const float* noise, float* tmp_grid, float* xyzs_out, double* mean_density,
-                             double* partials, hipStream_t s) {
+int mf_nerf_occupancy_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const NerfGridBufs& g, int cascades, int grid_size, float bound, float decay,
+                             float density_thresh, const float* noise, hipStream_t s) {
     MF_REQUIRE(bound > 0.f, "nerf_density_grid_update: bound must be positive");
     const uint32_t H = (uint32_t)grid_size, log2_H3 = grid_size == 32 ? 15u : (grid_size == 64 ? 18u : 21u);
     const int cells = cascades << log2_H3;
     FusedArgs a{};
-    fused_args(a, packed, emb, offsets, log2_pls, base_res, field_bound, nullptr, nullptr, enc_a, nullptr, 0, eye, has_eye, cells, tmp_grid, nullptr, nullptr, nullptr, nullptr,
-               nullptr, density_scale, nullptr, nullptr);
+    int rc;
+    if ((rc = fused_args(a, f, in, nullptr, nullptr, cells, NerfFieldOut{g.tmp_grid, nullptr, nullptr, nullptr, nullptr}))) return rc;
     SweepArgs w{};
-    w.H = H; w.log2_H3 = log2_H3; w.inv_hm1 = 1.0f / (float)(H - 1); w.noise = noise; w.xyzs_out = xyzs_out;
+    w.H = H; w.log2_H3 = log2_H3; w.inv_hm1 = 1.0f / (float)(H - 1); w.noise = noise; w.xyzs_out = g.xyzs_out;
     for (int c = 0; c < cascades; ++c) {
         // `bound = min(2 ** cas, self.bound)`, `half_grid_size = bound / self.grid_size`: Python floats (doubles)
         const double bc = std::min((double)(1 << c), (double)bound), half = bc / (double)grid_size;
         w.scale[c] = (float)(bc - half);
         w.half[c] = (float)half;
     }
-    const size_t lds = (size_t)NFRAG * (x3 ? 2 : 1) * 1024;
+    const size_t lds = (size_t)NFRAG * (f.x3 ? 2 : 1) * 1024;
     static bool attr_done[2] = {false, false};
-    int rc;
-    if ((rc = x3 ? fused_lds_attr(k_density_sweep<true>, attr_done[1], lds) : fused_lds_attr(k_density_sweep<false>, attr_done[0], lds))) return rc;
+    if ((rc = f.x3 ? fused_lds_attr(k_density_sweep<true>, attr_done[1], lds) : fused_lds_attr(k_density_sweep<false>, attr_done[0], lds))) return rc;
     const int grid = std::min(a.ntiles, 256);
-    if (x3) hipLaunchKernelGGL(k_density_sweep<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a, w);
+    if (f.x3) hipLaunchKernelGGL(k_density_sweep<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a, w);
     else hipLaunchKernelGGL(k_density_sweep<false>, dim3(grid), dim3(NWAVE * 64), lds, s, a, w);
     MF_HIP(hipGetLastError());
     const unsigned nwg = (unsigned)(cells / OCC_CELLS);
-    hipLaunchKernelGGL(k_dilate_ema, dim3(nwg), dim3(OCC_T), 0, s, tmp_grid, density_grid, H, log2_H3, decay, partials);
+    hipLaunchKernelGGL(k_dilate_ema, dim3(nwg), dim3(OCC_T), 0, s, g.tmp_grid, g.density_grid, H, log2_H3, decay, g.partials);
     MF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_reduce_pack, dim3(nwg), dim3(OCC_T), 0, s, density_grid, partials, nwg, (double)cells, density_thresh, density_bitfield, mean_density);
+    hipLaunchKernelGGL(k_reduce_pack, dim3(nwg), dim3(OCC_T), 0, s, g.density_grid, g.partials, nwg, (double)cells, density_thresh, g.bitfield, g.mean_density);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

@@ -11,7 +11,7 @@
 // Arithmetic is plain fp32 (one fused multiply-add per weight; even and odd inputs of a row in two partial sums) in BOTH precision modes: closer to the reference's fp32
 // nets than the bf16x3 GEMMs were.  Everything outside the dense layers rounds as written (contraction off), so the frequency
 // features, the warp and the grid features are bit-identical to mf_freq_encode_forward / mf_grid_encode_forward.
-#include "mf_common.h"
+#include "mf_nerf_host.h"
 #include "mf_nerf_grid.h"
 #include <cmath>
 
@@ -296,30 +296,26 @@ __global__ void k_torso_grid_mean(const double* __restrict__ partials, int n_par
     *mean_out = (float)(acc / cells);
 }
 
-void torso_args(TorsoFusedArgs& a, const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
-                float shrink, int G, int N) {
-    a.w = w; a.emb = emb;
-    for (int i = 0; i < HID; ++i) { a.bias_d[i] = bias_d[i]; a.bias_t[i] = bias_t[i]; }
-    for (int l = 0; l < NLEV; ++l) {
-        const float scale = exp2f((float)l * log2_pls) * (float)base_res - 1.0f;              // gridencoder.cu:123
-        a.scale[l] = scale;
-        a.resolution[l] = (uint32_t)std::ceil(scale) + 1;                                     // gridencoder.cu:124
-        a.offset[l] = (uint32_t)offsets_host[l];
-        a.hashmap_size[l] = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
-    }
-    a.shrink = shrink; a.G = G; a.N = N;
+int torso_args(TorsoFusedArgs& a, const NerfTorsoConsts& t, const float* bias, int N) {
+    a.w = t.w; a.emb = t.emb;
+    for (int i = 0; i < HID; ++i) { a.bias_d[i] = bias[i]; a.bias_t[i] = bias[HID + i]; }
+    GridLevels lv;
+    if (const int rc = mf_grid_levels(lv, t.offsets, NLEV, t.log2_pls, (uint32_t)t.base_res)) return rc;
+    for (int l = 0; l < NLEV; ++l) { a.scale[l] = lv.scale[l]; a.resolution[l] = lv.resolution[l]; a.offset[l] = lv.offset[l]; a.hashmap_size[l] = lv.hashmap_size[l]; }
+    a.shrink = t.shrink; a.G = t.G; a.N = N;
+    return MF_OK;
 }
 
 }  // namespace
 
 int mf_nerf_torso_fused_weight_count() { return W_TOTAL; }
 
-// w: device table laid out as W_D1 .. W_T3 above; bias_d / bias_t: host, 32 each; offsets_host: 17 level offsets
-int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls,
-                               int base_res, const float* density, int G, const float* bg_coords, float shrink, float thresh, const float* bg,
+// t.w: device table laid out as W_D1 .. W_T3 above
+int mf_nerf_torso_fused_launch(const NerfTorsoConsts& t, const float* bias, const float* density, const float* bg_coords, float thresh, const float* bg,
                                int bg_per_ray, float bg_const, int N, float* out, float* alpha_out, float* deform, hipStream_t s) {
     TorsoFusedArgs a{};
-    torso_args(a, w, bias_d, bias_t, emb, offsets_host, log2_pls, base_res, shrink, G, N);
+    int rc;
+    if ((rc = torso_args(a, t, bias, N))) return rc;
     a.bg_coords = bg_coords; a.density = density; a.bg = bg;
     a.thresh = thresh; a.bg_const = bg_const; a.bg_per_ray = bg_per_ray;
     a.out = out; a.alpha_out = alpha_out; a.deform = deform;
@@ -329,13 +325,13 @@ int mf_nerf_torso_fused_launch(const float* w, const float* bias_d, const float*
 }
 
 // The torso grid's rebuild (mf_nerf_torso_grid_update, mf_nerf_net.hip, where the handle is defined): sweep, dilate + EMA, mean.  The served sizes were accepted by
-// mf_nerf_occupancy_shape; partials: G^2 / 256 doubles.
-int mf_nerf_torso_grid_launch(const float* w, const float* bias_d, const float* bias_t, const float* emb, const int* offsets_host, float log2_pls, int base_res,
-                              float shrink, int G, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out, float* mean,
-                              double* partials, hipStream_t s) {
-    const int cells = G * G;
+// mf_nerf_occupancy_shape.
+int mf_nerf_torso_grid_launch(const NerfTorsoConsts& t, const float* bias, const float* noise, float decay, float* density_grid, float* raw_grid, float* xys_out,
+                              float* mean, double* partials, hipStream_t s) {
+    const int G = t.G, cells = G * G;
     TorsoFusedArgs a{};
-    torso_args(a, w, bias_d, bias_t, emb, offsets_host, log2_pls, base_res, shrink, G, cells);
+    int rc;
+    if ((rc = torso_args(a, t, bias, cells))) return rc;
     a.alpha_out = raw_grid; a.noise = noise; a.xys_out = xys_out;
     // `half_grid_size = 1 / self.grid_size` and `1 - half_grid_size` are Python floats (doubles), rounded when they meet the float32 tensor
     const double half = 1.0 / (double)G;
