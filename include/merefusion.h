@@ -560,6 +560,49 @@ int mf_nerf_head_ctl_snapshot(mf_nerf_head* h, int* out, int n_ints);
 int mf_nerf_head_sums(mf_nerf_head* h, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream);
 void mf_nerf_head_destroy(mf_nerf_head* h);
 
+/* ---- several head frames in one device loop ------------------------------------------------------------------
+ * The F frames of a serving step (4 per session) rendered by ONE chain of launches: init, the rounds of (march, field, composite) and the finish carry a
+ * frame index in the grid, so the chain's launch latency is paid once and the late rounds, which hold few rays per frame, are filled with other frames' rays.
+ * Every frame keeps its own round control (n_alive, n_step, step: its own control block), so the per-ray and per-sample arithmetic is mf_nerf_head_render's:
+ * a frame rendered in a batch is the same bits as the same frame rendered alone.
+ * All frames of a call share the field, the bitfield, the ray count and the scalar render parameters; what a descriptor holds is per frame. */
+typedef struct mf_nerf_frame_desc {
+    const float *rays_o, *rays_d;      /* device, [n_rays, 3] */
+    const float *enc_a, *ind_code;     /* device, [32] / [individual_dim] or NULL */
+    const float* eye_dev;              /* device, the eye feature; NULL: `eye` below */
+    float eye;
+    const float* bg_color;             /* bg_color / bg_per_ray / bg_const as mf_nerf_head_render; bg_per_ray < 0: the frame is left unfinished */
+    int bg_per_ray;
+    float bg_const;
+    float *image, *depth, *weights_sum;   /* outputs, device: [n_rays, 3], [n_rays], [n_rays] or NULL */
+    uint8_t* frame_u8;                 /* [n_rays, 3] or NULL */
+} mf_nerf_frame_desc;
+typedef struct mf_nerf_head_batch mf_nerf_head_batch;
+/* Scratch for up to max_frames (1..64) frames of up to max_rays rays over `field`.  The handle owns, per frame slot, what a mf_nerf_head owns for its one
+ * frame: the per-ray and per-sample buffers, two alive lists, one control block and two pinned feedback words -- 96 bytes per ray and slot, 25 MB per
+ * 512 x 512 slot (1.6 GB for 64 of them: size max_frames to the serving step) -- and a ring of four frame tables (pinned staging + device). */
+int mf_nerf_head_batch_create(mf_nerf_field* field, int max_rays, int max_frames, mf_nerf_head_batch** out);
+/* frames: HOST array of n_frames descriptors, read before the call returns; the table reaches the device by an asynchronous copy from pinned memory on
+ * `stream` (no host synchronisation; a call waits only if the four calls before it are all still in flight).  aabb_dev: device fp32 [6] as
+ * mf_nerf_head_set_aabb takes, or NULL for the box from the field's bound.  Frame i uses slot i.  Rounds enqueued as launches: the most any frame of the
+ * batches observed so far needed (the slots' feedback words, read without a sync; every round until a first batch has reported; MF_NERF_TAIL_AFTER
+ * overrides), then one tail launch per frame on that frame's control block, which in the usual case reads three words and leaves.  MF_NERF_MARCH and
+ * MF_NERF_SKIP_EMPTY apply as in mf_nerf_head_render.  Not capturable in a hipGraph.
+ * A slot whose tail kernel once gave up waiting (its error flag, see mf_nerf_head_batch_last_rounds) refuses every later call that uses the slot, i.e. every call
+ * with n_frames above its index, before anything is launched; as with mf_nerf_head the flag is cleared only by a later frame of that slot, so the way out is to
+ * destroy the handle and create a new one. */
+int mf_nerf_head_batch_render(mf_nerf_head_batch* h, const mf_nerf_frame_desc* frames, int n_frames, int n_rays, const uint8_t* density_bitfield,
+                              int cascades, int grid_size, float min_near, float dt_gamma, int max_steps, float T_thresh, float density_scale,
+                              const float* aabb_dev, void* stream);
+/* mf_nerf_head_finish for the frame rendered last in slot `frame` with bg_per_ray < 0. */
+int mf_nerf_head_batch_finish(mf_nerf_head_batch* h, int frame, int n_rays, const float* bg_color, int bg_per_ray, float bg_const, float* image,
+                              float* depth, const float* weights_sum, uint8_t* frame_u8, void* stream);
+/* mf_nerf_head_sums for the frame rendered last in slot `frame`. */
+int mf_nerf_head_batch_sums(mf_nerf_head_batch* h, int frame, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream);
+/* rounds / error_flags: HOST int [max_frames] (either may be NULL): per slot, what mf_nerf_head_last_rounds reports for a head. */
+int mf_nerf_head_batch_last_rounds(mf_nerf_head_batch* h, int* rounds, int* error_flags);
+void mf_nerf_head_batch_destroy(mf_nerf_head_batch* h);
+
 /* ---- ER-NeRF torso branch --------------------------------------------------------------------- */
 typedef struct mf_nerf_torso mf_nerf_torso;
 typedef struct mf_nerf_torso_config {

@@ -43,6 +43,13 @@ class MfNerfTorsoConfig(C.Structure):
                 ("log2_per_level_scale", C.c_float), ("offsets", C.c_int * 33), ("individual_dim", C.c_int), ("grid_size", C.c_int)]
 
 
+class MfNerfFrameDesc(C.Structure):
+    """mf_nerf_frame_desc: one frame of mf_nerf_head_batch_render"""
+    _fields_ = [("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("enc_a", C.c_void_p), ("ind_code", C.c_void_p), ("eye_dev", C.c_void_p), ("eye", C.c_float),
+                ("bg_color", C.c_void_p), ("bg_per_ray", C.c_int), ("bg_const", C.c_float), ("image", C.c_void_p), ("depth", C.c_void_p),
+                ("weights_sum", C.c_void_p), ("frame_u8", C.c_void_p)]
+
+
 class MfVaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("n_blocks", C.c_int),
                 ("block_out_channels", C.c_int * 4), ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int),
@@ -207,6 +214,13 @@ SIGNATURES = {
     "mf_nerf_head_last_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mf_nerf_head_ctl_snapshot": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "mf_nerf_head_destroy": (None, [C.c_void_p]),
+    "mf_nerf_head_batch_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mf_nerf_head_batch_render": (C.c_int, [C.c_void_p, C.POINTER(MfNerfFrameDesc), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                            C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "mf_nerf_head_batch_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 5),
+    "mf_nerf_head_batch_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "mf_nerf_head_batch_last_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mf_nerf_head_batch_destroy": (None, [C.c_void_p]),
     "mf_nerf_torso_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mf_nerf_torso_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 4),
     "mf_nerf_torso_set_grid": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -58,11 +58,12 @@ constexpr int LOOP_MAX_STEP = 8;                 // renderer.py:256 caps n_step 
 // FAST: one cascade and a power-of-two grid.  Then level == 0 for every position (both mip_from_* clamp to [0, C - 1]), so the mip bound and
 // its reciprocal leave the loop, and 0.5 * v * H is a power-of-two scaling -- exact in float as in the reference's double -- so the
 // double round trip goes too.  Same bits, about a third fewer instructions on the dependent chain.
+// (the body is a device function: k_loop_march runs it for the one frame of mf_nerf_head_render, k_loop_march_batch for the frame blockIdx.y names)
 template <bool FAST>
-__global__ __launch_bounds__(NT) void k_loop_march(const int* __restrict__ ctl, const int* __restrict__ rays_alive, const float* __restrict__ rays_t,
-                                                   const float* __restrict__ rays_o, const float* __restrict__ rays_d, float bound, float dt_gamma,
-                                                   uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t* __restrict__ grid,
-                                                   const float* __restrict__ fars, float* xyzs, float* dirs, float* deltas) {
+__device__ __forceinline__ void loop_march_block(const int* __restrict__ ctl, const int* __restrict__ rays_alive, const float* __restrict__ rays_t,
+                                                 const float* __restrict__ rays_o, const float* __restrict__ rays_d, float bound, float dt_gamma,
+                                                 uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t* __restrict__ grid,
+                                                 const float* __restrict__ fars, float* xyzs, float* dirs, float* deltas) {
     const uint32_t n_alive = (uint32_t)ctl[0], n_step = (uint32_t)ctl[1];
     const uint32_t base = blockIdx.x * NT;
     if (base >= n_alive || n_step == 0) return;
@@ -193,6 +194,21 @@ __global__ __launch_bounds__(NT) void k_loop_march(const int* __restrict__ ctl, 
         pt[0] = dt; pt[1] = t1;
     }
 }
+template <bool FAST>
+__global__ __launch_bounds__(NT) void k_loop_march(const int* __restrict__ ctl, const int* __restrict__ rays_alive, const float* __restrict__ rays_t,
+                                                   const float* __restrict__ rays_o, const float* __restrict__ rays_d, float bound, float dt_gamma,
+                                                   uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t* __restrict__ grid,
+                                                   const float* __restrict__ fars, float* xyzs, float* dirs, float* deltas) {
+    loop_march_block<FAST>(ctl, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, fars, xyzs, dirs, deltas);
+}
+// grid (blocks(N), n_frames): every block reads its frame's entry of the table and only that frame's control block; `odd`: the round reads alive1
+template <bool FAST>
+__global__ __launch_bounds__(NT) void k_loop_march_batch(const LoopFrame* __restrict__ frames, int odd, float bound, float dt_gamma, uint32_t max_steps,
+                                                         uint32_t C, uint32_t H, const uint8_t* __restrict__ grid) {
+    const LoopFrame f = frames[blockIdx.y];
+    loop_march_block<FAST>(f.ctl, odd ? f.alive1 : f.alive0, f.rays_t, f.rays_o, f.rays_d, bound, dt_gamma, max_steps, C, H, grid, f.fars, f.xyzs, f.dirs,
+                           f.deltas);
+}
 
 // kernel_composite_rays_triplane, raymarching.cu:2142-2249 (composite_ray: mf_nerf_march.h)
 __global__ __launch_bounds__(NT) void k_composite_rays_triplane(uint32_t n_alive, uint32_t n_step, float T_thresh, int* rays_alive,
@@ -311,9 +327,9 @@ __global__ __launch_bounds__(NT) void k_freq_encode(const float* __restrict__ in
 
 // tail of run_cuda (renderer.py:275-280) + the uint8 conversion of nerfreal.py:111: image = clamp(image + (1 - w) * bg, 0, 1),
 // depth = clamp(depth - near, 0) / (far - near); frame = uint8(image * 255) (numpy astype truncates)
-__global__ __launch_bounds__(NT) void k_nerf_finish(float* image, float* depth, const float* __restrict__ weights_sum,
-                                                    const float* __restrict__ nears, const float* __restrict__ fars,
-                                                    const float* __restrict__ bg, int bg_per_ray, float bg_const, uint32_t N, uint8_t* frame) {
+__device__ __forceinline__ void nerf_finish_block(float* image, float* depth, const float* __restrict__ weights_sum,
+                                                  const float* __restrict__ nears, const float* __restrict__ fars,
+                                                  const float* __restrict__ bg, int bg_per_ray, float bg_const, uint32_t N, uint8_t* frame) {
     const uint32_t n = threadIdx.x + blockIdx.x * NT;
     if (n >= N) return;
     const float t = 1 - weights_sum[n];
@@ -325,6 +341,17 @@ __global__ __launch_bounds__(NT) void k_nerf_finish(float* image, float* depth, 
         if (frame) frame[3 * n + k] = (uint8_t)(v * 255.f);
     }
     depth[n] = fmaxf(depth[n] - nears[n], 0.f) / (fars[n] - nears[n]);
+}
+__global__ __launch_bounds__(NT) void k_nerf_finish(float* image, float* depth, const float* __restrict__ weights_sum,
+                                                    const float* __restrict__ nears, const float* __restrict__ fars,
+                                                    const float* __restrict__ bg, int bg_per_ray, float bg_const, uint32_t N, uint8_t* frame) {
+    nerf_finish_block(image, depth, weights_sum, nears, fars, bg, bg_per_ray, bg_const, N, frame);
+}
+// grid (blocks(N), n_frames); a frame with bg_per_ray < 0 stays unfinished (mf_nerf_head_batch_finish closes it later)
+__global__ __launch_bounds__(NT) void k_nerf_finish_batch(const LoopFrame* __restrict__ frames, uint32_t N) {
+    const LoopFrame f = frames[blockIdx.y];
+    if (f.bg_per_ray < 0) return;
+    nerf_finish_block(f.image, f.depth, f.wsum, f.nears, f.fars, f.bg, f.bg_per_ray, f.bg_const, N, f.frame_u8);
 }
 
 // a24, utils.py:1208-1216 + nerfreal.py:111: the rendered [h, w] frame resized to the GUI's [H, W] -- image bilinear with half-pixel centres
@@ -357,9 +384,9 @@ __global__ __launch_bounds__(NT) void k_nerf_resize(const float* __restrict__ im
 // ---- device-controlled render loop (no host sync between rounds) ---------------------------------------------------------
 // control block `ctl` and the head of a round (loop_next_round): mf_nerf_march.h
 // rays_o != null: near / far of every ray (k_near_far_from_aabb's arithmetic) are computed and stored here too -- one launch less at the head of a frame
-__global__ void k_loop_init(int* ctl, int N, int max_steps, int* alive, float* rays_t, float* nears, float* weights_sum, float* depth,
-                            float* image, float* amb_aud_sum, float* amb_eye_sum, float* unc_sum, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                            const float* __restrict__ aabb, float min_near, float* fars) {
+__device__ __forceinline__ void loop_init_block(int* ctl, int N, int max_steps, int* alive, float* rays_t, float* nears, float* weights_sum, float* depth,
+                                                float* image, float* amb_aud_sum, float* amb_eye_sum, float* unc_sum, const float* __restrict__ rays_o,
+                                                const float* __restrict__ rays_d, const float* __restrict__ aabb, float min_near, float* fars) {
     const int n = blockIdx.x * NT + threadIdx.x;
     if (n == 0) { ctl[4] = 0; ctl[5] = 0; ctl[LOOP_CTL_ROUNDS] = 0; ctl[LOOP_CTL_ERR] = 0; loop_next_round(ctl, N, 0, N, max_steps); }
     // the tail kernel's tickets (take | finished | survivors | ready, one entry per round: mf_nerf_fused.hip k_loop_tail)
@@ -377,6 +404,17 @@ __global__ void k_loop_init(int* ctl, int N, int max_steps, int* alive, float* r
     weights_sum[n] = depth[n] = amb_aud_sum[n] = amb_eye_sum[n] = unc_sum[n] = 0.f;
     image[3 * n] = image[3 * n + 1] = image[3 * n + 2] = 0.f;
 }
+__global__ void k_loop_init(int* ctl, int N, int max_steps, int* alive, float* rays_t, float* nears, float* weights_sum, float* depth,
+                            float* image, float* amb_aud_sum, float* amb_eye_sum, float* unc_sum, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                            const float* __restrict__ aabb, float min_near, float* fars) {
+    loop_init_block(ctl, N, max_steps, alive, rays_t, nears, weights_sum, depth, image, amb_aud_sum, amb_eye_sum, unc_sum, rays_o, rays_d, aabb, min_near, fars);
+}
+// grid (blocks(N), n_frames)
+__global__ void k_loop_init_batch(const LoopFrame* __restrict__ frames, int N, int max_steps, const float* __restrict__ aabb, float min_near) {
+    const LoopFrame f = frames[blockIdx.y];
+    loop_init_block(f.ctl, N, max_steps, f.alive0, f.rays_t, f.nears, f.wsum, f.depth, f.image, f.aasum, f.aesum, f.unsum, f.rays_o, f.rays_d, aabb, min_near,
+                    f.fars);
+}
 // tail of a round in one launch: composite (raymarching.cu:2142-2249), `rays_alive = rays_alive[rays_alive >= 0]` (renderer.py:266) as a
 // wave-aggregated append (the order of the survivors is not kept: rays are independent, only their slot changes), and -- by the last
 // block to finish -- the head of the next round.
@@ -385,11 +423,11 @@ __global__ void k_loop_init(int* ctl, int N, int max_steps, int* alive, float* r
 #endif
 constexpr int CT = MF_NERF_CT;           // composite block: one contended 64-bit atomic per 512 rays (with the fence in front of that atomic 1 024 measured best; without it
                                          // 512: 0.487 -> 0.481 ms per frame, 256: 0.485)
-__global__ __launch_bounds__(CT) void k_loop_composite(int* ctl, int N, int max_steps, float T_thresh, const int* __restrict__ alive_in, int* alive_out,
-                                                       float* rays_t, const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                       const float* __restrict__ deltas, const float* __restrict__ ambs_aud,
-                                                       const float* __restrict__ ambs_eye, const float* __restrict__ uncertainties, float* weights_sum,
-                                                       float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum, float* uncertainty_sum) {
+__device__ __forceinline__ void loop_composite_block(int* ctl, int N, int max_steps, float T_thresh, const int* __restrict__ alive_in, int* alive_out,
+                                                     float* rays_t, const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                     const float* __restrict__ deltas, const float* __restrict__ ambs_aud,
+                                                     const float* __restrict__ ambs_eye, const float* __restrict__ uncertainties, float* weights_sum,
+                                                     float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum, float* uncertainty_sum) {
     const uint32_t n_alive = (uint32_t)ctl[0], n_step = (uint32_t)ctl[1];
     const uint32_t base = blockIdx.x * CT;
     if (n_step == 0 || base >= n_alive) return;     // ended loop: ctl stays as it is; blocks past the alive rays take no part
@@ -474,6 +512,20 @@ __global__ __launch_bounds__(CT) void k_loop_composite(int* ctl, int N, int max_
     if (keep) alive_out[slot + before + __popcll(m & ((1ull << lane) - 1))] = v;
     const int nblocks = (int)((n_alive + CT - 1) / CT);
     if (threadIdx.x == 0 && (int)(old >> 32) == nblocks - 1) loop_next_round(ctl, slot + mine, ctl[2], N, max_steps);
+}
+__global__ __launch_bounds__(CT) void k_loop_composite(int* ctl, int N, int max_steps, float T_thresh, const int* __restrict__ alive_in, int* alive_out,
+                                                       float* rays_t, const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                       const float* __restrict__ deltas, const float* __restrict__ ambs_aud,
+                                                       const float* __restrict__ ambs_eye, const float* __restrict__ uncertainties, float* weights_sum,
+                                                       float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum, float* uncertainty_sum) {
+    loop_composite_block(ctl, N, max_steps, T_thresh, alive_in, alive_out, rays_t, sigmas, rgbs, deltas, ambs_aud, ambs_eye, uncertainties, weights_sum, depth,
+                         image, amb_aud_sum, amb_eye_sum, uncertainty_sum);
+}
+// grid (ceil(N / CT), n_frames): the survivor counter, the block count and the head of the next round are the frame's own (its control block)
+__global__ __launch_bounds__(CT) void k_loop_composite_batch(const LoopFrame* __restrict__ frames, int odd, int N, int max_steps, float T_thresh) {
+    const LoopFrame f = frames[blockIdx.y];
+    loop_composite_block(f.ctl, N, max_steps, T_thresh, odd ? f.alive1 : f.alive0, odd ? f.alive0 : f.alive1, f.rays_t, f.sigmas, f.rgbs, f.deltas, f.amb_aud,
+                         f.amb_eye, f.unc, f.wsum, f.depth, f.image, f.aasum, f.aesum, f.unsum);
 }
 
 inline unsigned blocks(uint64_t n) { return (unsigned)((n + NT - 1) / NT); }
@@ -604,6 +656,33 @@ int mf_nerf_loop_composite(const NerfLoop& l, int round, const NerfFieldOut& f, 
     hipLaunchKernelGGL(k_loop_composite, dim3((unsigned)((l.N + CT - 1) / CT)), dim3(CT), 0, s, l.ctl, l.N, l.max_steps, l.T_thresh, l.alive[round & 1],
                        l.alive[(round + 1) & 1], l.rays_t, f.sigmas, f.rgbs, l.deltas, f.amb_aud, f.amb_eye,
                        f.unc, r.wsum, r.depth, r.image, r.aasum, r.aesum, r.unsum);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+// ---- the same four launches over the frames of a batch (mf_nerf_head_batch_render, mf_nerf_head_batch.hip): grid (blocks, n_frames) -------------------
+int mf_nerf_batch_init(const NerfBatchLoop& b, const float* aabb, float min_near, hipStream_t s) {
+    hipLaunchKernelGGL(k_loop_init_batch, dim3(blocks(b.N), b.n_frames), dim3(NT), 0, s, b.frames, b.N, b.max_steps, aabb, min_near);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+int mf_nerf_batch_march(const NerfBatchLoop& b, int round, float bound, hipStream_t s) {
+    const char* e = getenv("MF_NERF_MARCH");                                 // as mf_nerf_loop_march
+    const bool fast = b.cascades == 1 && (b.grid_size & (b.grid_size - 1)) == 0 && b.grid_size <= 128 && !(e && !strcmp(e, "generic"));
+    const auto kernel = fast ? k_loop_march_batch<true> : k_loop_march_batch<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks(b.N), b.n_frames), dim3(NT), 0, s, b.frames, round & 1, bound, b.dt_gamma, (uint32_t)b.max_steps, b.cascades,
+                       b.grid_size, b.bitfield);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+int mf_nerf_batch_composite(const NerfBatchLoop& b, int round, hipStream_t s) {
+    hipLaunchKernelGGL(k_loop_composite_batch, dim3((unsigned)((b.N + CT - 1) / CT), b.n_frames), dim3(CT), 0, s, b.frames, round & 1, b.N, b.max_steps,
+                       b.T_thresh);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+int mf_nerf_batch_finish(const NerfBatchLoop& b, hipStream_t s) {
+    hipLaunchKernelGGL(k_nerf_finish_batch, dim3(blocks(b.N), b.n_frames), dim3(NT), 0, s, b.frames, (uint32_t)b.N);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

@@ -36,6 +36,49 @@ __global__ __launch_bounds__(NWAVE * 64) void k_nerf_field_fused(const FusedArgs
         field_tile<X3>(a, smem, lt, eye_v, tile * TILE + wave * 16 * NSF, M);
 }
 
+// ---- the field over the round's samples of EVERY frame of a batch (mf_nerf_head_batch_render), one launch ----------------------------------------------
+// A (tiles, n_frames) grid would stage the 63 - 126 KB of weight fragments once per frame and workgroup.  Here a workgroup reads every frame's sample count
+// (ctl[3]; 0 for a frame whose loop has ended), forms the prefix of the per-frame tile counts in LDS (n_frames <= 64: one wave), stages the weights ONCE and walks
+// the flattened (frame, tile) pairs with stride gridDim.x, calling the unchanged field_tile with that frame's pointers -- a sample's result depends on nothing but
+// the sample, so a frame is the same bits as through k_nerf_field_fused.  Frame index, counts and pointers are wave-uniform scalars.
+constexpr int BATCH_MAX_FRAMES = 64;
+template <bool X3>
+__global__ __launch_bounds__(NWAVE * 64) void k_nerf_field_batch(const FusedArgs a, const LoopFrame* __restrict__ frames, const int n_frames, const int skip_empty) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ LevelTab lt;
+    __shared__ int s_first[BATCH_MAX_FRAMES + 16], s_M[BATCH_MAX_FRAMES];     // s_first[f]: tiles of the frames before f, s_first[n_frames ...]: all tiles
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    auto uni = [](int x) __attribute__((always_inline)) { return __builtin_amdgcn_readfirstlane(x); };
+    if (wave == 0) {
+        const int lane = threadIdx.x;
+        const int M = lane < n_frames ? frames[lane].ctl[3] : 0;
+        int upto = (M + TILE - 1) / TILE;                                     // inclusive prefix over the 64 lanes
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(upto, d);
+            if (lane >= d) upto += o;
+        }
+        s_M[lane] = M;
+        s_first[lane + 1] = upto;
+        if (lane == 0) s_first[0] = 0;
+    }
+    __syncthreads();
+    const int total = uni(s_first[n_frames]);
+    if ((int)blockIdx.x >= total) return;           // (every frame's round already finished: total == 0)
+    field_stage_weights<X3>(a, smem, lt, NWAVE * 64);
+    int f = 0;
+    for (int p = blockIdx.x; p < total; p += gridDim.x) {
+        while (uni(s_first[f + 1]) <= p) ++f;       // p only grows, so does its frame
+        const int tile = p - uni(s_first[f]), M = uni(s_M[f]);
+        const LoopFrame& fr = frames[f];
+        FusedArgs af = a;
+        af.xyzs = fr.xyzs; af.dirs = fr.dirs; af.deltas = skip_empty ? fr.deltas : nullptr; af.enc_a = fr.enc_a; af.ind = fr.ind;
+        af.sigmas = fr.sigmas; af.rgbs = fr.rgbs; af.amb_aud = fr.amb_aud; af.amb_eye = fr.amb_eye; af.unc = fr.unc;
+        const float eye_v = fr.eye_dev ? *fr.eye_dev : fr.eye;
+        field_tile<X3>(af, smem, lt, eye_v, tile * TILE + wave * 16 * NSF, M);
+    }
+}
+
 // ---- the render loop's TAIL: every round the launch chain did not enqueue, in one launch ------------------------------------------------------
 // mf_nerf_head_render enqueues R rounds as (march, field, composite) launches -- R follows the round counts of the frames before (a frame needs ~5 of the
 // max_steps = 16 the reference allows: renderer.py:246-270) -- and then this kernel ONCE.  It finds the loop ended (ctl[1] == 0: the usual case, one empty launch
@@ -265,6 +308,22 @@ int mf_nerf_fused_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, co
     const int grid = std::min(a.ntiles, 256);
     if (f.x3) hipLaunchKernelGGL(k_nerf_field_fused<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a);
     else hipLaunchKernelGGL(k_nerf_field_fused<false>, dim3(grid), dim3(NWAVE * 64), lds, s, a);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+int mf_nerf_fused_batch_launch(const NerfFieldConsts& f, float sigma_scale, const NerfBatchLoop& b, hipStream_t s) {
+    MF_REQUIRE(b.n_frames >= 1 && b.n_frames <= BATCH_MAX_FRAMES, "nerf_fused_batch_launch: %d frames (1..%d)", b.n_frames, BATCH_MAX_FRAMES);
+    FusedArgs a{};
+    int rc;
+    // (the per-frame members -- samples, outputs, enc_a, ind, eye -- are filled in by the kernel from the frame table; a.ntiles: one frame's upper bound)
+    if ((rc = fused_args(a, f, NerfFrameInputs{nullptr, nullptr, 0.f, nullptr, sigma_scale}, nullptr, nullptr, b.N, NerfFieldOut{nullptr, nullptr, nullptr, nullptr, nullptr}))) return rc;
+    const size_t lds = (size_t)NFRAG * (f.x3 ? 2 : 1) * 1024;
+    static bool attr_done[2] = {false, false};
+    if ((rc = f.x3 ? fused_lds_attr(k_nerf_field_batch<true>, attr_done[1], lds) : fused_lds_attr(k_nerf_field_batch<false>, attr_done[0], lds))) return rc;
+    const int grid = (int)std::min<int64_t>((int64_t)a.ntiles * b.n_frames, 256);
+    if (f.x3) hipLaunchKernelGGL(k_nerf_field_batch<true>, dim3(grid), dim3(NWAVE * 64), lds, s, a, b.frames, b.n_frames, (int)b.skip_empty);
+    else hipLaunchKernelGGL(k_nerf_field_batch<false>, dim3(grid), dim3(NWAVE * 64), lds, s, a, b.frames, b.n_frames, (int)b.skip_empty);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }

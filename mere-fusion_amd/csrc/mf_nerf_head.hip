@@ -30,18 +30,11 @@ struct mf_nerf_head {
     }
 };
 
-constexpr int HEAD_MAX_ROUNDS = 1024;     // max_steps accepted by mf_nerf_head_render (one round per step at least: renderer.py:270); the control block holds tail tickets for as many
-
 // How many rounds of the next frame are enqueued as (march, field, composite) launches; the tail launch covers the rest.  The most rounds any of the last four
-// observed frames ran; every round (no tail) until a first frame has reported.  MF_NERF_TAIL_AFTER=<k> fixes it (tests, A/B: 0 = the tail runs the whole
-// loop, "off" = launches only, as before round 6); read per call.
+// observed frames ran; every round (no tail) until a first frame has reported.  MF_NERF_TAIL_AFTER=<k> fixes it (nerf_tail_after_env, mf_nerf_host.h).
 static int head_plan(mf_nerf_head* h, int max_steps) {
-    const char* e = getenv("MF_NERF_TAIL_AFTER");
-    if (e && *e) {
-        if (!strcmp(e, "off")) return max_steps;
-        const int k = atoi(e);
-        return k < 0 ? max_steps : (k < max_steps ? k : max_steps);
-    }
+    const int fixed = nerf_tail_after_env(max_steps);
+    if (fixed >= 0) return fixed;
     const int seen = h->fb ? h->fb[0] : 0;
     if (seen > 0) { h->hist[h->hist_n & 3] = seen; h->hist_n++; }
     if (h->hist_n == 0) return max_steps;

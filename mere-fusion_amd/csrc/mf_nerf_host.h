@@ -4,6 +4,8 @@
 // kernel-argument structs (FusedArgs, TailArgs, TorsoFusedArgs, ...).
 #pragma once
 #include "mf_nn.h"
+#include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -39,6 +41,15 @@ struct NerfLoop {                        // the device-controlled render loop of
     bool skip_empty;                     // MF_NERF_SKIP_EMPTY, read once per frame: the field skips fragments whose slots hold no sample
     const float* skip_deltas() const { return skip_empty ? deltas : nullptr; }    // what the field kernels get as FusedArgs::deltas
 };
+struct LoopFrame;                        // mf_nerf_march.h: one frame of a batch as the kernels read it
+struct NerfBatchLoop {                   // the render loops of the frames of one mf_nerf_head_batch_render call: what the frames share
+    const LoopFrame* frames;             // device table, n_frames entries
+    int n_frames, N, max_steps;
+    const uint8_t* bitfield;
+    uint32_t cascades, grid_size;
+    float dt_gamma, T_thresh;
+    bool skip_empty;                     // as NerfLoop::skip_empty
+};
 struct NerfGridBufs { float* density_grid; uint8_t* bitfield; float *tmp_grid, *xyzs_out; double *mean_density, *partials; };   // mf_nerf_density_grid_update's
 struct NerfTorsoConsts {                 // what a torso handle holds for the fused kernel
     const float *w, *emb;                // device: the six layers' fp32 tables (mf_nerf_torso_fused_weight_count entries), the tiled grid's embedding
@@ -59,12 +70,32 @@ int mf_nerf_fused_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, co
 int mf_nerf_tail_launch(const NerfFieldConsts& f, const NerfFrameInputs& in, const NerfFieldOut& out, const NerfLoop& loop, const NerfRaySums& sums,
                         int rounds_launched, hipStream_t s);
 
+// one launch for the round's samples of every frame of a batch: a workgroup stages the weights once and walks (frame, tile) pairs (k_nerf_field_batch)
+int mf_nerf_fused_batch_launch(const NerfFieldConsts& f, float sigma_scale, const NerfBatchLoop& b, hipStream_t s);
+
+// ---- the render loop's limits and switches shared by mf_nerf_head.hip and mf_nerf_head_batch.hip ---------------------------------------------------
+constexpr int HEAD_MAX_ROUNDS = 1024;     // max_steps accepted by mf_nerf_head_render (one round per step at least: renderer.py:270); the control block holds tail tickets for as many
+// MF_NERF_TAIL_AFTER=<k> fixes how many rounds go out as launches (tests, A/B: 0 = the tail runs the whole loop, "off" = launches only, as before round 6); read per
+// call.  Returns that count, or -1 when the variable is not set.
+inline int nerf_tail_after_env(int max_steps) {
+    const char* e = getenv("MF_NERF_TAIL_AFTER");
+    if (!(e && *e)) return -1;
+    if (!strcmp(e, "off")) return max_steps;
+    const int k = atoi(e);
+    return k < 0 ? max_steps : (k < max_steps ? k : max_steps);
+}
+
 // ---- mf_nerf.hip: the launches of a round --------------------------------------------------------------------------------------------------------
 // init: alive[0] = 0..N-1, near / far of every ray (raymarching.cu:92-145), zeroed sums, the first round's head
 int mf_nerf_loop_init(const NerfLoop& loop, const NerfRaySums& sums, float* nears, const float* aabb, float min_near, hipStream_t s);
 int mf_nerf_loop_march(const NerfLoop& loop, int round, float bound, hipStream_t s);
 // composite + compaction + head of the next round
 int mf_nerf_loop_composite(const NerfLoop& loop, int round, const NerfFieldOut& field, const NerfRaySums& sums, hipStream_t s);
+// the same launches with a frame index in blockIdx.y (and the finish of every frame whose bg_per_ray >= 0)
+int mf_nerf_batch_init(const NerfBatchLoop& b, const float* aabb, float min_near, hipStream_t s);
+int mf_nerf_batch_march(const NerfBatchLoop& b, int round, float bound, hipStream_t s);
+int mf_nerf_batch_composite(const NerfBatchLoop& b, int round, hipStream_t s);
+int mf_nerf_batch_finish(const NerfBatchLoop& b, hipStream_t s);
 
 // ---- mf_nerf_occupancy.hip: the occupancy-grid rebuild over the fused field's weight fragments (sweep, dilate + EMA, reduce + pack) -----------------
 int mf_nerf_occupancy_shape(const char* what, int cascades, int grid_size, size_t* n_partials);      // the one place the served sizes are checked

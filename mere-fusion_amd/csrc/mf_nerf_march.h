@@ -11,6 +11,19 @@
 #include <cmath>
 #include <cstdint>
 
+// One frame of a batched head call (mf_nerf_head_batch_render) as the frame-indexed kernels read it: a device table with one entry per blockIdx.y.  The handle's
+// frame slot (control block, alive lists, per-ray and per-sample buffers) and the caller's per-frame inputs and outputs, already resolved to plain pointers.
+struct LoopFrame {
+    int *ctl, *alive0, *alive1;                                      // slot: control block (layout below), the two alive lists
+    float *rays_t, *nears, *fars, *xyzs, *dirs, *deltas;             // slot: per ray, and the round's samples
+    float *sigmas, *rgbs, *amb_aud, *amb_eye, *unc;                  // slot: the field's outputs per sample
+    float *wsum, *depth, *image, *aasum, *aesum, *unsum;             // per-ray sums: depth / image are the caller's, wsum the caller's or the slot's
+    const float *rays_o, *rays_d, *enc_a, *ind, *eye_dev, *bg;       // the caller's inputs (eye_dev, ind, bg may be null)
+    uint8_t* frame_u8;                                               // or null
+    float eye, bg_const;
+    int bg_per_ray;                                                  // < 0: the frame is left unfinished
+};
+
 namespace {
 
 __device__ __forceinline__ float signf_(float x) { return copysignf(1.0f, x); }

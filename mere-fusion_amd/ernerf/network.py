@@ -30,9 +30,9 @@ class _Results(dict):
     """`run_cuda`'s result dict.  `image` and `depth` are what `test_step` reads (utils.py:953-954); the three per-ray sums the reference also returns
     (renderer.py:286-288) are copied out of the head's buffers only if somebody asks for them -- before the next frame is rendered."""
 
-    def __init__(self, owner, frame_id, prefix, n, *a, **k):
+    def __init__(self, owner, frame_id, prefix, n, slot=None, *a, **k):
         super().__init__(*a, **k)
-        self._owner, self._frame_id, self._prefix, self._n = owner, frame_id, prefix, n
+        self._owner, self._frame_id, self._prefix, self._n, self._slot = owner, frame_id, prefix, n, slot      # slot: the frame's place in a render_frames batch
 
     def __missing__(self, key):
         if key not in ("ambient_aud", "ambient_eye", "uncertainty"):
@@ -43,8 +43,11 @@ class _Results(dict):
         dev = self["image"].device
         aa, ae, un = (torch.empty(self._n, device=dev) for _ in range(3))
         import ctypes as C
-        _lib.check(_lib.lib().mf_nerf_head_sums(o._mf["renderer"]._head, self._n, C.c_void_p(aa.data_ptr()), C.c_void_p(ae.data_ptr()),
-                                                C.c_void_p(un.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mf_nerf_head_sums")
+        ptrs = (C.c_void_p(aa.data_ptr()), C.c_void_p(ae.data_ptr()), C.c_void_p(un.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if self._slot is None:
+            _lib.check(_lib.lib().mf_nerf_head_sums(o._mf["renderer"]._head, self._n, *ptrs), "mf_nerf_head_sums")
+        else:
+            _lib.check(_lib.lib().mf_nerf_head_batch_sums(o._mf["renderer"]._batch, self._slot, self._n, *ptrs), "mf_nerf_head_batch_sums")
         self["ambient_aud"], self["ambient_eye"], self["uncertainty"] = aa.view(*self._prefix), ae.view(*self._prefix), un
         return self[key]
 
@@ -116,7 +119,81 @@ class HipRenderMixin:
                                "reference's loop over the extension shims, which need a device too)")
         prefix = rays_o.shape[:-1]
         n = int(prefix.numel())
-        dev = rays_o.device
+        r = self._mf_refresh(n, rays_o.device)
+        with torch.no_grad():
+            auds_in = self._mf_audio_in(r, auds)
+            out = r.render(rays_o, rays_d, auds_in, bg_coords, poses, eye, bg_color=bg_color, loop="device", dt_gamma=float(dt_gamma),
+                           max_steps=int(max_steps), T_thresh=float(T_thresh))
+            if self.smooth_lips and not self.emb:
+                self.enc_a = r.enc_a                                    # the EMA state lives where the reference keeps it (renderer.py:128-129, 190-194)
+        self.__dict__["_mf_frame_id"] = self._mf_frame_id + 1
+        self.__dict__["mf_frames"] = self.mf_frames + 1
+        return self._mf_results(out, prefix, n)
+
+    def _mf_results(self, out, prefix, n, slot=None):
+        res = _Results(self, self._mf_frame_id, prefix, n, slot)
+        res["depth"] = out["depth"].view(*prefix)
+        res["image"] = out["image"].view(*prefix, 3)
+        res["weights_sum"] = out["weights_sum"]
+        return res
+
+    def _mf_audio_in(self, r, auds):
+        """what the renderer takes as one frame's `auds`, and who applies the lip-smoothing EMA to it (the state is `self.enc_a` either way)"""
+        if self.emb:                                                # network.py:229-230: an embedding lookup in front of the audio net -- the reference's modules run it
+            enc_a = super().encode_audio(auds)
+            if enc_a is not None and self.smooth_lips:
+                if self.enc_a is not None:
+                    enc_a = 0.35 * self.enc_a + (1 - 0.35) * enc_a
+                self.enc_a = enc_a
+            r.smooth_lips = False
+            return enc_a
+        r.smooth_lips = bool(self.smooth_lips)
+        r.enc_a = self.enc_a if self.smooth_lips else None
+        return auds
+
+    def render_frames(self, jobs, dt_gamma=0, max_steps=1024, T_thresh=1e-4, reserve_frames=0, **kwargs):
+        """`run_cuda` for several frames of one ray count with ONE head call (HipHeadRenderer.render_frames): jobs is a list of dicts (rays_o, rays_d, auds,
+        bg_coords, poses, eye, bg_color).  The per-frame refreshes of run_cuda happen once for the group; the audio windows, the EMA and the torso are taken per
+        frame, in order.  Returns one result dict per frame, each the same bits as run_cuda gives for that frame alone.  Frames the device loop does not serve
+        (see _mf_fast_path) go through run_cuda one by one.  reserve_frames: see HipHeadRenderer.run_cuda_device_batch."""
+        kw = dict(dt_gamma=dt_gamma, max_steps=max_steps, T_thresh=T_thresh)
+        if not jobs:
+            return []
+        if not all(self._mf_fast_path(j["rays_o"], j["auds"], j.get("eye"), False) and torch.is_tensor(j["rays_o"]) and j["rays_o"].is_cuda for j in jobs):
+            outs = []
+            for j in jobs:
+                box = j.get("ema")
+                if box is not None:
+                    self.enc_a = box[0]
+                outs.append(self.run_cuda(j["rays_o"], j["rays_d"], j["auds"], j["bg_coords"], j["poses"], eye=j.get("eye"), bg_color=j.get("bg_color"), **kw))
+                if box is not None:
+                    box[0] = self.enc_a
+            return outs
+        prefix = jobs[0]["rays_o"].shape[:-1]
+        n = int(prefix.numel())
+        r = self._mf_refresh(n, jobs[0]["rays_o"].device)
+        with torch.no_grad():
+            if self.emb:
+                feed = []
+                for j in jobs:                                          # (`ema`: see HipHeadRenderer.render_frames; here the state is the module's own)
+                    box = j.get("ema")
+                    if box is not None:
+                        self.enc_a = box[0]
+                    feed.append(dict(j, auds=self._mf_audio_in(r, j["auds"]), ema=None))
+                    if box is not None:
+                        box[0] = self.enc_a
+            else:
+                self._mf_audio_in(r, None)                              # the renderer applies the EMA frame by frame from the module's state
+                feed = jobs
+            outs = r.render_frames(feed, reserve_frames=reserve_frames, dt_gamma=float(dt_gamma), max_steps=int(max_steps), T_thresh=float(T_thresh))
+            if self.smooth_lips and not self.emb:
+                self.enc_a = r.enc_a
+        self.__dict__["_mf_frame_id"] = self._mf_frame_id + 1
+        self.__dict__["mf_frames"] = self.mf_frames + len(jobs)
+        return [self._mf_results(out, prefix, n, slot=i) for i, out in enumerate(outs)]
+
+    def _mf_refresh(self, n, dev):
+        """the device objects for n rays on dev, with the per-frame attributes the reference reads at call time handed over; returns the renderer"""
         st = self._mf
         if st is None or st["cap"] < n or st["device"] != dev or st["bitfield_ptr"] != self.density_bitfield.data_ptr():
             st = self._mf_build(n, dev)
@@ -144,28 +221,7 @@ class HipRenderMixin:
             g = getattr(self, "density_grid_torso", None)
             if torch.is_tensor(g):
                 r.torso.density_grid = g if r.torso._is_grid(g) else g.detach().to(dev, torch.float32).contiguous()
-        with torch.no_grad():
-            if self.emb:                                                # network.py:229-230: an embedding lookup in front of the audio net -- the reference's modules run it
-                enc_a = super().encode_audio(auds)
-                if enc_a is not None and self.smooth_lips:
-                    if self.enc_a is not None:
-                        enc_a = 0.35 * self.enc_a + (1 - 0.35) * enc_a
-                    self.enc_a = enc_a
-                auds_in, r.smooth_lips = enc_a, False
-            else:
-                auds_in, r.smooth_lips = auds, bool(self.smooth_lips)
-                r.enc_a = self.enc_a if self.smooth_lips else None
-            out = r.render(rays_o, rays_d, auds_in, bg_coords, poses, eye, bg_color=bg_color, loop="device", dt_gamma=float(dt_gamma),
-                           max_steps=int(max_steps), T_thresh=float(T_thresh))
-            if self.smooth_lips and not self.emb:
-                self.enc_a = r.enc_a                                    # the EMA state lives where the reference keeps it (renderer.py:128-129, 190-194)
-        self.__dict__["_mf_frame_id"] = self._mf_frame_id + 1
-        self.__dict__["mf_frames"] = self.mf_frames + 1
-        res = _Results(self, self._mf_frame_id, prefix, n)
-        res["depth"] = out["depth"].view(*prefix)
-        res["image"] = out["image"].view(*prefix, 3)
-        res["weights_sum"] = out["weights_sum"]
-        return res
+        return r
 
 
     # ---- occupancy-grid maintenance (renderer.py:355-539) ---------------------------------------------------------------------------

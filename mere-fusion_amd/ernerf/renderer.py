@@ -27,30 +27,32 @@ class HipHeadRenderer:
         self.aabb_infer = torch.tensor([-b, -b / 2, -b, b, b / 2, b], dtype=torch.float32, device=density_bitfield.device)   # renderer.py:86-89
         self._aabb_default = self.aabb_infer        # rebinding `aabb_infer` (a checkpoint's buffer: HipRenderMixin does, and NerfSession for a bare renderer) makes the device loop read it too
         self._lib = _lib.lib()
-        self._head, self._side = None, None
+        self._head, self._side, self._batch = None, None, None
+
+    def _audio_part(self, auds):
+        """audio window -> enc_a with the lip-smoothing EMA of renderer.py:190-194 (state: self.enc_a)"""
+        if self.audio is not None and self.smooth_lips and hasattr(self.audio, "encode_audio_smooth"):
+            # the EMA of renderer.py:190-194 inside the encoder's launch (three torch elementwise launches per frame otherwise; same bits)
+            enc_a = self.audio.encode_audio_smooth(auds, self.enc_a)
+            if enc_a is not None:
+                self.enc_a = enc_a
+            return enc_a
+        enc_a = self.audio.encode_audio(auds) if self.audio is not None else auds
+        if enc_a is not None and self.smooth_lips:
+            if self.enc_a is not None:
+                enc_a = 0.35 * self.enc_a + (1 - 0.35) * enc_a
+            self.enc_a = enc_a
+        return enc_a
 
     @torch.no_grad()
     def render(self, rays_o, rays_d, auds, bg_coords, poses, eye, bg_color=None, **kw):
         """One frame as `NeRFRenderer.render` -> `run_cuda` does it (renderer.py:657-677, 158-291): audio window -> enc_a (+ the lip
         smoothing EMA of :190-194), fixed individual code 0 (:197-202), head loop, torso / background mix (:272-277).
         loop="device" runs the head with device-side round control."""
-        def audio_part():
-            if self.audio is not None and self.smooth_lips and hasattr(self.audio, "encode_audio_smooth"):
-                # the EMA of renderer.py:190-194 inside the encoder's launch (three torch elementwise launches per frame otherwise; same bits)
-                enc_a = self.audio.encode_audio_smooth(auds, self.enc_a)
-                if enc_a is not None:
-                    self.enc_a = enc_a
-                return enc_a
-            enc_a = self.audio.encode_audio(auds) if self.audio is not None else auds
-            if enc_a is not None and self.smooth_lips:
-                if self.enc_a is not None:
-                    enc_a = 0.35 * self.enc_a + (1 - 0.35) * enc_a
-                self.enc_a = enc_a
-            return enc_a
         device_loop = kw.pop("loop", "host") == "device"
         # (the torso on a second stream beside the head paid while it was a ~0.3 ms launch chain; as one 71 us kernel the cross-stream dependency cost more
         # than the overlap returned, 0.737 vs 0.711 ms per frame: the path left in round 5)
-        enc_a = audio_part()
+        enc_a = self._audio_part(auds)
         if device_loop and self.torso is not None and not kw.get("graph"):
             # the head loop is enqueued FIRST and left unfinished; the torso's per-frame host work (the wrapped anchors: a 4 x 4 inverse and 42 sines, ~90 us, and the
             # device -> host copy of the pose when it lives on the device as the reference's does) then runs while the GPU marches, and the background mix closes the
@@ -92,6 +94,10 @@ class HipHeadRenderer:
         if h:
             self._lib.mf_nerf_head_destroy(h)
             self._head = None
+        b = getattr(self, "_batch", None)
+        if b:
+            self._lib.mf_nerf_head_batch_destroy(b)
+            self._batch = None
 
     @torch.no_grad()
     def run_cuda_device(self, rays_o, rays_d, enc_a, ind_code, eye, bg_color=None, dt_gamma=1 / 256, max_steps=16, T_thresh=1e-4, want_u8=False,
@@ -121,9 +127,7 @@ class HipHeadRenderer:
         _lib.check(self._lib.mf_nerf_head_set_eye(self._head, p(eye_dev)), "mf_nerf_head_set_eye")
         # the box of near / far: the reference reads its persistent buffer `self.aabb_infer` every frame (renderer.py:226); the head reads a rebound one where it
         # lives (mf_nerf_head_set_aabb).  Never rebound: the head's own box from `bound`, as before
-        aabb = None if self.aabb_infer is self._aabb_default else self.aabb_infer
-        if aabb is not None and not (torch.is_tensor(aabb) and aabb.is_cuda and aabb.dtype == torch.float32 and aabb.is_contiguous() and aabb.numel() == 6):
-            raise RuntimeError("HipHeadRenderer: aabb_infer must be a contiguous float32 CUDA tensor of 6 values (there is no CPU path)")
+        aabb = self._aabb_arg()
         _lib.check(self._lib.mf_nerf_head_set_aabb(self._head, p(aabb)), "mf_nerf_head_set_aabb")
 
         def enqueue(out):
@@ -169,6 +173,106 @@ class HipHeadRenderer:
                     dst.copy_(src)
         hit[0].replay()
         return hit[1]
+
+    # ---- several frames in one device loop (mf_nerf_head_batch_render) ----------------------------------------------------------------
+    MAX_BATCH_FRAMES = 64               # the library's limit per call
+
+    def _aabb_arg(self):
+        """the box the device loops read: None for the built-in one from `bound`, else the rebound `aabb_infer` (checked)"""
+        aabb = None if self.aabb_infer is self._aabb_default else self.aabb_infer
+        if aabb is not None and not (torch.is_tensor(aabb) and aabb.is_cuda and aabb.dtype == torch.float32 and aabb.is_contiguous() and aabb.numel() == 6):
+            raise RuntimeError("HipHeadRenderer: aabb_infer must be a contiguous float32 CUDA tensor of 6 values (there is no CPU path)")
+        return aabb
+
+    def _batch_handle(self, n_rays, n_frames):
+        """the batch handle, created or grown (rays or frame slots) on demand"""
+        if getattr(self, "_batch", None) is None or self._batch_cap[0] < n_rays or self._batch_cap[1] < n_frames:
+            cap = (n_rays, n_frames)
+            if getattr(self, "_batch", None):
+                cap = (max(n_rays, self._batch_cap[0]), max(n_frames, self._batch_cap[1]))
+                self._lib.mf_nerf_head_batch_destroy(self._batch)
+                self._batch = None
+            h = C.c_void_p()
+            _lib.check(self._lib.mf_nerf_head_batch_create(self.field._h, cap[0], cap[1], C.byref(h)), "mf_nerf_head_batch_create")
+            self._batch, self._batch_cap = h, cap
+        return self._batch
+
+    @torch.no_grad()
+    def run_cuda_device_batch(self, frames, dt_gamma=1 / 256, max_steps=16, T_thresh=1e-4, want_u8=False, finish=True, reserve_frames=0):
+        """`run_cuda_device` for several frames of one ray count in ONE chain of launches: frames is a list of dicts (rays_o, rays_d, enc_a, eye, bg_color and
+        optionally ind_code, default the renderer's); returns the list of the dicts run_cuda_device returns.  Every frame is the same bits as rendered alone.
+        reserve_frames: frame slots the batch handle is created with when that is more than this call needs -- a caller that knows its largest call says so once,
+        because growing the handle later frees and reallocates every slot (a synchronising free)."""
+        F = len(frames)
+        if not 1 <= F <= self.MAX_BATCH_FRAMES:
+            raise RuntimeError(f"HipHeadRenderer.run_cuda_device_batch: {F} frames (1..{self.MAX_BATCH_FRAMES} per call)")
+        p = lambda t: t.data_ptr() if t is not None else None
+        descs = (_lib.MfNerfFrameDesc * F)()
+        keep, outs, N, dev = [], [], None, None
+        for i, fr in enumerate(frames):
+            rays_o = fr["rays_o"].contiguous().view(-1, 3).float()
+            rays_d = fr["rays_d"].contiguous().view(-1, 3).float()
+            if N is None:
+                N, dev = rays_o.shape[0], rays_o.device
+            elif rays_o.shape[0] != N:
+                raise RuntimeError(f"HipHeadRenderer.run_cuda_device_batch: frame {i} has {rays_o.shape[0]} rays, frame 0 has {N} (one ray count per call)")
+            bg_color, eye, ind_code = fr.get("bg_color"), fr.get("eye"), fr.get("ind_code", self.ind_code)
+            bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
+            per_ray = bg is not None and bg.numel() == 3 * N
+            bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
+            ea = fr["enc_a"].float().reshape(-1).contiguous()
+            ic = ind_code.float().reshape(-1).contiguous() if ind_code is not None else None
+            eye_dev = eye.float().reshape(-1)[:1].contiguous() if (torch.is_tensor(eye) and eye.is_cuda) else None      # as run_cuda_device
+            ev = 0.0 if (eye is None or eye_dev is not None) else float(eye.reshape(-1)[0])
+            out = {"image": torch.empty(N, 3, device=dev), "depth": torch.empty(N, device=dev), "weights_sum": torch.empty(N, device=dev),
+                   "frame_u8": torch.empty(N, 3, dtype=torch.uint8, device=dev) if want_u8 else None}
+            d = descs[i]
+            d.rays_o, d.rays_d, d.enc_a, d.ind_code, d.eye_dev, d.eye = p(rays_o), p(rays_d), p(ea), p(ic), p(eye_dev), ev
+            d.bg_color, d.bg_per_ray, d.bg_const = p(bg), (int(per_ray) if finish else -1), bgc
+            d.image, d.depth, d.weights_sum, d.frame_u8 = p(out["image"]), p(out["depth"]), p(out["weights_sum"]), p(out["frame_u8"])
+            keep.append((rays_o, rays_d, ea, ic, eye_dev, bg))         # what the descriptors point at lives until the call is enqueued
+            outs.append(out)
+        aabb = self._aabb_arg()
+        h = self._batch_handle(N, max(F, min(int(reserve_frames), self.MAX_BATCH_FRAMES)))
+        _lib.check(self._lib.mf_nerf_head_batch_render(h, descs, F, N, C.c_void_p(self.bitfield.data_ptr()), self.cascade, self.grid_size, self.min_near,
+                                                       float(dt_gamma), int(max_steps), float(T_thresh), self.density_scale,
+                                                       C.c_void_p(aabb.data_ptr()) if aabb is not None else None,
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_batch_render")
+        del keep
+        return outs
+
+    def finish_device_batch(self, outs, bg_colors):
+        """finish_device for the results of a run_cuda_device_batch(finish=False): frame i with bg_colors[i]"""
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        for i, (out, bg_color) in enumerate(zip(outs, bg_colors)):
+            N = out["image"].shape[0]
+            bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
+            per_ray = bg is not None and bg.numel() == 3 * N
+            bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
+            _lib.check(self._lib.mf_nerf_head_batch_finish(self._batch, i, N, p(bg), int(per_ray), bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]),
+                                                           p(out["frame_u8"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_batch_finish")
+        return outs
+
+    @torch.no_grad()
+    def render_frames(self, jobs, reserve_frames=0, **kw):
+        """`render(..., loop="device")` for several frames with ONE head call: jobs is a list of dicts (rays_o, rays_d, auds, bg_coords, poses, eye, bg_color), kw
+        the render keywords they share (dt_gamma, max_steps, T_thresh, want_u8).  Per frame and in order: audio window -> enc_a with the lip-smoothing EMA; then the
+        batched head, left unfinished when there is a torso net; then per frame the torso and the finish.  Same kernels per frame, same bits.
+        A job may carry `ema`, a one-element list: the EMA value its frame continues (installed before the frame's audio, written back after it), so that frames of
+        several sessions -- each with its own lip-smoothing state -- share one call (nerf_serving.NerfBatcher)."""
+        frames = []
+        for j in jobs:
+            box = j.get("ema")
+            if box is not None:
+                self.enc_a = box[0]
+            enc_a = self._audio_part(j["auds"])
+            if box is not None:
+                box[0] = self.enc_a
+            frames.append(dict(rays_o=j["rays_o"], rays_d=j["rays_d"], enc_a=enc_a, eye=j.get("eye"), bg_color=j.get("bg_color")))
+        if self.torso is None:
+            return self.run_cuda_device_batch(frames, reserve_frames=reserve_frames, **kw)
+        outs = self.run_cuda_device_batch(frames, finish=False, reserve_frames=reserve_frames, **kw)
+        return self.finish_device_batch(outs, [self.torso.run_torso(j["bg_coords"], j["poses"], j.get("bg_color"))["bg_color"] for j in jobs])
 
     GRID_SIZES = (32, 64, 128)          # what the grid-maintenance entry points serve (the reference always uses 128); the library's rule: mf_nerf_occupancy_shape
 

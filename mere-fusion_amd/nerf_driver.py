@@ -168,30 +168,48 @@ class NerfSession:
     def step(self, auds, audiotype=(0, 0), out=None):
         """One `NeRFReal.test_step`: the uint8 RGB frame as a device tensor -- [GH, GW, 3], [FH, FW, 3] with body frames, or the custom image's size.
         auds: `NerfASRFrontend.get_next_feat()`; audiotype: the types of the frame's two audio chunks (nerfreal.py:81-88); out: see frame_out."""
+        job = self.begin(auds, audiotype, out=out)
+        if not isinstance(job, dict):                           # the finished custom-video frame
+            return job
+        if self._is_module:                                                                      # utils.py:949-950
+            res = self.model.render(job["rays_o"], job["rays_d"], auds, self.bg_coords, job["poses"], eye=job["eye"], index=[job["mi"]], staged=True,
+                                    bg_color=job["bg_color"], perturb=False, **self.render_kw)
+        else:
+            self.bind_aabb()
+            res = self.model.render(job["rays_o"], job["rays_d"], auds, self.bg_coords, job["poses"], job["eye"], bg_color=job["bg_color"], loop="device",
+                                    **self.render_kw)
+        return self.end(job, res["image"], out=out)
+
+    # ---- the same frame in two halves, so that a batcher can render the frames of many sessions in one call between them (nerf_serving.NerfBatcher) ----------
+    @torch.no_grad()
+    def begin(self, auds, audiotype=(0, 0), out=None):
+        """The part of step() in front of the render: advances the loader and returns either the finished custom-video frame (`out` as in step) or the
+        frame's render job -- a dict of what `model.render` / `render_frames` take (rays_o, rays_d, auds, bg_coords, poses, eye, bg_color) plus `mi`, the mirrored
+        index, and `body`, the body frame or None."""
         ai, mi = loader_indices(self.size, self.index)          # the loader advances on every frame, a custom-video one included (nerfreal.py:72-76)
         self.index += 1
         self.last_audio_index, self.last_index = ai, mi
-        dst = {} if out is None else {"out": out}
         custom = self.next_custom(audiotype)
         if custom is not None:
-            return self.frame_out(None, custom, **dst)
+            return self.frame_out(None, custom, **({} if out is None else {"out": out}))
         pose = self.poses[mi:mi + 1]
         rays = frontend.get_rays(self._ref_get_rays, pose, self.intrinsics, self.H, self.W)
         eye = None if self.eye_area is None else self.eye_area[mi:mi + 1]
         bg = self.background(mi)
-        if self._is_module:                                                                      # utils.py:949-950
-            out = self.model.render(rays["rays_o"], rays["rays_d"], auds, self.bg_coords, pose, eye=eye, index=[mi], staged=True, bg_color=bg[None], perturb=False,
-                                    **self.render_kw)
-        else:
-            r = self.model
-            if self.aabb_infer is not None:
-                r.aabb_infer = self.aabb_infer                                                   # renderer.py:226 reads the buffer every frame
-            out = r.render(rays["rays_o"], rays["rays_d"], auds, self.bg_coords, pose, eye, bg_color=bg, loop="device", **self.render_kw)
-        image = out["image"].reshape(self.H, self.W, 3)
+        return {"rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "auds": auds, "bg_coords": self.bg_coords, "poses": pose, "eye": eye,
+                "bg_color": bg[None] if self._is_module else bg, "mi": mi, "body": None if self.fullbody_frames is None else self.fullbody_frames[mi]}
+
+    def bind_aabb(self):
+        """a bare HipHeadRenderer reads the session's box (renderer.py:226 reads the buffer every frame)"""
+        if not self._is_module and self.aabb_infer is not None:
+            self.model.aabb_infer = self.aabb_infer
+
+    def end(self, job, image, out=None):
+        """The part of step() behind the render: the rendered `image` of `job` -> the uint8 RGB frame (`out` as in step)."""
+        image = image.reshape(self.H, self.W, 3)
         if image.dtype != torch.float32 or not image.is_contiguous():
             image = image.float().contiguous()
-        body = None if self.fullbody_frames is None else self.fullbody_frames[mi]
-        return self.frame_out(image, body, **dst)
+        return self.frame_out(image, job["body"], **({} if out is None else {"out": out}))
 
     def step_to_ring(self, ring, auds, audio_frames, audiotype=(0, 0)):
         """step() and the frame into `ring` (transport.FrameRing): one DMA into the slot behind the frame's kernels, one stream fence, then the consumer's

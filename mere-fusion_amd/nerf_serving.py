@@ -12,6 +12,7 @@
                                             session's FrameRing; picking, back-pressure, advance-once and publication are serving.py's code
 
 `ernerf.asr.NerfASRFrontend` stays the per-session restatement of the reference these are tested against."""
+import os
 import time
 
 import numpy as np
@@ -207,15 +208,25 @@ class NerfASRDeviceFrontend:
 class NerfBatcher:
     """The `batcher` the schedulers drive, over a list of NerfSessions.  batch_size 4 is one wav2vec2 cadence (m / 2 frames): every picked session's net window
     completes in every step.  Sessions may share one model object; the lip-smoothing EMA `model.enc_a` (the drop-in module and the bare HipHeadRenderer keep it
-    there) is then one value per session here, installed before the session's frames and read back after them."""
+    there) is then one value per session here, installed before the session's frames and read back after them.
 
-    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None):
+    A step has three stages: `NerfSession.begin` for every frame of every picked session; the render jobs that leaves, grouped by model, ray count and render_kw,
+    rendered `frames_per_render` at a time by ONE head call each (`render_frames`: mf_nerf_head_batch_render); `NerfSession.end` into the step's output blocks.  Each
+    job carries its session's EMA value in a box the renderer reads before and writes after the frame's audio, so sessions that share a model share a head call
+    and still keep their own EMA.  A session or model without these entry points, and everyone under MF_NERF_BATCH=0, takes one `step` per frame."""
+
+    MAX_FRAMES_PER_RENDER = 64          # mf_nerf_head_batch's limit per call
+
+    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32):
         who = "NerfBatcher"
         self.sessions, self.batch_size, self.pool, self.device = list(sessions), int(batch_size), pool, torch.device(device)
         if not self.sessions:
             _refuse(who, "at least one session is required")
         if self.batch_size < 1:
             _refuse(who, f"batch_size {batch_size}")
+        if int(frames_per_render) < 1:
+            _refuse(who, f"frames_per_render {frames_per_render}")
+        self.frames_per_render = min(int(frames_per_render), self.MAX_FRAMES_PER_RENDER)
         self.max_sessions_per_step = len(self.sessions) if max_sessions_per_step is None else int(max_sessions_per_step)
         if pool is not None and pool.n_sessions != len(self.sessions):
             _refuse(who, f"a feature pool of {pool.n_sessions} rows for {len(self.sessions)} sessions")
@@ -256,23 +267,70 @@ class NerfBatcher:
         picked, _ = step_sessions(self, inputs, only, skip_none=False)          # (ER-NeRF renders silent batches too)
         for k in picked:                                                 # every input is checked BEFORE any session moves
             self._check_input(k, inputs[k])
+        batched = os.environ.get("MF_NERF_BATCH", "1") != "0"           # read per step; "0": one NerfSession.step per frame for everyone (A/B, cross-checks)
         out = [None] * len(self.sessions)
-        for k in picked:
-            s, (auds, types) = self.sessions[k], inputs[k]
-            frames = torch.empty((B,) + self.out_shape[k], dtype=torch.uint8, device=auds.device)
-            idx = []
-            shared = hasattr(s.model, "enc_a")
-            if shared:
-                s.model.enc_a = self.enc_a[k]
-            try:
-                for b in range(B):
-                    s.step(auds[b], (int(types[b][0]), int(types[b][1])), out=frames[b])
-                    idx.append(s.last_index)
-            finally:
-                if shared:
-                    self.enc_a[k] = s.model.enc_a
-            out[k] = (frames, idx)
+        jobs, ema = [], {}              # jobs: (session, frame, render job) in session order then frame order; ema: per session, the one-element box its jobs carry
+        try:
+            # ---- begin: every frame of every picked session (loader, custom-video frames, rays, background); nothing is rendered yet
+            for k in picked:
+                s, (auds, types) = self.sessions[k], inputs[k]
+                frames = torch.empty((B,) + self.out_shape[k], dtype=torch.uint8, device=auds.device)
+                idx = []
+                shared = hasattr(s.model, "enc_a")
+                if batched and self._can_batch(s):
+                    if shared:
+                        ema[k] = [self.enc_a[k]]
+                    for b in range(B):
+                        job = s.begin(auds[b], (int(types[b][0]), int(types[b][1])), out=frames[b])
+                        idx.append(s.last_index)
+                        if isinstance(job, dict):                        # (anything else: the finished custom-video frame, already in frames[b])
+                            if shared:
+                                job["ema"] = ema[k]
+                            jobs.append((k, b, job))
+                else:                                                    # a session (or model) without the two halves: one step per frame
+                    if shared:
+                        s.model.enc_a = self.enc_a[k]
+                    try:
+                        for b in range(B):
+                            s.step(auds[b], (int(types[b][0]), int(types[b][1])), out=frames[b])
+                            idx.append(s.last_index)
+                    finally:
+                        if shared:
+                            self.enc_a[k] = s.model.enc_a
+                out[k] = (frames, idx)
+            # ---- group and render, then end into the step's output blocks
+            for group in self._groups(jobs):
+                s0 = self.sessions[group[0][0]]
+                for c in range(0, len(group), self.frames_per_render):
+                    chunk = group[c:c + self.frames_per_render]
+                    s0.bind_aabb()
+                    res = s0.model.render_frames([job for _, _, job in chunk], reserve_frames=self._most_frames(s0.model), **s0.render_kw)
+                    for (k, b, job), r in zip(chunk, res):
+                        self.sessions[k].end(job, r["image"], out=out[k][0][b])
+        finally:
+            for k, box in ema.items():
+                self.enc_a[k] = box[0]
         return out
+
+    @staticmethod
+    def _can_batch(s):
+        return all(hasattr(s, n) for n in ("begin", "end", "bind_aabb")) and hasattr(s.model, "render_frames")
+
+    def _most_frames(self, model):
+        """the most frames one head call over `model` can get from this batcher: what its batch handle is sized for at the first call, so that it never has to be
+        rebuilt (a synchronising free of every frame slot) in the serving loop"""
+        n = sum(1 for s in self.sessions if s.model is model and self._can_batch(s))
+        return min(self.frames_per_render, self.batch_size * min(n, self.max_sessions_per_step))
+
+    def _groups(self, jobs):
+        """the step's render jobs grouped by what one batched head call shares: the model object, the ray count, render_kw (and, for a bare renderer, the session's
+        box); a group keeps the order of `jobs`, the groups the order in which their first job appears"""
+        groups = {}
+        for k, b, job in jobs:
+            s = self.sessions[k]
+            key = (id(s.model), int(job["rays_o"].numel()) // 3, tuple(sorted(s.render_kw.items())), id(getattr(s, "aabb_infer", None)))
+            groups.setdefault(key, []).append((k, b, job))
+        return list(groups.values())
 
     @torch.no_grad()
     def prewarm(self, auds=None):
@@ -282,18 +340,36 @@ class NerfBatcher:
             if self.pool is None:
                 _refuse("NerfBatcher.prewarm", "without a feature pool the windows of one frame must be given")
             auds = torch.zeros((self.pool.HIST if self.pool.att > 0 else 1, self.pool.audio_dim, 16), dtype=torch.float32, device=self.device)
+        def save(s):
+            return (s.index, s.last_index, s.last_audio_index, dict(s.custom_index), s.model.enc_a if hasattr(s.model, "enc_a") else None)
+
+        def restore(s, keep):
+            s.index, s.last_index, s.last_audio_index = keep[:3]
+            s.custom_index.clear()
+            s.custom_index.update(keep[3])
+            if hasattr(s.model, "enc_a"):
+                s.model.enc_a = keep[4]
         for s in self.sessions:
-            keep = (s.index, s.last_index, s.last_audio_index, dict(s.custom_index))
-            shared = hasattr(s.model, "enc_a")
-            ema = s.model.enc_a if shared else None
+            keep = save(s)
             try:
                 s.step(auds, (0, 0))
             finally:
-                s.index, s.last_index, s.last_audio_index = keep[:3]
-                s.custom_index.clear()
-                s.custom_index.update(keep[3])
-                if shared:
-                    s.model.enc_a = ema
+                restore(s, keep)
+        # ... and whole steps of rendered frames through the batched route, at most max_sessions_per_step sessions each as a serving step has them (the fullest
+        # slices first), so that the batch handles exist with their frame slots and every session's size has been through the batched kernels
+        ks = [k for k, s in enumerate(self.sessions) if self._can_batch(s)]
+        if ks and os.environ.get("MF_NERF_BATCH", "1") != "0":
+            B, cap = self.batch_size, max(1, self.max_sessions_per_step)
+            inp = (auds.unsqueeze(0).expand(B, *auds.shape), [(0, 0)] * B)
+            keeps, emas = [save(self.sessions[k]) for k in ks], list(self.enc_a)
+            try:
+                for c in range(0, len(ks), cap):
+                    part = ks[c:c + cap]
+                    self.step([inp if k in part else None for k in range(len(self.sessions))], only=part)
+            finally:
+                for k, keep in zip(ks, keeps):
+                    restore(self.sessions[k], keep)
+                self.enc_a = emas
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
