@@ -238,6 +238,27 @@ int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_rows_geom* gx,
 /* mf_attention_forward's contract on the five-launch path (pack K, GEMM, row softmax, pack V^T, GEMM) the VAE mid-block runs: any head_dim % 8 == 0. */
 int mf_attention_composite_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk, int heads, int head_dim,
                                    int precision, float* y_full, void* stream);
+/* The fused attention kernel (mf_attention_forward's) launched on VIEWS, as the networks launch it.  q, out: device fp32 [batch][gq->h * gq->w][c]; k, v:
+ * [batch][gk->h * gk->w][c]; c = heads * head_dim, the same for all four views.  packing 0: q, k and v each in a buffer of their own; 1: q alone, k and v
+ * as two slices of ONE buffer (cross-attention: gk and gv name the same cbuf, h, w, halo); 2: all three as slices of one buffer (packed self-attention:
+ * gq, gk and gv name the same buffer).  Buffers are sequences (h == 1, any halo) or halo-free maps; every view starts on an 8-channel group.  tq, tk > 0:
+ * only the first tq queries attend to the first tk keys of every item; output rows >= tq stay poison.  y_full: the whole padded output buffer of go. */
+int mf_attention_view_forward(const float* q, const float* k, const float* v, float* out, const mf_rows_geom* gq, const mf_rows_geom* gk,
+                              const mf_rows_geom* gv, const mf_rows_geom* go, int packing, int batch, int heads, int tq, int tk, int precision,
+                              float* y_full, void* stream);
+/* One convolution layer launched on VIEWS, as the networks launch it (the test seam of the sequence layers: (1 x k) kernels on h == 1 buffers, token
+ * prefixes, channel-slice operands).  weight, bias: HOST fp32 [groups][cout][cin][kh][kw] and [groups][cout] (bias optional), no BatchNorm.
+ * x: device fp32 [batch][in_h * in_w][gx->c], loaded into the view gx of a buffer whose halo ring is zero and whose other interior channels are poison;
+ * gx->h, gx->w are the layer's input size, gx->halo at least what its padding needs, gx->c / groups >= cin rounded up to 8 (the caller fills the padding
+ * channels: zero, as the networks do).  The output view gy (gy->c == groups * cout; GEGLU: cout / 2) lies in a fully poisoned buffer of the layer's output
+ * size.  res / gr (optional, together): the residual operand [batch][out_h * out_w][gy->c] in view gr of a third buffer; with desc->residual set and no
+ * gr the residual is the input's own view.  Group g is a plan of its own from weight[g], launched on channels g * (c / groups) of each view;
+ * only_group >= 0 launches that one alone (-1: all).  tokens > 0: the prefix handed to the launch.  pin (optional): HOST int[6] (bm, bn, wgm, wgn, split,
+ * ld) for mf_conv2d_pin_config's slot, all zero = unpinned.  info (optional): HOST int[11], what ran, as mf_conv2d_launch_config reports it (resolved with
+ * the prefix).  y: the view gy as fp32 [batch][out_h * out_w][gy->c]; y_full: the whole padded output buffer. */
+int mf_conv_view_forward(const mf_conv2d_desc* desc, const float* weight, const float* bias, const float* x, const float* res, float* y,
+                         const mf_rows_geom* gx, const mf_rows_geom* gy, const mf_rows_geom* gr, int batch, int tokens, int groups, int only_group,
+                         const int* pin, int* info, int precision, float* y_full, void* stream);
 /* The producers of the MF_PREC_F16Q activation format, one call each: the bytes a convolution of that precision reads.  Per pixel and 32-channel block the
  * first plane holds 32 f16 words and the second 64 bytes [q6(v - f16(v)) | q6(f16(v))], each half 24 bytes of e2m3 codes (channel t of the block in bits
  * [6t, 6t + 6)), one E8M0 scale byte 127 + floor(log2 max) - 2 and 7 zero bytes.

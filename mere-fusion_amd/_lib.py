@@ -179,6 +179,9 @@ SIGNATURES = {
     "mf_gemm_bt_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_int64] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2),
     "mf_vae_post_u8_forward": (C.c_int, [C.c_void_p] * 2 + [C.POINTER(MfRowsGeom), C.c_int, C.c_int, C.c_void_p]),
     "mf_attention_composite_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "mf_attention_view_forward": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] * 4 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "mf_conv_view_forward": (C.c_int, [C.POINTER(MfConv2dDesc)] + [C.c_void_p] * 5 + [C.POINTER(MfRowsGeom)] * 3 + [C.c_int] * 4
+                             + [C.POINTER(C.c_int)] * 2 + [C.c_int] + [C.c_void_p] * 2),
     "mf_act_q_encode": (C.c_int, [C.c_void_p, C.POINTER(MfRowsGeom)] + [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_int, C.c_float] + [C.c_void_p] * 4),
     "mf_near_far_from_aabb": (C.c_int, [C.c_void_p] * 3 + [C.c_uint32, C.c_float] + [C.c_void_p] * 3),
     "mf_march_rays": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32]

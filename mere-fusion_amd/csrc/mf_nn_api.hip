@@ -2,7 +2,8 @@
 // tensors in and out, every op launched exactly as the model builders launch it.  Each call owns its buffers: they are filled with a fixed finite
 // poison value first (MF_NN_POISON_*), the input view is loaded over it, and `y_full` hands the whole padded output buffer back, so a test sees
 // every element an op wrote outside its view (halo ring, neighbouring channels of a wider buffer, tokens past a prefix).
-// mf_act_q_encode is the same kind of seam for the producers of the f16 + FP6-block activation format (mf_aux.hip): it hands back the raw planes.
+// mf_conv_view_forward and mf_attention_view_forward launch a conv layer and the fused attention on views the same way (sequence layers, token prefixes,
+// packed q | k | v).  mf_act_q_encode is the same kind of seam for the producers of the f16 + FP6-block activation format (mf_aux.hip): it hands back the raw planes.
 #include "mf_nn.h"
 #include "mf_aux.h"
 #include <cmath>
@@ -82,7 +83,30 @@ struct PlanGuard {
     ~PlanGuard() { mf_conv_plan_destroy(&p); }
 };
 
-#define API_PREC(name)                                                                                                                    \
+// the halo ring of every item, and the allocation's tail, as mf_actbuf_alloc leaves them: zero (a conv reads its padding there)
+__global__ __launch_bounds__(256) void k_zero_ring(bf16_t* hi, bf16_t* lo, int C, int H, int W, int halo, int64_t n, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    if (i < n) {
+        const int64_t px = i / C;
+        const int Wp = W + 2 * halo, Hp = H + 2 * halo;
+        const int col = (int)(px % Wp), row = (int)((px / Wp) % Hp);
+        if (col >= halo && col < halo + W && row >= halo && row < halo + H) return;
+    }
+    hi[i] = 0;
+    if (lo) lo[i] = 0;
+}
+
+int zero_ring(const PBuf& b, hipStream_t s) {
+    const int64_t total = b.n + 64;
+    hipLaunchKernelGGL(k_zero_ring, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, b.b.hi, b.b.lo, b.b.C, b.b.H, b.b.W, b.b.halo, b.n, total);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+bool same_buffer(const mf_rows_geom* a, const mf_rows_geom* b) { return a->cbuf == b->cbuf && a->h == b->h && a->w == b->w && a->halo == b->halo; }
+
+#define API_PREC(name)                                                                                                                  \
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, name ": unknown precision %d", precision);                       \
     const bool x3 = precision == MF_PREC_BF16X3;                                                                                          \
     hipStream_t s = (hipStream_t)stream;                                                                                                  \
@@ -216,6 +240,88 @@ extern "C" int mf_attention_composite_forward(const float* q, const float* k, co
     if ((rc = mf_attention_composite(&ps.p, &pv.p, &sc.b, &pm.b, bq.all(), bk.all(), bv.all(), bo.all(), heads, batch, precision, s))) return rc;
     if ((rc = mf_rows_to_f32(bo.all(), out, batch, s))) return rc;
     if ((rc = bo.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+// The fused attention on views, as the model builders launch it: q | k | v slices of one packed buffer (self-attention), q alone beside a shared k | v
+// buffer (cross-attention), or three buffers; every buffer poisoned before its views are loaded, so the four row pitches, offsets and batch strides differ
+// wherever the geometries do.
+extern "C" int mf_attention_view_forward(const float* q, const float* k, const float* v, float* out, const mf_rows_geom* gq, const mf_rows_geom* gk,
+                                         const mf_rows_geom* gv, const mf_rows_geom* go, int packing, int batch, int heads, int tq, int tk, int precision,
+                                         float* y_full, void* stream) {
+    MF_REQUIRE(q && k && v && out && geom_ok(gq) && geom_ok(gk) && geom_ok(gv) && geom_ok(go) && batch > 0 && heads > 0,
+               "attention_view_forward: null argument or bad geometry");
+    MF_REQUIRE(packing >= 0 && packing <= 2, "attention_view_forward: packing %d (0: three buffers, 1: q alone, k and v share one, 2: one buffer)", packing);
+    MF_REQUIRE(packing == 0 || same_buffer(gk, gv), "attention_view_forward: k and v share a buffer, their geometries must name the same one");
+    MF_REQUIRE(packing != 2 || same_buffer(gq, gk), "attention_view_forward: q, k and v share a buffer (Tq == Tk), their geometries must name the same one");
+    auto apart = [](const mf_rows_geom* a, const mf_rows_geom* b) { return a->coff + a->c <= b->coff || b->coff + b->c <= a->coff; };
+    MF_REQUIRE(packing == 0 || apart(gk, gv), "attention_view_forward: the k and v views of one buffer overlap");
+    MF_REQUIRE(packing != 2 || (apart(gq, gk) && apart(gq, gv)), "attention_view_forward: the q view overlaps k or v");
+    API_PREC("attention_view_forward");
+    PBuf bq, bk, bv, bo;
+    if ((rc = bq.alloc(*gq, batch, x3, s)) || (rc = bo.alloc(*go, batch, x3, s))) return rc;
+    if (packing < 2 && (rc = bk.alloc(*gk, batch, x3, s))) return rc;
+    if (packing < 1 && (rc = bv.alloc(*gv, batch, x3, s))) return rc;
+    const PBuf& pk = packing == 2 ? bq : bk;
+    const PBuf& pv = packing == 0 ? bv : pk;
+    if ((rc = mf_rows_from_f32(q, nullptr, bq.view(*gq), batch, s))) return rc;
+    if ((rc = mf_rows_from_f32(k, nullptr, pk.view(*gk), batch, s))) return rc;
+    if ((rc = mf_rows_from_f32(v, nullptr, pv.view(*gv), batch, s))) return rc;
+    if ((rc = mf_attention(bq.view(*gq), pk.view(*gk), pv.view(*gv), bo.view(*go), heads, batch, precision, s, tq, tk))) return rc;
+    if ((rc = mf_rows_to_f32(bo.view(*go), out, batch, s))) return rc;
+    if ((rc = bo.full(y_full, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+// One mf_conv_plan_create layer (or `groups` of them, one per channel group, as mf_wav2vec2::body launches its positional convolution) through
+// mf_conv_launch on views: the input in a view of a buffer whose other channels are poisoned and whose halo ring is zero, the output in a view of a fully
+// poisoned buffer, the residual in a view of a third buffer -- or, with desc->residual set and no gr, the input's own view.
+extern "C" int mf_conv_view_forward(const mf_conv2d_desc* desc, const float* weight, const float* bias, const float* x, const float* res, float* y,
+                                    const mf_rows_geom* gx, const mf_rows_geom* gy, const mf_rows_geom* gr, int batch, int tokens, int groups,
+                                    int only_group, const int* pin, int* info, int precision, float* y_full, void* stream) {
+    MF_REQUIRE(desc && weight && x && y && geom_ok(gx) && geom_ok(gy) && batch > 0, "conv_view_forward: null argument or bad geometry");
+    MF_REQUIRE(groups > 0 && only_group >= -1 && only_group < groups, "conv_view_forward: group %d of %d", only_group, groups);
+    MF_REQUIRE((res != nullptr) == (gr != nullptr) && (!gr || geom_ok(gr)), "conv_view_forward: the residual and its geometry come together");
+    MF_REQUIRE(!gr || desc->residual, "conv_view_forward: a residual operand needs desc->residual 1 (before the activation) or 2 (after it)");
+    const int n_out = desc->act == 5 ? desc->cout / 2 : desc->cout;
+    MF_REQUIRE(gx->c % groups == 0 && gy->c == groups * n_out && (!gr || gr->c == gy->c),
+               "conv_view_forward: views of %d (in), %d (out) channels for %d groups of %d output channels", gx->c, gy->c, groups, n_out);
+    API_PREC("conv_view_forward");
+    const int gci = gx->c / groups;
+    PBuf bx, by, br;
+    if ((rc = bx.alloc(*gx, batch, x3, s)) || (rc = zero_ring(bx, s)) || (rc = by.alloc(*gy, batch, x3, s))) return rc;
+    if (gr && (rc = br.alloc(*gr, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*gx), batch, s))) return rc;
+    if (gr && (rc = mf_rows_from_f32(res, nullptr, br.view(*gr), batch, s))) return rc;
+    const size_t wsz = (size_t)desc->cout * desc->cin * desc->kh * desc->kw;
+    bool reported = false;
+    for (int g = 0; g < groups; ++g) {
+        if (only_group >= 0 && g != only_group) continue;
+        PlanGuard pg;
+        if ((rc = mf_conv_plan_create(&pg.p, *desc, weight + g * wsz, bias ? bias + (size_t)g * desc->cout : nullptr, nullptr, nullptr, nullptr, nullptr, precision)))
+            return rc;
+        if ((rc = mf_conv_bind(&pg.p, bx.b))) return rc;
+        if (pin && (pin[0] || pin[1] || pin[2] || pin[3] || pin[4] || pin[5]) &&
+            (rc = mf_conv_pin(&pg.p, batch, ConvTuned{ConvTile{pin[0], pin[1], pin[2], pin[3], pin[4]}, pin[5]})))
+            return rc;
+        const ActView in{&bx.b, gx->coff + g * gci, gci}, out{&by.b, gy->coff + g * n_out, n_out};
+        ActView r{};
+        if (gr) r = ActView{&br.b, gr->coff + g * n_out, n_out};
+        else if (desc->residual) r = ActView{&bx.b, in.coff, n_out};
+        if ((rc = mf_conv_launch(&pg.p, in, out, r, batch, s, tokens))) return rc;
+        if (info && !reported) {
+            ConvLaunchCfg c;
+            if ((rc = mf_conv_resolve(&pg.p, batch, tokens, 0, &c))) return rc;
+            const int v[11] = {c.family, c.tile.bm, c.tile.bn, c.tile.wgm, c.tile.wgn, c.tile.nsplit, c.ld, c.bk, c.nphase, c.stats, c.pinned ? 1 : 0};
+            for (int i = 0; i < 11; ++i) info[i] = v[i];
+            reported = true;
+        }
+        MF_HIP(hipStreamSynchronize(s));          // the plan (weights, split-K workspace) goes away with this iteration
+    }
+    if ((rc = mf_rows_to_f32(by.view(*gy), y, batch, s))) return rc;
+    if ((rc = by.full(y_full, s))) return rc;
     MF_HIP(hipStreamSynchronize(s));
     return MF_OK;
 }

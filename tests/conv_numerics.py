@@ -1,4 +1,4 @@
-"""Storage-format emulation and float64 references shared by the conv tests (test_net_ops.py, test_conv_configs.py).
+"""Storage-format emulation and float64 references shared by the conv tests (test_net_ops.py, test_conv_configs.py, test_seq_conv_views.py).
 
 - U[prec]: relative rounding of one stored value; F32: fp32 unit roundoff.  `stored` / `exact` emulate the (hi, lo) bf16 planes and bf16 alone.
 - conv_ref: the full mf_conv2d_desc in float64 -- Conv2d or ConvTranspose2d (output_padding), pad_hi, nearest-2x upsample, eval BatchNorm folded into the
@@ -77,11 +77,12 @@ def max_phase_taps(d):
     return kh * kw
 
 
-def conv_ref(x, w, b, d, bn=None):
+def conv_ref(x, w, b, d, bn=None, res=None):
     """float64 forward of one mf_conv2d_desc `d` (dict with the desc's field names) -> (want, mag) where
          want  the layer's output,
-         mag   {"pre": conv(|x|, |w'|) + |b'| (+ |x| for residual 1) of the pre-activation, "res": |x| added after the activation (residual 2) or 0,
-                "v", "u": GEGLU only, the value and gate halves of the pre-activation, "mv", "mu": their magnitudes}.
+         mag   {"pre": conv(|x|, |w'|) + |b'| (+ |r| for residual 1) of the pre-activation, "res": |r| added after the activation (residual 2) or 0,
+                "v", "u": GEGLU only, the value and gate halves of the pre-activation, "mv", "mu": their magnitudes},
+         r     the residual operand: `res` ([B, cout, Ho, Wo], a tensor of its own, as a network hands a layer the positional table or another branch), or x.
     x: [B, cin, H, W]; w: [cout, cin, kh, kw] (Conv2d) or [cin, cout, kh, kw] (ConvTranspose2d); b: [cout] or None; bn: (gamma, beta, mean, var) or None.
     Tensors of any device; computed in float64 there."""
     dev = x.device if torch.is_tensor(x) else "cpu"
@@ -106,10 +107,11 @@ def conv_ref(x, w, b, d, bn=None):
         return F.conv2d(xx, ww, bb, stride=st, padding=pad)
 
     pre, mpre = lin(x, w, b), lin(x.abs(), w.abs(), b.abs())
+    r = x if res is None else t(res)
     res = d.get("residual", 0)
     if res == 1:
-        pre, mpre = pre + x, mpre + x.abs()
-    mag = {"pre": mpre, "res": x.abs() if res == 2 else torch.zeros((), dtype=torch.float64, device=dev)}
+        pre, mpre = pre + r, mpre + r.abs()
+    mag = {"pre": mpre, "res": r.abs() if res == 2 else torch.zeros((), dtype=torch.float64, device=dev)}
     if d["act"] == 5:
         h = cout // 2
         v, u = pre[:, :h], pre[:, h:]
@@ -117,8 +119,24 @@ def conv_ref(x, w, b, d, bn=None):
         return v * gelu64(u), mag
     want = act64(pre, d["act"])
     if res == 2:
-        want = want + x
+        want = want + r
     return want, mag
+
+
+def grouped_seq_ref(x, w, b, d, res=None):
+    """G layers of desc `d`, one per channel group, side by side: group g reads channels [g cin, (g + 1) cin) of x [B, G cin, H, W] with w[g] ([G, cout, cin,
+    kh, kw]) and b[g] ([G, cout] or None) and writes channels [g cout, (g + 1) cout) -- conv_ref per group, the outputs and magnitudes concatenated.  The
+    residual of group g is its slice of `res` ([B, G cout, Ho, Wo]) or, without one, of x: the form of wav2vec2's positional convolution (one launch per group
+    of a grouped Conv1d, GELU, then + the hidden state the layer read)."""
+    G, cin, cout = len(w), d["cin"], d["cout"]
+    wants, pres, ress = [], [], []
+    for g in range(G):
+        want, mag = conv_ref(x[:, g * cin:(g + 1) * cin], w[g], None if b is None else b[g], d,
+                             res=None if res is None else res[:, g * cout:(g + 1) * cout])
+        wants.append(want)
+        pres.append(mag["pre"])
+        ress.append(mag["res"].expand_as(want))
+    return torch.cat(wants, 1), {"pre": torch.cat(pres, 1), "res": torch.cat(ress, 1)}
 
 
 # Lipschitz constants of the activations (act 0 .. 4): GELU's derivative peaks at 1.1289 (t = sqrt(2)), SiLU's at 1.0998 (t = 2.3994), sigmoid's at 1/4
