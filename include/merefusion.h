@@ -733,6 +733,16 @@ int mf_paste_frames(const void* res, int res_is_f32, int res_h, int res_w, const
 /* cv2.resize(src, (dw, dh)) for uint8 [sh][sw][3] with the default INTER_LINEAR (lipreal.py:211, musereal.py:241). */
 int mf_resize_linear_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, void* stream);
 
+/* ---- finished frames as planar YUV 4:2:0 (I420): what the encoder behind `VideoFrame` wants ---------- */
+/* frames: device uint8 [n_frames][H][W][3], packed, rgb_order 0: BGR (mf_paste_frames' output), 1: RGB (mf_nerf_frame_out's);
+ * out: device uint8 [n_frames][H * 3 / 2][W] -- per frame H rows of Y, then the H/2 x W/2 Cb plane as bytes, then Cr: the
+ * array `VideoFrame.from_ndarray(a, format="yuv420p")` takes.  BT.601 studio swing in 16.16 fixed point, chroma from the
+ * sum of each 2 x 2 block (csrc/mf_i420.hip states the integers; parity with libswscale is unpinned).  One launch for the
+ * whole block: 8-pixel strips per thread when W % 8 == 0 and both pointers are 4-byte aligned, else 2 x 2 blocks with byte
+ * accesses; the bytes are the same.  Refuses null pointers, n_frames < 1, non-positive or odd H / W and an rgb_order other
+ * than 0 / 1 (MF_ERR_INVALID, the value named in mf_last_error) before anything is launched. */
+int mf_frames_to_i420(const uint8_t* frames, int n_frames, int H, int W, int rgb_order, uint8_t* out, void* stream);
+
 /* ---- ER-NeRF audio front-end: wav2vec2 / HuBERT CTC network ----------------------------------- */
 /* Replaces `self.processor(frame, ...)` + `self.model(inputs.input_values)` of NerfASR.__frame_to_text (nerfasr.py:128-143):
  * transformers' Wav2Vec2FeatureExtractor normalisation, then Wav2Vec2ForCTC (`.logits`) or HubertModel (`.last_hidden_state`, out_hidden = 1)

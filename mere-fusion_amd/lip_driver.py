@@ -245,14 +245,16 @@ class LipEndToEndScheduler(PipelinedScheduler):
     Everything else (picking, reservation, deferral episodes in `ring_full`, publish order, the waiter thread, close(), single_stream) is PipelinedScheduler's code.
     A window slides when its batch is PICKED, not when it is submitted, and once (`_advance`): it is one device row per session, and several batches may be queued."""
 
-    def __init__(self, batcher, frontends=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
+    def __init__(self, batcher, frontends=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed"):
         fes = batcher.frontends() if frontends is None else list(frontends)
         if len(fes) != len(batcher.sessions):                             # before anything (streams, the parent's state) is created
             raise RuntimeError("one LipASRDeviceFrontend per session is required")
         for k, fe in enumerate(fes):
             if not isinstance(fe, LipASRDeviceFrontend) or fe.pool is not fes[0].pool or fe.row != k or fe.batch_size != batcher.batch_size:
                 raise RuntimeError(f"frontend {k}: one LipASRDeviceFrontend per session, row k of one pool, is required (LipBatcher.frontends())")
-        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream)
+        if frame_format == "i420" and not batcher.paste:
+            raise RuntimeError("LipEndToEndScheduler: frame_format='i420' converts the pasted uint8 frames; the batcher was built with paste=False (fp32 crops)")
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
         self.frontends, self.windows = fes, fes[0].pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):

@@ -154,10 +154,10 @@ class EndToEndScheduler(PipelinedScheduler):
     Stages can be switched off individually to price them (bench.py `paced_sessions.stages`)."""
 
     def __init__(self, batcher, frontends, audio_processor, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, fixed_chunks=None,
-                 asr_stream=True, single_stream=False):
+                 asr_stream=True, single_stream=False, frame_format="packed"):
         if len(frontends) != len(batcher.sessions):
             raise RuntimeError("one MuseASRFrontend per session is required")
-        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream)
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
         # (fixed_chunks: measurement only, this [B, 50, 384] tensor instead of the Whisper stage)
         self.fixed_chunks, self.frontends, self.audio_processor = fixed_chunks, list(frontends), audio_processor
         # The Whisper front-end of a step on its OWN stream: with two steps in flight it runs beside the previous step's VAE instead of between that VAE and

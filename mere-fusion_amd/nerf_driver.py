@@ -16,9 +16,10 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ernerf import frontend
 from .serving import mirror_index, refuse
+from .transport import is_i420_shape
 
 
 def loader_indices(size, index):
@@ -137,9 +138,12 @@ class NerfSession:
                    "mf_nerf_frame_background")
         return out
 
-    def frame_out(self, image, body=None, out=None):
+    def frame_out(self, image, body=None, out=None, i420=False):
         """The uint8 RGB frame: `image` [H, W, 3] fp32 (or None: `body` alone, channels reversed) resized to the GUI size, over `body` at the offset.
-        out: the contiguous uint8 device tensor of the frame's size to write instead of a new one (nerf_serving.NerfBatcher: one block per step)."""
+        out: the contiguous uint8 device tensor of the frame's size to write instead of a new one (nerf_serving.NerfBatcher: one block per step).
+        i420: the frame as planar YUV 4:2:0 instead, uint8 [FH * 3 / 2, FW] (ops.frames_to_i420 behind the same launch; `out` then has that shape)."""
+        if i420:
+            return ops.frames_to_i420(self.frame_out(image, body), order="rgb", out=out)
         dev = self.poses.device
         FH, FW = (self.GH, self.GW) if body is None else (int(body.shape[0]), int(body.shape[1]))
         if out is None:
@@ -211,11 +215,18 @@ class NerfSession:
             image = image.float().contiguous()
         return self.frame_out(image, job["body"], **({} if out is None else {"out": out}))
 
-    def step_to_ring(self, ring, auds, audio_frames, audiotype=(0, 0)):
+    def step_to_ring(self, ring, auds, audio_frames, audiotype=(0, 0), i420=False):
         """step() and the frame into `ring` (transport.FrameRing): one DMA into the slot behind the frame's kernels, one stream fence, then the consumer's
         `(frame, idx, audio_frames)` tuple is published -- idx the frame's mirrored index, audio_frames its two (pcm, type) pairs.  A custom-video frame
-        takes the same way.  Returns (the device frame, idx)."""
+        takes the same way.  i420: the frame is converted to planar YUV 4:2:0 on the same stream and travels as uint8 [h * 3 / 2, w] (ops.frames_to_i420, RGB
+        order; the consumer's line is `VideoFrame.from_ndarray(frame, format="yuv420p")`); a ring whose slots are no such block (transport.i420_shape) is
+        refused before the session moves.  Returns (the device frame as it entered the ring, idx)."""
+        if i420 and not is_i420_shape(tuple(getattr(ring, "frame_shape", ()))):
+            _refuse(f"step_to_ring(i420=True): the ring has slots of shape {tuple(getattr(ring, 'frame_shape', ()))}, which is no [H * 3 / 2, W] plane block "
+                    f"(FrameRing(slots, transport.i420_shape(H, W)))")
         frame = self.step(auds, audiotype)
+        if i420:
+            frame = ops.frames_to_i420(frame, order="rgb")
         idx = self.last_index
         tok = ring.begin_batch(frame[None], [idx])
         try:

@@ -216,6 +216,11 @@ class NerfBatcher:
     and still keep their own EMA.  A session or model without these entry points, and everyone under MF_NERF_BATCH=0, takes one `step` per frame."""
 
     MAX_FRAMES_PER_RENDER = 64          # mf_nerf_head_batch's limit per call
+    frame_order = "rgb"                 # channel 0 of the uint8 frames a step returns (mf_nerf_frame_out)
+
+    def frame_hw(self, k):
+        """(H, W) of session k's frames"""
+        return self.out_shape[k][:2]
 
     def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32):
         who = "NerfBatcher"
@@ -389,11 +394,11 @@ class NerfEndToEndScheduler(PipelinedScheduler):
     ER-NeRF has no silent-batch skip: an all-silent batch renders like any other.  Everything else (picking, reservation, deferral, publish order, the waiter
     thread, close(), single_stream) is PipelinedScheduler's code.  A session's features advance when its batch is PICKED, not when it is submitted, and once."""
 
-    def __init__(self, batcher, pool=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
+    def __init__(self, batcher, pool=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed"):
         pool = batcher.pool if pool is None else pool
         if not isinstance(pool, NerfFeaturePool) or pool.n_sessions != len(batcher.sessions):     # before anything (streams, the parent's state) is created
             _refuse("NerfEndToEndScheduler", "a NerfFeaturePool with one row per session of the batcher is required")
-        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream)
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
         self.pool = pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):

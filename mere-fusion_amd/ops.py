@@ -135,6 +135,38 @@ def melspec_windows(wav, starts, pad_mode, out=None):
     return out
 
 
+FRAME_ORDERS = {"bgr": 0, "rgb": 1}
+
+
+def frames_to_i420(frames, order="bgr", out=None):
+    """Finished packed frames as planar YUV 4:2:0 in one launch (mf_frames_to_i420; the integers are in csrc/mf_i420.hip): frames contiguous uint8 [B, H, W, 3] or
+    [H, W, 3] on the device, channels in `order` ("bgr": the paste-back's frames, "rgb": ER-NeRF's) -> uint8 [B, H * 3 / 2, W] or [H * 3 / 2, W], per frame the
+    array `VideoFrame.from_ndarray(a, format="yuv420p")` takes.  H and W must be even.  out: the contiguous uint8 device tensor of that shape to write."""
+    if not torch.is_tensor(frames):
+        raise RuntimeError(f"frames_to_i420: expected a uint8 device tensor, got {type(frames).__name__}")
+    _require_cuda("frames_to_i420", frames)
+    if order not in FRAME_ORDERS:
+        raise RuntimeError(f"frames_to_i420: order must be 'bgr' or 'rgb', got {order!r}")
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise RuntimeError(f"frames_to_i420: frames must be contiguous uint8 [B, H, W, 3] or [H, W, 3], got {frames.dtype} {tuple(frames.shape)}"
+                           f"{'' if frames.is_contiguous() else ' (not contiguous)'}")
+    H, W = int(frames.shape[-3]), int(frames.shape[-2])
+    B = int(frames.shape[0]) if frames.dim() == 4 else 1
+    if H % 2 or W % 2:
+        raise RuntimeError(f"frames_to_i420: frame size {H} x {W} (H x W) is odd; 4:2:0 chroma covers 2 x 2 blocks")
+    if B < 1 or H < 2 or W < 2:
+        raise RuntimeError(f"frames_to_i420: nothing to convert in {tuple(frames.shape)}")
+    shape = ((B,) if frames.dim() == 4 else ()) + (H * 3 // 2, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.is_cuda and out.device == frames.device and out.is_contiguous() and tuple(out.shape) == shape):
+        what = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise RuntimeError(f"frames_to_i420: out must be a contiguous uint8 tensor {shape} on {frames.device}, got {what}")
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.lib().mf_frames_to_i420(frames.data_ptr(), B, H, W, FRAME_ORDERS[order], out.data_ptr(), _stream_ptr(frames.device)), "frames_to_i420")
+    return out
+
+
 def _ints(v):
     v = [int(x) for x in v]
     return (C.c_int * len(v))(*v), len(v)

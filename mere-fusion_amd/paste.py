@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import frames_to_i420                                      # noqa: F401  (re-exported: the frames' last launch before the ring)
 
 
 def _dev_u8(x, device):
@@ -80,6 +81,13 @@ class AvatarFrames:
                                                   self.n, self.H, self.W, jobs, B, out.data_ptr(),
                                                   C.c_void_p(torch.cuda.current_stream(res.device).cuda_stream)), "paste_frames")
         return out
+
+    def paste_i420(self, res, indices, out=None):
+        """paste() and the composed BGR frames as planar YUV 4:2:0, both launches on the caller's stream: uint8 [B, H * 3 / 2, W] (ops.frames_to_i420; H and W
+        must be even).  out: the tensor of that shape to write."""
+        if self.H % 2 or self.W % 2:
+            raise RuntimeError(f"paste_i420: the avatar's frames are {self.H} x {self.W} (H x W); 4:2:0 needs even sizes")
+        return frames_to_i420(self.paste(res, indices), order="bgr", out=out)
 
 
 def resize_linear_u8(src, dw, dh):

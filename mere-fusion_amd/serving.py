@@ -13,6 +13,8 @@ from collections import deque
 
 import torch
 
+from .transport import i420_shape, is_i420_shape
+
 
 def refuse(who, msg):
     raise RuntimeError(f"{who}: {msg}")
@@ -68,6 +70,13 @@ def step_sessions(batcher, inputs, only, skip_none=True):
 class PooledBatcher:
     """N sessions (SessionWalks) through one set of handles per step, every session's cached frames in one pool.  A model's batcher says: _check_input(k, x), which
     refuses session k's input if the forward cannot take it; _forward(xs, rows): the active sessions' inputs (`cat_inputs` joins them) and pool rows -> frames."""
+
+    frame_order = "bgr"                                                  # channel 0 of the uint8 frames a step returns (Wav2Lip and MuseTalk: cv2's order)
+
+    def frame_hw(self, k):
+        """(H, W) of session k's pasted frames; None where the size is not known before a step (paste=False)"""
+        av = self.sessions[k].avatar_frames if self.paste else None
+        return None if av is None else (av.H, av.W)
 
     def _lay_out_pool(self):
         for k, s in enumerate(self.sessions):                            # every session's first row in the pool its frames are concatenated into
@@ -194,11 +203,18 @@ class PipelinedScheduler(SessionScheduler):
     thread saw.  A step is: pick -> reserve ring places -> the model's audio stage -> batcher.step -> each session's frames leave through ITS FrameRing as
     (res_frame, idx, audio_frames) tuples (musereal.py:116,153; lipreal.py:104,136): the D2H runs on a copy stream behind the step (the next step's kernels do
     not wait for it) and the descriptors are published when its event is done.  run_once(now) -> finished batches [(k, frames_or_None, indices, latency_s)]:
-    latency = arrival -> descriptors published (rings given) or frames complete in HBM (rings=None).  With rings=None or single_stream=True no stream is created."""
+    latency = arrival -> descriptors published (rings given) or frames complete in HBM (rings=None).  With rings=None or single_stream=True no stream is created.
+    frame_format="i420": each session's uint8 [B, H, W, 3] block is converted to planar YUV 4:2:0 (ops.frames_to_i420, the batcher's `frame_order`) on the step's
+    stream right before its begin_batch, so the rings (built with transport.i420_shape) and the D2H carry 1.5 bytes per pixel and the consumer's line is
+    `VideoFrame.from_ndarray(frame, format="yuv420p")`; run_once then reports those frames.  Nothing else changes: silent batches still travel as None."""
 
-    def __init__(self, batcher, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False):
+    FRAME_FORMATS = ("packed", "i420")
+
+    def __init__(self, batcher, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed"):
+        self._check_frame_format(batcher, rings, frame_format)       # before anything (streams, the parent's state) is created
         super().__init__(batcher, period_s=period_s, hold_s=hold_s, clock=clock)
         self.rings = rings
+        self.frame_format = frame_format
         self.depth = max(int(depth), 1)                              # steps in flight: the one computing + the one whose frames are being copied
         # single_stream: a model's audio stage, the step and the D2H of its frames all on the caller's stream -- no cross-stream event wait anywhere (with handles
         # created under MF_NO_GRAPH=2 the whole rank is one launch chain: no runtime thread spins, see mf_musetalk.hip); costs the copy / Whisper overlap
@@ -216,6 +232,40 @@ class PipelinedScheduler(SessionScheduler):
         self.ring_full = 0                                           # deferral EPISODES (a session found its ring full), not polls
         self._deferred = {}                                          # session -> time at which it is offered again even if its ring still looks full
         self._busy_until = 0.0
+
+    @classmethod
+    def _check_frame_format(cls, batcher, rings, frame_format):
+        """frame_format "i420": every session's rings carry planar YUV 4:2:0 slots (transport.i420_shape) and the batcher says which channel its frames start with
+        (`frame_order`).  A ring of another slot shape is refused HERE, not at the first copy.  "packed" (the default) checks nothing: the frames leave as they are."""
+        who = cls.__name__
+        if frame_format not in cls.FRAME_FORMATS:
+            refuse(who, f"frame_format must be one of {cls.FRAME_FORMATS}, got {frame_format!r}")
+        if frame_format == "packed":
+            return
+        if rings is None:
+            refuse(who, "frame_format='i420' is what the rings carry; without rings the frames stay packed in HBM")
+        if getattr(batcher, "frame_order", None) not in ("bgr", "rgb"):
+            refuse(who, f"frame_format='i420': {type(batcher).__name__} does not state its frames' channel order (frame_order = 'bgr' or 'rgb')")
+        if len(rings) != len(batcher.sessions):
+            refuse(who, f"{len(rings)} rings for {len(batcher.sessions)} sessions")
+        frame_hw = getattr(batcher, "frame_hw", None)
+        for k, ring in enumerate(rings):
+            have = tuple(getattr(ring, "frame_shape", ()))
+            hw = frame_hw(k) if frame_hw is not None else None
+            if hw is not None and (hw[0] % 2 or hw[1] % 2):
+                refuse(who, f"frame_format='i420': session {k}'s frames are {hw[0]} x {hw[1]} (H x W); 4:2:0 needs even sizes")
+            if hw is not None and have != i420_shape(*hw):
+                refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}; session {k}'s {hw[0]} x {hw[1]} frames need {i420_shape(*hw)} "
+                            f"(FrameRing(slots, transport.i420_shape(H, W)))")
+            if not is_i420_shape(have):
+                refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}, which is no [H * 3 / 2, W] plane block (FrameRing(slots, transport.i420_shape(H, W)))")
+
+    def _delivered(self, fr):
+        """the frames of one session as they enter its ring: as they are, or (frame_format "i420") converted on the step's stream, one launch for the block"""
+        if fr is None or self.frame_format == "packed":
+            return fr
+        from . import ops
+        return ops.frames_to_i420(fr, order=self.batcher.frame_order)
 
     @staticmethod
     def _wait_loop(evq, wake, errors):
@@ -366,6 +416,8 @@ class PipelinedScheduler(SessionScheduler):
             ev = torch.cuda.Event()
             if self.rings is not None:
                 cur = torch.cuda.current_stream(dev)
+                for k in ks:                                             # (i420: each session's block is converted on the step's stream, before the copy stream waits)
+                    out[k] = (self._delivered(out[k][0]), out[k][1])
                 if self.copy_stream is not None:
                     self.copy_stream.wait_stream(cur)
                 for k in ks:
