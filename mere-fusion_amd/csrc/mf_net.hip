@@ -10,12 +10,10 @@
 // The op list is one hipGraph per batch size like the other stages (mf_graph_run.h).
 #include "mf_nn.h"
 #include "mf_aux.h"
-#include "mf_graph_run.h"
+#include "mf_schedule.h"
 #include "mf_net_planes.h"
 #include <cfloat>
 #include <cmath>
-#include <functional>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -136,31 +134,17 @@ struct mf_net {
     std::vector<std::unique_ptr<ActBuf>> bufs;
     std::vector<std::unique_ptr<ConvPlan>> plans;
     std::vector<float*> dev;
-    typedef std::function<int(int, hipStream_t)> Op;
-    std::vector<Op> ops;
-    struct Tunable { ConvPlan* p; ActView in, out, res; };
-    std::vector<Tunable> tunables;
-    std::vector<std::string> names;
-    std::vector<double> flops;
-    GraphRunner graph;
+    Schedule sch;                                                          // the op list and its runner (no side branches here: it never forks)
     void* scratch = nullptr;                                               // mf_net_scratch: the candidate lists of mf_s3fd_detect
     size_t scratch_bytes = 0;
 
     ~mf_net() {
-        graph.drop_all();
+        sch.graph.drop_all();
         for (auto& p : plans) mf_conv_plan_destroy(p.get());
         for (auto& b : bufs) mf_actbuf_free(b.get());
         for (float* d : dev) (void)hipFree(d);
     }
     ActBuf* B(int id) { return id >= 0 && id < (int)bufs.size() ? bufs[id].get() : nullptr; }
-    int run_body(int batch, hipStream_t s) {
-        for (auto& op : ops) { int rc = op(batch, s); if (rc) return rc; }
-        return MF_OK;
-    }
-    int measure(int batch, hipStream_t s) {
-        for (auto& t : tunables) { int rc = mf_conv_tune(t.p, t.in, t.out, t.res, batch, s); if (rc) return rc; }
-        return MF_OK;
-    }
 };
 
 #define NET_BUF(var, id) ActBuf* var = h->B(id); MF_REQUIRE(var, "net: no buffer %d", id)
@@ -170,7 +154,7 @@ extern "C" int mf_net_create(int max_batch, int precision, mf_net** out) {
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "net_create: unknown precision %d", precision);
     std::unique_ptr<mf_net> h(new mf_net());
     h->precision = precision; h->cap = max_batch;
-    const int rc = h->graph.init(mf_no_graph_mode() == 0);   // eager for any non-zero MF_NO_GRAPH
+    const int rc = h->sch.init(mf_no_graph_mode() == 0, false);   // eager for any non-zero MF_NO_GRAPH
     if (rc) return rc;
     *out = h.release();
     return MF_OK;
@@ -203,10 +187,8 @@ extern "C" int mf_net_conv(mf_net* h, const mf_conv2d_desc* d, const float* weig
     if ((rc = mf_conv_bind(p, *ib))) return rc;
     const ActView in{ib, in_coff, (dd.cin + 7) / 8 * 8 <= ib->C - in_coff ? (dd.cin + 7) / 8 * 8 : dd.cin}, out{ob, out_coff, dd.cout};
     const ActView res = rb ? ActView{rb, res_coff, dd.cout} : ActView{};
-    h->ops.push_back([p, in, out, res](int B, hipStream_t s) { return mf_conv_launch(p, in, out, res, B, s); });
-    h->tunables.push_back(mf_net::Tunable{p, in, out, res});
-    h->names.push_back(name ? name : "conv");
-    h->flops.push_back(mf_conv_flops(p, 1));
+    const int op = h->sch.push(name ? name : "conv", "", mf_conv_flops(p, 1), [p, in, out, res](int B, hipStream_t s) { return mf_conv_launch(p, in, out, res, B, s); });
+    h->sch.tunable(Schedule::Tunable{p, in, out, res, op});
     return MF_OK;
 }
 
@@ -218,13 +200,12 @@ extern "C" int mf_net_maxpool(mf_net* h, int in_buf, int out_buf, int k, int str
                ib->W + 2 * pad);
     MF_REQUIRE(ob->C == ib->C && ob->H == (ib->H + 2 * pad - k) / stride + 1 && ob->W == (ib->W + 2 * pad - k) / stride + 1,
                "net_maxpool: output buffer %dx%dx%d does not match floor((%dx%d + 2*%d - %d) / %d) + 1", ob->C, ob->H, ob->W, ib->H, ib->W, pad, k, stride);
-    h->ops.push_back([ib, ob, k, stride, pad](int B, hipStream_t s) {
+    h->sch.push("maxpool", "", 0.0, [ib, ob, k, stride, pad](int B, hipStream_t s) {
         const int64_t total = (int64_t)B * ob->H * ob->W * ob->C;
         hipLaunchKernelGGL(k_maxpool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pl_of(*ib), pl_of(*ob), k, stride, pad, total);
         MF_HIP(hipGetLastError());
         return MF_OK;
     });
-    h->names.push_back("maxpool"); h->flops.push_back(0.0);
     return MF_OK;
 }
 
@@ -236,13 +217,12 @@ extern "C" int mf_net_l2norm(mf_net* h, int in_buf, int out_buf, const float* we
     MF_HIP(hipMalloc(&dw, C * sizeof(float)));
     MF_HIP(hipMemcpy(dw, weight, C * sizeof(float), hipMemcpyHostToDevice));
     h->dev.push_back(dw);
-    h->ops.push_back([ib, ob, dw, C, eps](int B, hipStream_t s) {
+    h->sch.push("l2norm", "", 0.0, [ib, ob, dw, C, eps](int B, hipStream_t s) {
         const int64_t px = (int64_t)B * ib->H * ib->W;
         hipLaunchKernelGGL(k_l2norm, dim3((unsigned)((px + 3) / 4)), dim3(256), 0, s, pl_of(*ib), pl_of(*ob), dw, eps, C, px);
         MF_HIP(hipGetLastError());
         return MF_OK;
     });
-    h->names.push_back("l2norm"); h->flops.push_back(0.0);
     return MF_OK;
 }
 
@@ -250,12 +230,11 @@ extern "C" int mf_net_global_avgpool(mf_net* h, int in_buf, int in_coff, int C, 
     MF_REQUIRE(h && C > 0 && in_coff >= 0, "net_global_avgpool: bad argument");
     NET_BUF(ib, in_buf); NET_BUF(ob, out_buf);
     MF_REQUIRE(ob->H == 1 && ob->W == 1 && C <= ob->C && in_coff + C <= ib->C, "net_global_avgpool: the output must be a 1x1 map with >= %d channels", C);
-    h->ops.push_back([ib, ob, in_coff, C](int B, hipStream_t s) {
+    h->sch.push("global_avgpool", "", 0.0, [ib, ob, in_coff, C](int B, hipStream_t s) {
         hipLaunchKernelGGL(k_gap, dim3((C + 63) / 64, B), dim3(256), 0, s, pl_of(*ib), in_coff, C, pl_of(*ob));
         MF_HIP(hipGetLastError());
         return MF_OK;
     });
-    h->names.push_back("global_avgpool"); h->flops.push_back(0.0);
     return MF_OK;
 }
 
@@ -268,7 +247,7 @@ extern "C" int mf_net_scale_add(mf_net* h, int x_buf, int x_coff, int C, int s_b
     MF_REQUIRE(!sb || (sb->H == 1 && sb->W == 1 && sb->C >= C), "net_scale_add: the scale must be a 1x1 map");
     MF_REQUIRE(!vb || (vb->H == 1 && vb->W == 1 && vb->C >= C), "net_scale_add: the broadcast addend must be a 1x1 map");
     MF_REQUIRE(!tb || (tb->H == xb->H && tb->W == xb->W && t_coff + C <= tb->C), "net_scale_add: the addend must have x's size");
-    h->ops.push_back([=](int B, hipStream_t s) {
+    h->sch.push("scale_add", "", 0.0, [=](int B, hipStream_t s) {
         const int64_t total = (int64_t)B * xb->H * xb->W * C;
         const Pl none{};
         hipLaunchKernelGGL(k_scale_add, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pl_of(*xb), x_coff, sb ? pl_of(*sb) : none, tb ? pl_of(*tb) : none,
@@ -276,7 +255,6 @@ extern "C" int mf_net_scale_add(mf_net* h, int x_buf, int x_coff, int C, int s_b
         MF_HIP(hipGetLastError());
         return MF_OK;
     });
-    h->names.push_back("scale_add"); h->flops.push_back(0.0);
     return MF_OK;
 }
 
@@ -284,22 +262,19 @@ extern "C" int mf_net_upsample_nearest(mf_net* h, int in_buf, int out_buf) {
     MF_REQUIRE(h, "net_upsample_nearest: null handle");
     NET_BUF(ib, in_buf); NET_BUF(ob, out_buf);
     MF_REQUIRE(ib->C == ob->C, "net_upsample_nearest: channel mismatch");
-    h->ops.push_back([ib, ob](int B, hipStream_t s) {
+    h->sch.push("upsample_nearest", "", 0.0, [ib, ob](int B, hipStream_t s) {
         const int64_t total = (int64_t)B * ob->H * ob->W * ob->C;
         hipLaunchKernelGGL(k_up_nearest, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pl_of(*ib), pl_of(*ob), ob->C, total);
         MF_HIP(hipGetLastError());
         return MF_OK;
     });
-    h->names.push_back("upsample_nearest"); h->flops.push_back(0.0);
     return MF_OK;
 }
 
-extern "C" int mf_net_num_ops(const mf_net* h) { return h ? (int)h->ops.size() : 0; }
+extern "C" int mf_net_num_ops(const mf_net* h) { return h ? (int)h->sch.ops.size() : 0; }
 
 extern "C" double mf_net_flops_per_item(const mf_net* h) {
-    double f = 0.0;
-    if (h) for (double x : h->flops) f += x;
-    return f;
+    return h ? h->sch.flops_per_frame() : 0.0;
 }
 
 extern "C" int mf_net_set_input(mf_net* h, int buf, const float* nchw, int C, int batch, void* stream) {
@@ -311,13 +286,12 @@ extern "C" int mf_net_set_input(mf_net* h, int buf, const float* nchw, int C, in
 // the explicit warm-up (GraphRunner::retune): time every conv's launch configurations on the buffers the last run at this batch size filled
 extern "C" int mf_net_tune(mf_net* h, int batch, void* stream) {
     MF_REQUIRE(h && batch >= 1 && batch <= h->cap, "net_tune: batch %d exceeds the capacity %d", batch, h ? h->cap : 0);
-    return h->graph.retune(batch, (hipStream_t)stream, "net_tune: run the net once", [=](hipStream_t s) { return h->measure(batch, s); });
+    return h->sch.tune(batch, (hipStream_t)stream, "net_tune: run the net once");
 }
 
 extern "C" int mf_net_run(mf_net* h, int batch, void* stream) {
     MF_REQUIRE(h && batch >= 1 && batch <= h->cap, "net_run: batch %d exceeds the capacity %d", batch, h ? h->cap : 0);
-    return h->graph.run(batch, (hipStream_t)stream, [=](hipStream_t s) { return h->run_body(batch, s); },
-                        [=] { for (auto& t : h->tunables) mf_conv_tune_lookup(t.p, t.in, batch); }, [=](hipStream_t s) { return h->measure(batch, s); });
+    return h->sch.run(batch, (hipStream_t)stream);
 }
 
 extern "C" int mf_net_get_output(mf_net* h, int buf, int coff, int C, float* nchw, int batch, void* stream) {
