@@ -845,6 +845,34 @@ int mf_face_mask_finish(const uint8_t* masks, int mask_h, int mask_w, const int*
                         uint8_t* out, void* stream);
 void mf_net_destroy(mf_net* h);
 
+/* ---- avatar preparation: boxes and crops (mf_crop_resize.hip) ------------------------------------------------------------ */
+/* The steps between the detector and the generators that wav2lip/genavatar.py:80-96,119 and musetalk/mere_musetalk.py:293-296 do with numpy and cv2.  Nothing here
+ * synchronises with the host.  (ABI version 4: additions only) */
+typedef struct mf_crop_job {
+    int frame_index;
+    int x1, y1, x2, y2;                                 /* the crop frames[frame_index][y1:y2, x1:x2] */
+} mf_crop_job;
+/* genavatar.py:80-96 on what the detector left on the device: boxes device fp32 [n][max_det][5] and counts device int32 [n] as written by the detect entry points
+ * above.  Per frame the first kept box is clipped at 0 and truncated to int (face_detection/api.py:64-79), padded by pads = (top, bottom, left, right) (host int32 [4])
+ * and clamped to the H x W frame; then, unless smooth_T is 0 (`nosmooth`), get_smoothened_boxes(boxes, smooth_T) exactly as written: in place, sequential, Python's
+ * slice of a negative start when n < smooth_T, means as truncated integer quotients (the reference passes T = 5).  coords: device int32 [n][4] in the reference's
+ * (y1, y2, x1, x2) order; jobs: device mf_crop_job [n] (frame_index = i) for the resampler below; n_no_face: device int32, 1 value, the number of frames with
+ * counts < 1 (their raw box is (0, 0, 0, 0); the reference raises on the first of them). */
+int mf_avatar_lip_boxes(const float* boxes, const int* counts, int n, int max_det, int H, int W, const int* pads, int smooth_T, int* coords, mf_crop_job* jobs,
+                        int* n_no_face, void* stream);
+/* Batched crop + resample: dst[i] (device uint8 [n_jobs][dh][dw][3]) = the crop of jobs[i] out of frames (device uint8 [n_frames][H][W][3]) resized to dw x dh.
+ * jobs is DEVICE memory.  jobs_host, when not NULL, is the host's copy of the same table: every job is checked before anything is launched (frame index in range,
+ * crop not empty, crop inside the frame; MF_ERR_INVALID names the job).  With jobs_host NULL (a table the device wrote and the host never saw) the kernel makes the
+ * same checks and zero-fills the destination of a job that fails them.  n_frames * H * W * 3 must stay below 2^31.
+ * MF_CROP_LINEAR: cv::resize INTER_LINEAR for 8UC3 as the paste entry point above defines it, the coefficients formed in the kernel from each job's box; a crop of
+ * exactly 2 dw x 2 dh takes INTER_AREA's fast path, decided per job.  The four table arguments are ignored.
+ * MF_CROP_LANCZOS4: 8-tap separable integer resampler on per-job device tables xofs int32 [n_jobs][dw], xcoef int16 [n_jobs][dw][8], yofs int32 [n_jobs][dh],
+ * ycoef int16 [n_jobs][dh][8] (coefficients scaled by 2048): tap k of destination column d reads crop column clamp(xofs[d] + k, 0, crop width - 1), the same for
+ * rows; horizontal sums int32 without a shift; vertical sums int32 (wrapping), then (sum + (1 << 21)) >> 22 saturated to 0..255. */
+enum { MF_CROP_LINEAR = 0, MF_CROP_LANCZOS4 = 1 };
+int mf_crop_resize_u8(const uint8_t* frames, int n_frames, int H, int W, const mf_crop_job* jobs, const mf_crop_job* jobs_host, int n_jobs, uint8_t* dst, int dh,
+                      int dw, int mode, const int* xofs, const int16_t* xcoef, const int* yofs, const int16_t* ycoef, void* stream);
+
 /* ---- measurement seam --------------------------------------------------------------------------------------------- */
 /* TFLOP/s of the convolution's own arithmetic that a kernel issuing NOTHING but matrix instructions sustains on this device (random operand bits, 8
  * waves per CU) for the instruction mix one product costs: mix 0 = bf16x3 as shipped (3 bf16 MFMAs), 1 = f16 + two FP8 block-scaled correction

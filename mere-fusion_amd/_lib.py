@@ -71,6 +71,15 @@ class MfPasteJob(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("frame_index", "x1", "y1", "x2", "y2", "cx1", "cy1", "cx2", "cy2")] + [("mask", C.c_void_p)]
 
 
+class MfCropJob(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("frame_index", "x1", "y1", "x2", "y2")]
+
+
+MF_CROP_LINEAR = 0
+MF_CROP_LANCZOS4 = 1
+CROP_MODES = {"linear": MF_CROP_LINEAR, "lanczos4": MF_CROP_LANCZOS4}
+
+
 def tensor_array(state_dict):
     """(ctypes array of MfTensor, keep-alive list) for a {name: fp32 cpu tensor} dict."""
     import torch
@@ -148,6 +157,9 @@ SIGNATURES = {
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mf_face_mask_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_net_destroy": (None, [C.c_void_p]),
+    "mf_avatar_lip_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_crop_resize_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(MfCropJob), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_probe_mfma_ceiling": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "mf_unet_create": (C.c_int, [C.POINTER(MfUnetConfig), C.POINTER(MfTensor), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mf_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

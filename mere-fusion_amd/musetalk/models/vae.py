@@ -180,10 +180,19 @@ class VAE:
 
     def get_latents_for_unet(self, img, generator=None):
         """vae.py:110-122: [masked latents | reference latents] of one 256 x 256 BGR crop -> [1, 8, 32, 32] (what latents.pt holds).  Both
-        encoder passes run as one batch of two; the two noise draws keep the reference's order (masked first)."""
+        encoder passes run as one batch of two; the two noise draws keep the reference's order (masked first).
+        A uint8 DEVICE tensor [B, 256, 256, 3] (avatar/prepare.py's crops) is encoded where it is, without a host round trip -> [B, 8, 32, 32], row b what the
+        call for crop b alone returns when the calls are made in order with the same generator."""
         if isinstance(img, str):
             raise RuntimeError("VAE.get_latents_for_unet: pass the 256 x 256 BGR crop (mere_musetalk.py:302-303), not a file name")
-        crop = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
+        if torch.is_tensor(img) and img.is_cuda:
+            if img.dtype != torch.uint8 or img.dim() not in (3, 4):
+                raise RuntimeError(f"VAE.get_latents_for_unet: a device crop must be uint8 [B, 256, 256, 3] or [256, 256, 3], got {img.dtype} {tuple(img.shape)}")
+            if img.dim() == 4:
+                return torch.cat([self.get_latents_for_unet(img[b], generator) for b in range(img.shape[0])], dim=0)
+            crop = img
+        else:
+            crop = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
         mom_masked = self.encode_moments_device(image_u8_bgr=crop[None], half_mask=True)
         mom_ref = self.encode_moments_device(image_u8_bgr=crop[None], half_mask=False)
         return torch.cat([self._sample(mom_masked, self.scaling_factor, generator), self._sample(mom_ref, self.scaling_factor, generator)], dim=1)

@@ -5,6 +5,7 @@ device pointers to libmerefusion_hip.so.  Ops refuse CPU tensors -- there is no 
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -164,6 +165,100 @@ def frames_to_i420(frames, order="bgr", out=None):
         raise RuntimeError(f"frames_to_i420: out must be a contiguous uint8 tensor {shape} on {frames.device}, got {what}")
     with torch.cuda.device(frames.device):
         _lib.check(_lib.lib().mf_frames_to_i420(frames.data_ptr(), B, H, W, FRAME_ORDERS[order], out.data_ptr(), _stream_ptr(frames.device)), "frames_to_i420")
+    return out
+
+
+def lanczos4_tables(ssize, dsize):
+    """One axis of cv::resize's INTER_LANCZOS4 tables for 8-bit images (imgproc/src/resize.cpp, OpenCV 4.x as published): -> (ofs int32 [dsize], coef int16
+    [dsize, 8]).  Position fx = (float)((d + 0.5) * scale - 0.5), scale = 1 / (dsize / ssize) in double; s = floor(fx); tap k reads source index ofs + k with
+    ofs = s - 3 (clamped to the image by whoever applies the table); coefficients from `interpolateLanczos4(fx - s)`: float32 values from the eight-entry cos / sin
+    rotation table, 1e30 where the argument is (nearly) zero, normalised by their float32 sum, then saturate_cast<short>(c * 2048) (round half to even).
+    Built on the host so that the device resampler is integer-only (mf_crop_resize.hip)."""
+    f32, f64 = np.float32, np.float64
+    ssize, dsize = int(ssize), int(dsize)
+    if ssize < 1 or dsize < 1:
+        raise ValueError(f"lanczos4_tables: sizes must be positive, got {ssize} -> {dsize}")
+    scale = f64(1.0) / (f64(dsize) / f64(ssize))
+    fx = ((np.arange(dsize, dtype=f64) + 0.5) * scale - 0.5).astype(f32)
+    s = np.floor(fx).astype(np.int64)
+    x = (fx - s.astype(f32)).astype(f32)                                  # fx -= sx, in float
+    s45 = 0.70710678118654752440084436210485
+    cs = np.array([[1, 0], [-s45, -s45], [0, 1], [s45, -s45], [-1, 0], [s45, s45], [0, -1], [-s45, s45]], dtype=f64)
+    x3 = (x + f32(3)).astype(f32)
+    y0 = -x3.astype(f64) * np.pi * 0.25
+    s0, c0 = np.sin(y0), np.cos(y0)
+    coef = np.empty((dsize, 8), dtype=f32)
+    total = np.zeros(dsize, dtype=f32)
+    for i in range(8):
+        yi = (x3 - f32(i)).astype(f32)
+        y = -yi.astype(f64) * np.pi * 0.25
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = ((cs[i, 0] * s0 + cs[i, 1] * c0) / (y * y)).astype(f32)
+        coef[:, i] = np.where(np.abs(yi) >= f32(1e-6), c, f32(1e30))
+        total = (total + coef[:, i]).astype(f32)
+    coef = (coef * (f32(1.0) / total).astype(f32)[:, None]).astype(f32)
+    q = np.clip(np.rint((coef * f32(2048.0)).astype(f32)), -32768, 32767).astype(np.int16)
+    return (s - 3).astype(np.int32), q
+
+
+def crop_resize_u8(frames, boxes, size, mode="linear", frame_indices=None, out=None):
+    """Batched crop + resize in one launch (mf_crop_resize_u8): frames contiguous uint8 [n, H, W, 3] on the device -> uint8 [n_jobs, dh, dw, 3].
+    size: the destination as cv2.resize's dsize (dw, dh), or one int for a square.
+    boxes: a host list of n_jobs (x1, y1, x2, y2) crops, box i cut from frame frame_indices[i] (default i); or a device int32 tensor [n_jobs, 5] of
+    (frame_index, x1, y1, x2, y2) rows, as mf_avatar_lip_boxes writes (nothing is copied to the host; a row that is empty or outside the frame gives a zeroed crop).
+    mode "linear": cv2.resize's default INTER_LINEAR (mf_blend.hip's arithmetic), coefficients formed on the device.  mode "lanczos4": cv2.resize(...,
+    interpolation=cv2.INTER_LANCZOS4) as the integer two-pass on `lanczos4_tables`; the tables are built here from the boxes, which therefore must be host values.
+    out: the contiguous uint8 device tensor [n_jobs, dh, dw, 3] to write (a slice of a larger block is fine)."""
+    if not torch.is_tensor(frames):
+        raise RuntimeError(f"crop_resize_u8: expected a uint8 device tensor, got {type(frames).__name__}")
+    _require_cuda("crop_resize_u8", frames)
+    if mode not in _lib.CROP_MODES:
+        raise RuntimeError(f"crop_resize_u8: mode must be 'linear' or 'lanczos4', got {mode!r}")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise RuntimeError(f"crop_resize_u8: frames must be contiguous uint8 [n, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+    dw, dh = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    dev = frames.device
+    n, H, W = (int(v) for v in frames.shape[:3])
+    tables = [None] * 4
+    if torch.is_tensor(boxes):
+        if mode != "linear":
+            raise RuntimeError("crop_resize_u8: lanczos4 builds its tables on the host from the boxes; pass them as a host list")
+        if not (boxes.is_cuda and boxes.device == dev and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 5 and boxes.is_contiguous()):
+            raise RuntimeError(f"crop_resize_u8: a device job table must be contiguous int32 [n_jobs, 5] on {dev}, got {boxes.dtype} {tuple(boxes.shape)} on {boxes.device}")
+        jobs_dev, jobs_host, n_jobs = boxes, None, int(boxes.shape[0])
+    else:
+        rows = [tuple(int(v) for v in b) for b in boxes]
+        idx = list(range(len(rows))) if frame_indices is None else [int(i) for i in frame_indices]
+        if len(idx) != len(rows) or any(len(r) != 4 for r in rows):
+            raise RuntimeError("crop_resize_u8: one (x1, y1, x2, y2) box and one frame index per crop")
+        n_jobs = len(rows)
+        jobs_host = (_lib.MfCropJob * max(n_jobs, 1))()
+        for k, (f, r) in enumerate(zip(idx, rows)):
+            jobs_host[k].frame_index, jobs_host[k].x1, jobs_host[k].y1, jobs_host[k].x2, jobs_host[k].y2 = (f,) + r
+        flat = np.array([(f,) + r for f, r in zip(idx, rows)], dtype=np.int32).reshape(n_jobs, 5)
+        jobs_dev = torch.from_numpy(flat).to(dev)
+        if mode == "lanczos4" and dh >= 1 and dw >= 1 and all(r[2] > r[0] and r[3] > r[1] for r in rows):
+            memo = {}
+
+            def axis(ssize, dsize):
+                if (ssize, dsize) not in memo:
+                    memo[(ssize, dsize)] = lanczos4_tables(ssize, dsize)
+                return memo[(ssize, dsize)]
+
+            xs = [axis(r[2] - r[0], dw) for r in rows]
+            ys = [axis(r[3] - r[1], dh) for r in rows]
+            tables = [torch.from_numpy(np.ascontiguousarray(np.stack(t))).to(dev) for t in ([a[0] for a in xs], [a[1] for a in xs], [a[0] for a in ys], [a[1] for a in ys])]
+        elif mode == "lanczos4":                       # an argument the entry point refuses below, before any launch: it needs non-null tables to say so
+            tables = [jobs_dev] * 4
+    shape = (n_jobs, dh, dw, 3)
+    if out is None:
+        out = torch.empty(tuple(max(v, 0) for v in shape), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.is_cuda and out.device == dev and out.is_contiguous() and tuple(out.shape) == shape):
+        what = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise RuntimeError(f"crop_resize_u8: out must be a contiguous uint8 tensor {shape} on {dev}, got {what}")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mf_crop_resize_u8(frames.data_ptr(), n, H, W, jobs_dev.data_ptr(), jobs_host, n_jobs, out.data_ptr(), dh, dw, _lib.CROP_MODES[mode],
+                                                *[None if t is None else t.data_ptr() for t in tables], _stream_ptr(dev)), "crop_resize_u8")
     return out
 
 
