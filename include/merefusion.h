@@ -845,6 +845,39 @@ int mf_face_mask_finish(const uint8_t* masks, int mask_h, int mask_w, const int*
                         uint8_t* out, void* stream);
 void mf_net_destroy(mf_net* h);
 
+/* ---- DWPose landmark network (mf_dwpose_ops.hip, mf_rtmcc_head.hip, mf_dwpose.hip): mmdet CSPNeXt + mmpose RTMCCHead + SimCC, and the landmark box of
+ * musetalk/utils/preprocessing.py:96-131.  Two more ops of the mf_net builder, then free functions that read / fill a net's buffers in place. */
+/* depthwise k x k conv (k 3 or 5, stride 1 or 2, pad k / 2) + eval BatchNorm (all four vectors or none; eps = bn_eps) + act (0 none, 1 ReLU, 4 SiLU) on C channels at
+ * in_coff of in_buf -> C channels at out_coff of out_buf.  weight: host fp32 [C][1][k][k]; bias may be null. */
+int mf_net_dwconv(mf_net* h, int C, int k, int stride, int act, const float* weight, const float* bias, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
+                  const float* bn_var, float bn_eps, int in_buf, int in_coff, int out_buf, int out_coff);
+/* mmdet ChannelAttention after its average pool: out = x * hardsigmoid(fc(pooled)); pooled_buf: a 1x1 map (mf_net_global_avgpool); fc_weight host fp32 [C][C], fc_bias [C] */
+int mf_net_chan_attn(mf_net* h, int x_buf, int x_coff, int C, int pooled_buf, const float* fc_weight, const float* fc_bias, int out_buf, int out_coff);
+/* RTMCCHead behind its final conv.  Weights: host fp32 in torch layout ([out][in]); mlp_g / ln_g: the ScaleNorm scalars; expansion factor 2.  forward reads `tokens` maps
+ * of `flat` = H * W values at channel coff of net buffer buf (after mf_net_run) and writes device fp32 logits_x [batch][tokens][bins_x], logits_y [batch][tokens][bins_y].
+ * The intermediate workspace belongs to the handle: forwards of one handle must be ordered on one stream (two streams would race on it); use one handle per stream. */
+typedef struct mf_rtmcc_head mf_rtmcc_head;
+int mf_rtmcc_head_create(int tokens, int flat, int hidden, int s, int bins_x, int bins_y, const float* mlp_g, const float* mlp_w, const float* ln_g, const float* uv_w,
+                         const float* gamma, const float* beta, const float* o_w, const float* res_scale, const float* cls_x_w, const float* cls_y_w, int max_batch,
+                         mf_rtmcc_head** out);
+int mf_rtmcc_head_forward(mf_rtmcc_head* h, mf_net* net, int buf, int coff, int batch, float* logits_x, float* logits_y, void* stream);
+void mf_rtmcc_head_destroy(mf_rtmcc_head* h);
+/* SimCC decode on the device, no host sync: with flip_x / flip_y (the logits of the mirrored images; flip_pairs: HOST int [keypoints], the dataset's flip_indices) the
+ * two passes are averaged first (simcc_x's bin axis reversed, keypoints swapped).  argmax per axis (first maximum), score = the smaller maximum, location -1 where
+ * score <= 0, / 2, then keypoints / (in_w, in_h) * scale + center - scale / 2 in fp32, one rounding per operation.  center, scale: host float [2].
+ * kpts: device fp32 [batch][keypoints][2]; scores: device fp32 [batch][keypoints]. */
+int mf_simcc_decode(const float* logits_x, const float* logits_y, const float* flip_x, const float* flip_y, const int* flip_pairs, int batch, int keypoints, int bins_x,
+                    int bins_y, int in_w, int in_h, const float* center, const float* scale, float* kpts, float* scores, void* stream);
+/* cv2.warpAffine(INTER_LINEAR, constant 0 border) as an integer model + channel reversal + (x - mean3[c]) / std3[c] into batch slot j of the 3-channel
+ * input buffer `buf`, and with flip != 0 the mirrored image into slot n + j.  frames: device uint8 [n][H][W][3]; minv: device float64 [n][6], the input -> source map. */
+int mf_warp_affine_u8(mf_net* net, int buf, const uint8_t* frames, int n, int H, int W, const double* minv, const float* mean3, const float* std3, int reverse_channels,
+                      int flip, void* stream);
+/* preprocessing.py:100-101, 113-131 in integer arithmetic.  kpts: device fp32 [n][keypoints][2] (keypoints >= 91: the face is [23, 91)); boxes / counts: the outputs of
+ * mf_s3fd_detect.  coords: device int32 [n][4] (x1, y1, x2, y2); flags: device int32 [n]: 0 no face (coords 0), 1 landmark box, 2 detector's box (clipped to the frame);
+ * range_sums: device int32 [3]: sum of range_minus, sum of range_plus, frames counted. */
+int mf_muse_landmark_boxes(const float* kpts, int keypoints, const float* boxes, const int* counts, int n, int max_det, int H, int W, int bbox_shift, int* coords, int* flags,
+                           int* range_sums, void* stream);
+
 /* ---- avatar preparation: boxes and crops (mf_crop_resize.hip) ------------------------------------------------------------ */
 /* The steps between the detector and the generators that wav2lip/genavatar.py:80-96,119 and musetalk/mere_musetalk.py:293-296 do with numpy and cv2.  Nothing here
  * synchronises with the host.  (ABI version 4: additions only) */

@@ -157,6 +157,14 @@ SIGNATURES = {
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mf_face_mask_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_net_destroy": (None, [C.c_void_p]),
+    "mf_net_dwconv": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_float] + [C.c_int] * 4),
+    "mf_net_chan_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mf_rtmcc_head_create": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.POINTER(C.c_void_p)]),
+    "mf_rtmcc_head_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mf_rtmcc_head_destroy": (None, [C.c_void_p]),
+    "mf_simcc_decode": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_int)] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 2 + [C.c_void_p] * 3),
+    "mf_warp_affine_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "mf_muse_landmark_boxes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),
     "mf_avatar_lip_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_crop_resize_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(MfCropJob), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

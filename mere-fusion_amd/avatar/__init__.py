@@ -4,4 +4,5 @@ from .s3fd import s3fd                 # noqa: F401
 from .bisenet import BiSeNet           # noqa: F401
 from .face_detection import FaceAlignment, LandmarksType, SFDDetector   # noqa: F401
 from .face_parsing import FaceParsing, finish_masks   # noqa: F401
-from .prepare import prepare_lip_avatar, prepare_muse_avatar   # noqa: F401
+from .dwpose import DWPose              # noqa: F401
+from .prepare import muse_landmark_boxes, prepare_lip_avatar, prepare_muse_avatar   # noqa: F401

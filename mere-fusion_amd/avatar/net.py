@@ -47,17 +47,36 @@ class Net:
         self._keep.append(t)
         return t
 
-    def conv(self, weight, in_buf, out_buf, stride=1, pad=0, act=0, bias=None, bn=None, in_coff=0, out_coff=0, res_buf=-1, res_coff=0, name="conv"):
-        """nn.Conv2d(cin, cout, k, stride, pad) [+ BatchNorm2d (gamma, beta, mean, var)] [+ residual] + act (0 none, 1 ReLU, 2 sigmoid)"""
+    def conv(self, weight, in_buf, out_buf, stride=1, pad=0, act=0, bias=None, bn=None, in_coff=0, out_coff=0, res_buf=-1, res_coff=0, name="conv", res_after_act=False):
+        """nn.Conv2d(cin, cout, k, stride, pad) [+ BatchNorm2d (gamma, beta, mean, var)] [+ residual] + act (0 none, 1 ReLU, 2 sigmoid, 4 SiLU); the residual
+        is added before the activation, or after it with res_after_act (mf_conv2d_desc.residual = 2)"""
         w = self._f32(weight)
         cout, cin, kh, kw = w.shape
         d = _lib.MfConv2dDesc(cin=cin, cout=cout, kh=kh, kw=kw, stride_h=stride, stride_w=stride, pad_h=pad, pad_w=pad, act=act,
-                              residual=1 if res_buf >= 0 else 0)
+                              residual=(2 if res_after_act else 1) if res_buf >= 0 else 0)
         b = self._f32(bias)
         g, be, m, v = (self._f32(t) for t in bn) if bn is not None else (None, None, None, None)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mf_net_conv(self._h, C.byref(d), _p(w), _p(b), _p(g), _p(be), _p(m), _p(v), in_buf, in_coff, out_buf, out_coff,
                                               res_buf, res_coff, name.encode()), f"net_conv({name})")
+
+    def dwconv(self, weight, in_buf, out_buf, stride=1, act=0, bias=None, bn=None, bn_eps=1e-5, in_coff=0, out_coff=0):
+        """nn.Conv2d(C, C, k, stride, k // 2, groups=C) [+ BatchNorm2d] + act (0 none, 1 ReLU, 4 SiLU); k 3 or 5, stride 1 or 2"""
+        w = self._f32(weight)
+        Cn, one, kh, kw = w.shape
+        if one != 1 or kh != kw:
+            raise ValueError(f"dwconv: a depthwise weight is [C, 1, k, k], got {tuple(w.shape)}")
+        b = self._f32(bias)
+        g, be, m, v = (self._f32(t) for t in bn) if bn is not None else (None, None, None, None)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mf_net_dwconv(self._h, Cn, kh, stride, act, _p(w), _p(b), _p(g), _p(be), _p(m), _p(v), C.c_float(bn_eps), in_buf, in_coff, out_buf,
+                                                out_coff), "net_dwconv")
+
+    def chan_attn(self, x_buf, Cn, pooled_buf, fc_weight, fc_bias, out_buf, x_coff=0, out_coff=0):
+        """x * hardsigmoid(fc(pooled)): mmdet's ChannelAttention after its average pool (global_avgpool into pooled_buf)"""
+        w, b = self._f32(torch.as_tensor(fc_weight).reshape(Cn, Cn)), self._f32(fc_bias)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mf_net_chan_attn(self._h, x_buf, x_coff, Cn, pooled_buf, _p(w), _p(b), out_buf, out_coff), "net_chan_attn")
 
     def maxpool(self, in_buf, out_buf, k, stride, pad=0):
         _lib.check(_lib.lib().mf_net_maxpool(self._h, in_buf, out_buf, k, stride, pad), "net_maxpool")

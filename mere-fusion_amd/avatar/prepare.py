@@ -5,7 +5,8 @@
 `prepare_lip_avatar` is wav2lip/genavatar.py:61-122 without its files: detection over slices of the frames, the pads / clamp / temporal smoothing of the boxes
 (mf_avatar_lip_boxes) and the crop + cv2.resize to 96 x 96 (mf_crop_resize_u8, linear) are enqueued back to back; the host waits once, for the counter of frames
 without a face and the coords.  `prepare_muse_avatar` is musetalk/mere_musetalk.py:284-310: crop + INTER_LANCZOS4 resize to 256 x 256, both VAE encoder passes on the
-device crop, and the blend masks of `prepare_materials`.  The DWPose landmark network (mmpose) is not built here: its boxes enter as an argument.  Image and video
+device crop, and the blend masks of `prepare_materials`; with `pose=` (the `DWPose` drop-in, avatar/dwpose.py) the landmark boxes of
+musetalk/utils/preprocessing.py:96-131 are built on the device too (`muse_landmark_boxes`: detector, landmark network, mf_muse_landmark_boxes, one read-back).  Image and video
 files, and the coords.pkl / latents.pt / PNG trees the reference writes, are the caller's.  There is no CPU path."""
 import ctypes as C
 
@@ -91,11 +92,57 @@ def prepare_lip_avatar(frames, fa, pads=(0, 10, 0, 0), nosmooth=False, img_size=
     return faces, [tuple(int(v) for v in row) for row in c]
 
 
-def prepare_muse_avatar(frames, vae, fp, boxes=None, fa=None, generator=None, det_batch=16):
+def landmark_boxes_device(kpts, boxes, counts, H, W, bbox_shift=0):
+    """mf_muse_landmark_boxes on device keypoints [n, K, 2] and the detector's device outputs -> (coords int32 [n, 4] as (x1, y1, x2, y2), flags int32 [n]: 0 no face /
+    1 landmark box / 2 detector's box, range sums int32 [3]), all on the device, nothing synchronised"""
+    if not (torch.is_tensor(kpts) and kpts.is_cuda and kpts.dtype == torch.float32 and kpts.dim() == 3 and kpts.shape[2] == 2):
+        raise RuntimeError("landmark_boxes_device needs fp32 [n, K, 2] keypoints on the HIP device; no CPU path exists here")
+    n, dev = int(kpts.shape[0]), kpts.device
+    if not (torch.is_tensor(boxes) and boxes.device == dev and boxes.dtype == torch.float32 and boxes.dim() == 3 and boxes.shape[0] == n and boxes.shape[2] == 5):
+        raise RuntimeError(f"landmark_boxes_device: boxes must be the detector's fp32 [{n}, max_det, 5] on {dev}")
+    if not (torch.is_tensor(counts) and counts.device == dev and counts.dtype == torch.int32 and tuple(counts.shape) == (n,)):
+        raise RuntimeError(f"landmark_boxes_device: counts must be int32 [{n}] on {dev}")
+    kpts, boxes, counts = kpts.contiguous(), boxes.contiguous(), counts.contiguous()
+    coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    flags = torch.empty(n, dtype=torch.int32, device=dev)
+    sums = torch.empty(3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mf_muse_landmark_boxes(kpts.data_ptr(), int(kpts.shape[1]), boxes.data_ptr(), counts.data_ptr(), n, int(boxes.shape[1]), int(H), int(W),
+                                                     int(bbox_shift), coords.data_ptr(), flags.data_ptr(), sums.data_ptr(),
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "muse_landmark_boxes")
+    return coords, flags, sums
+
+
+def range_text(n_frames, sums, bbox_shift=0):
+    """preprocessing.py:134 (with no face in any frame the reference divides by zero; here the range reads 0~0)"""
+    sm, sp, cnt = (int(v) for v in sums)
+    a, b = (int(sm / cnt), int(sp / cnt)) if cnt else (0, 0)
+    return f"Total frame:「{n_frames}」 Manually adjust range : [ -{a}~{b} ] , the current value: {bbox_shift}"
+
+
+def muse_landmark_boxes(frames, pose, fa, bbox_shift=0, det_batch=16):
+    """get_landmark_and_bbox (preprocessing.py:84-136) for frames already in memory: the detector, the landmark network and the box statements run back to back on the
+    device, one read-back.  Returns (coord_list, range_text): one (x1, y1, x2, y2) tuple of ints per frame, `(0.0, 0.0, 0.0, 0.0)` where no face was detected."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("muse_landmark_boxes needs a HIP device; no CPU path exists here")
+    dev = frames.device if torch.is_tensor(frames) and frames.is_cuda else pose.device
+    fr = _device_frames(frames, dev)
+    n, H, W = (int(v) for v in fr.shape[:3])
+    (b, counts, ncand), max_cand, max_det = _detect(fa, fr, det_batch)
+    kp = torch.cat([pose.keypoints(fr[i:i + pose.max_batch])[0] for i in range(0, n, pose.max_batch)])
+    coords, flags, sums = landmark_boxes_device(kp, b, counts, H, W, bbox_shift)
+    host = torch.cat([counts.to(torch.int32), ncand.to(torch.int32), flags, sums, coords.reshape(-1)]).cpu().numpy()      # the one sync
+    check_counts(torch.from_numpy(host[:n]), torch.from_numpy(host[n:2 * n]), max_cand, max_det)
+    fl, c = host[2 * n:3 * n], host[3 * n + 3:].reshape(n, 4)
+    return [tuple(int(v) for v in row) if f else COORD_PLACEHOLDER for row, f in zip(c, fl)], range_text(n, host[3 * n:3 * n + 3], bbox_shift)
+
+
+def prepare_muse_avatar(frames, vae, fp, boxes=None, fa=None, generator=None, det_batch=16, pose=None, bbox_shift=0):
     """mere_musetalk.py:284-310 for frames already in memory.  frames: n BGR uint8 frames of one size; vae: the `VAE` drop-in (with encoder weights); fp: the
     `FaceParsing` drop-in; boxes: the reference's coord_list -- one (x1, y1, x2, y2) per frame from the caller's landmark step (DWPose,
     musetalk/utils/preprocessing.py:96-131), `(0.0, 0.0, 0.0, 0.0)` where it found no face.  boxes=None takes the DETECTOR's first box of `fa` instead (clipped to
-    the frame), which is what preprocessing.py:126-128 falls back to when the landmark box is unusable: it is NOT the landmark box -- it is not cut at the
+    the frame) when `pose` is None too; with pose (the `DWPose` drop-in) and fa it builds the landmark boxes itself (`muse_landmark_boxes`, bbox_shift as in
+    get_landmark_and_bbox).  The detector's box is what preprocessing.py:126-128 falls back to when the landmark box is unusable: it is NOT the landmark box -- it is not cut at the
     half-face line and is wider -- so an avatar built this way differs from one built from landmarks.
     Frames with the placeholder are skipped, as mere_musetalk.py:291 skips them for the latents; here the frame leaves the avatar altogether, so that latents,
     frames, boxes and masks stay one per cached frame (what `MuseSession` requires).
@@ -107,6 +154,10 @@ def prepare_muse_avatar(frames, vae, fp, boxes=None, fa=None, generator=None, de
     dev = frames.device if torch.is_tensor(frames) and frames.is_cuda else vae.device
     fr = _device_frames(frames, dev)
     n, H, W = (int(v) for v in fr.shape[:3])
+    if boxes is None and pose is not None:
+        if fa is None:
+            raise ValueError("prepare_muse_avatar: the landmark boxes need the detector too (fa), as preprocessing.py:104 does")
+        boxes, _ = muse_landmark_boxes(fr, pose, fa, bbox_shift, det_batch)
     if boxes is None:
         if fa is None:
             raise ValueError("prepare_muse_avatar: give the landmark boxes, or fa to fall back on the detector's boxes")

@@ -12,6 +12,7 @@
 #include "mf_aux.h"
 #include "mf_schedule.h"
 #include "mf_net_planes.h"
+#include "mf_net_handle.h"
 #include <cfloat>
 #include <cmath>
 #include <memory>
@@ -128,26 +129,6 @@ __global__ __launch_bounds__(256) void k_maxout_bg(const float* __restrict__ src
 }
 
 }  // namespace
-
-struct mf_net {
-    int precision = MF_PREC_BF16X3, cap = 1;
-    std::vector<std::unique_ptr<ActBuf>> bufs;
-    std::vector<std::unique_ptr<ConvPlan>> plans;
-    std::vector<float*> dev;
-    Schedule sch;                                                          // the op list and its runner (no side branches here: it never forks)
-    void* scratch = nullptr;                                               // mf_net_scratch: the candidate lists of mf_s3fd_detect
-    size_t scratch_bytes = 0;
-
-    ~mf_net() {
-        sch.graph.drop_all();
-        for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) mf_actbuf_free(b.get());
-        for (float* d : dev) (void)hipFree(d);
-    }
-    ActBuf* B(int id) { return id >= 0 && id < (int)bufs.size() ? bufs[id].get() : nullptr; }
-};
-
-#define NET_BUF(var, id) ActBuf* var = h->B(id); MF_REQUIRE(var, "net: no buffer %d", id)
 
 extern "C" int mf_net_create(int max_batch, int precision, mf_net** out) {
     MF_REQUIRE(out && max_batch >= 1 && max_batch <= 256, "net_create: bad argument");

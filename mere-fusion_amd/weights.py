@@ -550,3 +550,77 @@ def make_bisenet_state_dict(seed=0, n_classes=19, shapes_only=False):
         cbr(p + ".conv", ci, mid, 3)
         conv(p + ".conv_out.weight", n_classes, mid, 1, 2.0)
     return sd
+
+
+# ---- DWPose: RTMPose-l whole-body (mmdet CSPNeXt-P5 + mmpose RTMCCHead), keys of an mmpose checkpoint -------------------------------------------------
+_CSPNEXT_P5 = ((64, 128, 3, True, False), (128, 256, 6, True, False), (256, 512, 6, True, False), (512, 1024, 3, False, True))
+
+
+def dwpose_manifest(deepen=1.0, widen=1.0, input_size=(288, 384), keypoints=133, hidden=256, s=128):
+    """[(key, shape)] in module order (num_batches_tracked included: strict loading of dw-ll_ucoco_384.pth needs the same key set)"""
+    out = []
+
+    def cm(p, ci, co, k, groups=1):
+        out.append((p + ".conv.weight", (co, ci // groups, k, k)))
+        out.extend([(p + ".bn.weight", (co,)), (p + ".bn.bias", (co,)), (p + ".bn.running_mean", (co,)), (p + ".bn.running_var", (co,)),
+                    (p + ".bn.num_batches_tracked", ())])
+
+    c = int(64 * widen)
+    cm("backbone.stem.0", 3, c // 2, 3); cm("backbone.stem.1", c // 2, c // 2, 3); cm("backbone.stem.2", c // 2, c, 3)
+    for i, (ci, co, nb, _, spp) in enumerate(_CSPNEXT_P5, 1):
+        ci, co, nb = int(ci * widen), int(co * widen), max(round(nb * deepen), 1)
+        p = f"backbone.stage{i}"
+        cm(p + ".0", ci, co, 3)
+        j = 1
+        if spp:
+            cm(p + ".1.conv1", co, co // 2, 1); cm(p + ".1.conv2", co // 2 * 4, co, 1)
+            j = 2
+        q, mid = f"{p}.{j}", int(co * 0.5)
+        cm(q + ".main_conv", co, mid, 1); cm(q + ".short_conv", co, mid, 1); cm(q + ".final_conv", 2 * mid, co, 1)
+        for b in range(nb):
+            cm(f"{q}.blocks.{b}.conv1", mid, mid, 3)
+            cm(f"{q}.blocks.{b}.conv2.depthwise_conv", mid, mid, 5, groups=mid)
+            cm(f"{q}.blocks.{b}.conv2.pointwise_conv", mid, mid, 1)
+        out.extend([(q + ".attention.fc.weight", (2 * mid, 2 * mid, 1, 1)), (q + ".attention.fc.bias", (2 * mid,))])
+    cf, flat, e = int(1024 * widen), (input_size[0] // 32) * (input_size[1] // 32), 2 * hidden
+    out.extend([("head.final_layer.weight", (keypoints, cf, 7, 7)), ("head.final_layer.bias", (keypoints,)), ("head.mlp.0.g", (1,)),
+                ("head.mlp.1.weight", (hidden, flat)), ("head.gau.gamma", (2, s)), ("head.gau.beta", (2, s)), ("head.gau.o.weight", (hidden, e)),
+                ("head.gau.uv.weight", (2 * e + s, hidden)), ("head.gau.ln.g", (1,)), ("head.gau.res_scale.scale", (hidden,)),
+                ("head.cls_x.weight", (int(input_size[0] * 2), hidden)), ("head.cls_y.weight", (int(input_size[1] * 2), hidden))])
+    return out
+
+
+def make_dwpose_state_dict(seed=0, shapes_only=False, **cfg):
+    """Seeded random weights (no checkpoint): BatchNorm statistics and affine are randomised, since a default-initialised BatchNorm collapses the output
+    (SURVEY 8c found that for Wav2Lip)."""
+    rng = np.random.default_rng(16000 + seed)
+    sd = {}
+    for key, shape in dwpose_manifest(**cfg):
+        if shapes_only:
+            sd[key] = tuple(shape)
+            continue
+        leaf = key.rsplit(".", 1)[1]
+        if key.endswith("num_batches_tracked"):
+            sd[key] = torch.tensor(0, dtype=torch.int64)
+            continue
+        if ".bn." in key:
+            v = {"weight": lambda: rng.uniform(0.8, 1.2, shape), "bias": lambda: rng.standard_normal(shape) * 0.1,
+                 "running_mean": lambda: rng.standard_normal(shape) * 0.1, "running_var": lambda: rng.uniform(0.5, 1.5, shape)}[leaf]()
+        elif key.endswith(".conv.weight") or key == "head.final_layer.weight":
+            v = rng.standard_normal(shape) * 1.6 * np.sqrt(1.0 / (shape[1] * shape[2] * shape[3]))     # SiLU keeps about 0.6 of the scale
+        elif ".attention.fc." in key:
+            v = rng.standard_normal(shape) * (4.0 * np.sqrt(1.0 / shape[0]) if leaf == "weight" else 1.5)   # pre-activations across all of hard-sigmoid's branches
+        elif leaf == "g":
+            v = rng.uniform(0.8, 1.2, shape)
+        elif key.startswith("head.gau.gamma") or key.startswith("head.gau.beta"):
+            v = rng.uniform(0.0, 1.0, shape)
+        elif key.endswith("res_scale.scale"):
+            v = rng.uniform(0.8, 1.2, shape)
+        elif key.endswith("final_layer.bias"):
+            v = rng.standard_normal(shape) * 0.1
+        elif key == "head.gau.o.weight":
+            v = rng.standard_normal(shape) * 0.015 * np.sqrt(1.0 / shape[1])                           # relu(qk)^2 summed over 133 tokens is in the hundreds
+        else:                                                                                             # the head's other Linears
+            v = rng.standard_normal(shape) * 1.5 * np.sqrt(1.0 / shape[1])
+        sd[key] = torch.from_numpy(np.asarray(v, np.float32))
+    return sd
