@@ -807,6 +807,18 @@ int mf_s3fd_maxout_bg(const float* cls4, float* cls2, int batch, int hw, void* s
  * `imgs - np.array([104, 117, 123])` of sfd/detect.py:59-60 and the `images[..., ::-1]` of face_detection/api.py:65 in one pass; bit-equal to mf_net_set_input of the
  * same values as fp32 (they are exact integers). */
 int mf_net_set_input_u8(mf_net* h, int buf, const uint8_t* u8_nhwc, const float* mean3, int reverse_channels, int batch, void* stream);
+/* Served uint8 frames -> an input buffer of 3 * T channels in one launch (csrc/mf_sync.hip): frames is device uint8 [n_frames][H][W][3], starts a HOST array of
+ * n_windows first frames; batch slot w, channel 3 * t + c, row y, column x = (float)frames[starts[w] + t][row0 + y][x][c] / 255.f.  The buffer must be rows x W with
+ * 3 * T channels.  SyncNet's face windows are T = 5, row0 = H / 2, rows = H / 2 (5 BGR frames on the channel axis, / 255., lower half: upstream Wav2Lip's
+ * color_syncnet_train.py).  Bit-equal to mf_net_set_input of the same values as fp32.  Windows may overlap; the frames are read in place.  MF_ERR_INVALID, before any
+ * launch, when starts[w] < 0 or starts[w] + T > n_frames, row0 + rows > H, n_windows exceeds the net's capacity, or the buffer's channels or size do not match. */
+int mf_net_set_input_u8_windows(mf_net* h, int buf, const uint8_t* frames, int n_frames, int H, int W, const int* starts, int n_windows, int T, int row0, int rows,
+                                void* stream);
+/* Banded audio / video similarity of two embedding sequences and its reduction (csrc/mf_sync.hip).  face_emb, audio_emb: device fp32 [W][dim], raw or normalised;
+ * sim: device fp32 [W][2 S + 1], sim[w][s] = <f_w, a_j> / (max(|f_w|, 1e-12) * max(|a_j|, 1e-12)) with j = w + s - S (a positive shift: the audio window is later than
+ * the video window; an all-zero row gives 0), 0 where j is outside [0, W); counts: device int [2 S + 1], the valid windows per shift; curve: device fp32 [2 S + 1], the
+ * mean of the valid entries (0 where counts is 0), summed in a fixed order: two runs give the same bits.  dim % 4 == 0, 4 <= dim <= 1024, 0 <= S <= 64, W >= 1. */
+int mf_sync_score(const float* face_emb, const float* audio_emb, int W, int dim, int max_shift, float* sim, float* curve, int* counts, void* stream);
 /* S3FD's post-process on the device (sfd/detect.py:58-94 batch_detect, bbox.py:111-129 batch_decode, bbox.py:44-64 nms, sfd_detector.py:41-47): after mf_net_run,
  * reads the six 8-channel head buffers (conf in channels 0..3, loc in 4..7; level 1's max-out background fused) in place.  Per image: candidates with softmax face
  * probability > cand_thresh are decoded and appended (at most max_candidates <= 4096 stored; n_candidates[b] counts them all, so n_candidates[b] > max_candidates

@@ -11,6 +11,11 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _pair(v):
+    """torch's int-or-(h, w) convention"""
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
 class Net:
     def __init__(self, max_batch=1, precision="bf16x3", device="cuda"):
         if not torch.cuda.is_available():
@@ -48,11 +53,12 @@ class Net:
         return t
 
     def conv(self, weight, in_buf, out_buf, stride=1, pad=0, act=0, bias=None, bn=None, in_coff=0, out_coff=0, res_buf=-1, res_coff=0, name="conv", res_after_act=False):
-        """nn.Conv2d(cin, cout, k, stride, pad) [+ BatchNorm2d (gamma, beta, mean, var)] [+ residual] + act (0 none, 1 ReLU, 2 sigmoid, 4 SiLU); the residual
-        is added before the activation, or after it with res_after_act (mf_conv2d_desc.residual = 2)"""
+        """nn.Conv2d(cin, cout, k, stride, pad) [+ BatchNorm2d (gamma, beta, mean, var)] [+ residual] + act (0 none, 1 ReLU, 2 sigmoid, 4 SiLU); stride and pad are
+        one int or an (h, w) pair as in torch; the residual is added before the activation, or after it with res_after_act (mf_conv2d_desc.residual = 2)"""
         w = self._f32(weight)
         cout, cin, kh, kw = w.shape
-        d = _lib.MfConv2dDesc(cin=cin, cout=cout, kh=kh, kw=kw, stride_h=stride, stride_w=stride, pad_h=pad, pad_w=pad, act=act,
+        (sh, sw), (ph, pw) = _pair(stride), _pair(pad)
+        d = _lib.MfConv2dDesc(cin=cin, cout=cout, kh=kh, kw=kw, stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, act=act,
                               residual=(2 if res_after_act else 1) if res_buf >= 0 else 0)
         b = self._f32(bias)
         g, be, m, v = (self._f32(t) for t in bn) if bn is not None else (None, None, None, None)
@@ -112,6 +118,17 @@ class Net:
             _lib.check(_lib.lib().mf_net_set_input_u8(self._h, buf, _p(x), (C.c_float * 3)(*[float(m) for m in mean]), int(bool(reverse_channels)), x.shape[0],
                                                       self._stream()), "net_set_input_u8")
         return x.shape[0]
+
+    def set_input_u8_windows(self, buf, frames, starts, T, row0, rows):
+        """uint8 device frames [n, H, W, 3] -> a 3 * T-channel input buffer, one launch: batch slot w = frames[starts[w] : starts[w] + T] concatenated on the
+        channel axis, rows [row0, row0 + rows), / 255 (mf_net_set_input_u8_windows).  starts is a host list; the frames are read in place."""
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError(f"set_input_u8_windows: contiguous uint8 device frames [n, H, W, 3] expected, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+        starts = [int(v) for v in starts]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mf_net_set_input_u8_windows(self._h, buf, _p(frames), frames.shape[0], frames.shape[1], frames.shape[2], (C.c_int * max(len(starts), 1))(*starts),
+                                                              len(starts), int(T), int(row0), int(rows), self._stream()), "net_set_input_u8_windows")
+        return len(starts)
 
     def run(self, batch):
         with torch.cuda.device(self.device):

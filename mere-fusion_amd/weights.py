@@ -118,6 +118,50 @@ def make_lip_inputs(batch, seed=0):
     return torch.from_numpy(mel), torch.from_numpy(np.ascontiguousarray(face)), u8
 
 
+# ---- SyncNet_color, the lip-sync expert (wav2lip/models/syncnet.py:7-53) ------------------------------
+# (cin, cout, k, stride, pad, residual) in constructor order; the blank lines of the reference's two Sequentials are the stage boundaries
+SYNCNET_FACE = [(15, 32, 7, 1, 3, 0),
+                (32, 64, 5, (1, 2), 1, 0), (64, 64, 3, 1, 1, 1), (64, 64, 3, 1, 1, 1),
+                (64, 128, 3, 2, 1, 0), (128, 128, 3, 1, 1, 1), (128, 128, 3, 1, 1, 1), (128, 128, 3, 1, 1, 1),
+                (128, 256, 3, 2, 1, 0), (256, 256, 3, 1, 1, 1), (256, 256, 3, 1, 1, 1),
+                (256, 512, 3, 2, 1, 0), (512, 512, 3, 1, 1, 1), (512, 512, 3, 1, 1, 1),
+                (512, 512, 3, 2, 1, 0), (512, 512, 3, 1, 0, 0), (512, 512, 1, 1, 0, 0)]
+SYNCNET_FACE_STAGE_ENDS = (0, 3, 7, 10, 13, 16)
+SYNCNET_AUDIO = [(1, 32, 3, 1, 1, 0), (32, 32, 3, 1, 1, 1), (32, 32, 3, 1, 1, 1),
+                 (32, 64, 3, (3, 1), 1, 0), (64, 64, 3, 1, 1, 1), (64, 64, 3, 1, 1, 1),
+                 (64, 128, 3, 3, 1, 0), (128, 128, 3, 1, 1, 1), (128, 128, 3, 1, 1, 1),
+                 (128, 256, 3, (3, 2), 1, 0), (256, 256, 3, 1, 1, 1), (256, 256, 3, 1, 1, 1),
+                 (256, 512, 3, 1, 0, 0), (512, 512, 1, 1, 0, 0)]
+
+
+def syncnet_layer_table():
+    """All 31 layers as (prefix, cin, cout, k, stride, pad, residual), in state-dict order of the reference constructor."""
+    return ([(f"face_encoder.{i}",) + s for i, s in enumerate(SYNCNET_FACE)] + [(f"audio_encoder.{i}",) + s for i, s in enumerate(SYNCNET_AUDIO)])
+
+
+def syncnet_state_dict(seed=0, dtype=torch.float32):
+    """217 tensors, 16,435,072 parameters and 14,080 BatchNorm statistics: per layer conv weight and bias, BatchNorm weight, bias, running_mean, running_var, num_batches_tracked.
+    The BatchNorm affine is wider than the generator's (gamma U(0.4, 1.6), beta N(0, 0.3)): both encoders end in a 1 x 1 map, and with a narrow affine the
+    embeddings of different inputs lie ~2e-3 apart (the stack averages the input away), which pins nothing -- tests/golden/make_syncnet_golden.py asserts
+    the separation the GPU gates need."""
+    rng = np.random.default_rng(7000 + seed)
+    sd = {}
+
+    def f(a):
+        return torch.from_numpy(np.asarray(a, dtype=np.float32)).to(dtype)
+
+    for prefix, ci, co, k, _stride, _pad, res in syncnet_layer_table():
+        g = G_RES if res else G_PLAIN
+        sd[f"{prefix}.conv_block.0.weight"] = f(rng.standard_normal((co, ci, k, k)) * (np.sqrt(2.0 / (ci * k * k)) * g))
+        sd[f"{prefix}.conv_block.0.bias"] = f(rng.standard_normal(co) * 0.05)
+        sd[f"{prefix}.conv_block.1.weight"] = f(rng.uniform(0.4, 1.6, co))
+        sd[f"{prefix}.conv_block.1.bias"] = f(rng.standard_normal(co) * 0.3)
+        sd[f"{prefix}.conv_block.1.running_mean"] = f(rng.standard_normal(co) * 0.1)
+        sd[f"{prefix}.conv_block.1.running_var"] = f(rng.uniform(0.6, 1.4, co))
+        sd[f"{prefix}.conv_block.1.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    return sd
+
+
 # ---- Whisper-tiny audio encoder (musetalk/whisper/whisper/model.py:131-171) --------------------------
 # dims of the public "tiny" checkpoint; the reference reads them from the checkpoint (whisper/__init__.py:112)
 WHISPER_TINY = dict(n_mels=80, n_audio_ctx=1500, n_audio_state=384, n_audio_head=6, n_audio_layer=4)
