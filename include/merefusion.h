@@ -512,6 +512,45 @@ int mf_nerf_frame_background(const uint8_t* torso_rgba, const float* bg_image, f
 int mf_nerf_frame_out(const float* render, int h, int w, int H, int W, const uint8_t* body_bgr, int FH, int FW, int x0, int y0, int linear_to_srgb,
                       uint8_t* frame_rgb, void* stream);
 
+/* ---- the three stages around the batched head render, for every frame of a step in one launch each (mf_nerf_frame_batch.hip) ----
+ * mf_nerf_frame_background, mf_nerf_torso_forward and mf_nerf_frame_out with a frame index in the grid (blockIdx.y): frame i of a call is the same
+ * bits as the single-frame entry point gives for the same inputs -- the per-pixel code is shared, and a frame's pixels keep tiles of their own (a frame
+ * whose pixel count is no multiple of the tile has a partial last tile; pixels of two frames never share one).
+ * The handle owns a ring of 16 descriptor tables in pinned host memory with their device copies, allocated at the first accepted call.  A call
+ * fills the next table, copies it to the device asynchronously on the caller's stream, launches, and records an event; it waits for the host only
+ * when all 16 entries belong to calls still in flight.  What the descriptors point at must stay valid until the call's launch has run.
+ * All frames of a call share the sizes; what a descriptor holds is per frame.  max_frames 1..64; max_pixels is per frame (the torso kernel keeps
+ * every pixel's activations on chip, so the handle holds no per-pixel scratch: max_pixels bounds n_pixels and nothing else). */
+typedef struct mf_nerf_frame_batch mf_nerf_frame_batch;
+typedef struct mf_nerf_bg_desc {
+    const uint8_t* torso_rgba;         /* device, uint8 [H, W, 4], 4-byte aligned */
+    const float* bg_image;             /* device, fp32 [H, W, 3], or NULL: bg_const */
+    float bg_const;
+    int half_mode;
+    float* bg_color;                   /* output, device fp32 [H * W, 3] */
+} mf_nerf_bg_desc;
+typedef struct mf_nerf_torso_desc {
+    float frame_consts[50];            /* the [42 + individual_dim] constants of mf_nerf_torso_forward, by value */
+    const float* bg_coords;            /* device, [n_pixels, 2] */
+    const float* bg_color;             /* as mf_nerf_torso_forward */
+    int bg_per_ray;
+    float bg_const, density_thresh;
+    float *bg_out, *torso_alpha, *deform;   /* outputs, device: [n_pixels, 3], [n_pixels] or NULL, [n_pixels, 2] or NULL */
+} mf_nerf_torso_desc;
+typedef struct mf_nerf_out_desc {
+    const float* render;               /* device fp32 [h, w, 3], or NULL: a custom-video frame (body_bgr alone, channels reversed) */
+    const uint8_t* body_bgr;           /* device uint8 [FH, FW, 3], or NULL (then FH x FW = H x W and the offset is 0) */
+    int x0, y0;
+} mf_nerf_out_desc;
+int mf_nerf_frame_batch_create(int max_frames, int max_pixels, mf_nerf_frame_batch** out);
+void mf_nerf_frame_batch_destroy(mf_nerf_frame_batch* h);
+/* mf_nerf_frame_background for n_frames frames of H x W pixels */
+int mf_nerf_frame_batch_background(mf_nerf_frame_batch* h, const mf_nerf_bg_desc* descs, int n_frames, int H, int W, void* stream);
+/* (mf_nerf_torso_forward_batch stands with the torso handle below) */
+/* mf_nerf_frame_out for n_frames frames into one block frames_rgb uint8 [n_frames, FH, FW, 3] (what mf_frames_to_i420 takes) */
+int mf_nerf_frame_batch_out(mf_nerf_frame_batch* h, const mf_nerf_out_desc* descs, int n_frames, int rh, int rw, int H, int W, int FH, int FW,
+                            int linear_to_srgb, uint8_t* frames_rgb, void* stream);
+
 /* ---- the audio features of many ER-NeRF sessions (mf_nerf_featpool.hip; nerf_serving.NerfFeaturePool) ---- */
 /* What `NerfASR` keeps per session in torch tensors, for N sessions in two caller-owned device buffers: rings fp32 [N][R][dim] (`feat_queue`,
  * nerfasr.py:48-50; R = feat_buffer_size * m = 32) and hist fp32 [N][8][dim][16] (`att_feats`, nerfasr.py:55, as a circular buffer).  Both entries are
@@ -666,6 +705,11 @@ int mf_nerf_torso_set_grid(mf_nerf_torso* h, const float* density_grid);
 int mf_nerf_torso_grid_update(mf_nerf_torso* h, const float* frame_consts_host, const float* noise, float decay, float* density_grid,
                               float* raw_grid, float* xys_out, float* mean, void* stream);
 void mf_nerf_torso_destroy(mf_nerf_torso* h);
+/* mf_nerf_torso_forward for n_frames frames of n_pixels pixels in one launch, through the descriptor table of a mf_nerf_frame_batch (above): frame i
+ * is the same bits as mf_nerf_torso_forward gives for descs[i] -- the first-layer biases are formed on the host the same way and travel in the table,
+ * and a frame's pixels fill 256-pixel tiles of their own.  Every frame samples the grid bound by mf_nerf_torso_set_grid.  Needs the fused torso kernel
+ * (MF_TORSO=gemm is refused). */
+int mf_nerf_torso_forward_batch(mf_nerf_torso* torso, mf_nerf_frame_batch* h, const mf_nerf_torso_desc* descs, int n_frames, int n_pixels, void* stream);
 
 /* ---- ER-NeRF audio features ------------------------------------------------------------------- */
 typedef struct mf_audio_encoder mf_audio_encoder;

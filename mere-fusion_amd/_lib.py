@@ -50,6 +50,22 @@ class MfNerfFrameDesc(C.Structure):
                 ("weights_sum", C.c_void_p), ("frame_u8", C.c_void_p)]
 
 
+class MfNerfBgDesc(C.Structure):
+    """mf_nerf_bg_desc: one frame of mf_nerf_frame_batch_background"""
+    _fields_ = [("torso_rgba", C.c_void_p), ("bg_image", C.c_void_p), ("bg_const", C.c_float), ("half_mode", C.c_int), ("bg_color", C.c_void_p)]
+
+
+class MfNerfTorsoDesc(C.Structure):
+    """mf_nerf_torso_desc: one frame of mf_nerf_torso_forward_batch"""
+    _fields_ = [("frame_consts", C.c_float * 50), ("bg_coords", C.c_void_p), ("bg_color", C.c_void_p), ("bg_per_ray", C.c_int), ("bg_const", C.c_float),
+                ("density_thresh", C.c_float), ("bg_out", C.c_void_p), ("torso_alpha", C.c_void_p), ("deform", C.c_void_p)]
+
+
+class MfNerfOutDesc(C.Structure):
+    """mf_nerf_out_desc: one frame of mf_nerf_frame_batch_out"""
+    _fields_ = [("render", C.c_void_p), ("body_bgr", C.c_void_p), ("x0", C.c_int), ("y0", C.c_int)]
+
+
 class MfVaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("n_blocks", C.c_int),
                 ("block_out_channels", C.c_int * 4), ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int),
@@ -225,6 +241,11 @@ SIGNATURES = {
     "mf_nerf_resize_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mf_nerf_frame_background": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mf_nerf_frame_out": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "mf_nerf_frame_batch_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "mf_nerf_frame_batch_destroy": (None, [C.c_void_p]),
+    "mf_nerf_frame_batch_background": (C.c_int, [C.c_void_p, C.POINTER(MfNerfBgDesc), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mf_nerf_frame_batch_out": (C.c_int, [C.c_void_p, C.POINTER(MfNerfOutDesc)] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    "mf_nerf_torso_forward_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MfNerfTorsoDesc), C.c_int, C.c_int, C.c_void_p]),
     "mf_nerf_feat_scatter": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "mf_nerf_feat_windows": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_int)] * 4 + [C.c_int, C.c_void_p, C.c_void_p]),
     "mf_nerf_head_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

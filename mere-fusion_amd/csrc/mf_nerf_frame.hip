@@ -12,6 +12,7 @@
 // pragma every +, -, *, / below rounds once, as written; divisions are the correctly rounded default of hipcc.
 #include "mf_common.h"
 #include "mf_nerf_frame.h"
+#include "mf_nerf_frame_batch.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -28,11 +29,9 @@ __device__ __forceinline__ float as_half(float v) { return (float)(_Float16)v; }
 // half, and the result widened (the render casts bg_color to fp32).
 struct __attribute__((packed, aligned(4))) Rgb32 { float v[3]; };      // 12 bytes, moved as one dwordx3
 
+// one pixel of the frame; the single-frame kernel and the frame-indexed one are this function and nothing else
 template <bool HALF>
-__global__ __launch_bounds__(NT) void k_nerf_frame_background(const uchar4* __restrict__ torso, const Rgb32* __restrict__ bg, float bg_const, int n,
-                                                              Rgb32* __restrict__ out) {
-    const int i = threadIdx.x + blockIdx.x * NT;
-    if (i >= n) return;
+__device__ __forceinline__ void nerf_background_pixel(const uchar4* __restrict__ torso, const Rgb32* __restrict__ bg, float bg_const, int i, Rgb32* __restrict__ out) {
     const uchar4 px = torso[i];
     const Rgb32 b3 = bg ? bg[i] : Rgb32{{bg_const, bg_const, bg_const}};
     const float c[3] = {(float)px.x / 255.f, (float)px.y / 255.f, (float)px.z / 255.f};
@@ -51,6 +50,23 @@ __global__ __launch_bounds__(NT) void k_nerf_frame_background(const uchar4* __re
     out[i] = o;
 }
 
+template <bool HALF>
+__global__ __launch_bounds__(NT) void k_nerf_frame_background(const uchar4* __restrict__ torso, const Rgb32* __restrict__ bg, float bg_const, int n,
+                                                              Rgb32* __restrict__ out) {
+    const int i = threadIdx.x + blockIdx.x * NT;
+    if (i >= n) return;
+    nerf_background_pixel<HALF>(torso, bg, bg_const, i, out);
+}
+
+// the frame in blockIdx.y: every frame has its own ceil(n / NT) workgroups, the last one partial
+__global__ __launch_bounds__(NT) void k_nerf_frame_background_batch(const NerfBgFrame* __restrict__ frames, int n) {
+    const int i = threadIdx.x + blockIdx.x * NT;
+    if (i >= n) return;
+    const NerfBgFrame f = frames[blockIdx.y];
+    if (f.half) nerf_background_pixel<true>((const uchar4*)f.torso, (const Rgb32*)f.bg, f.bg_const, i, (Rgb32*)f.out);
+    else nerf_background_pixel<false>((const uchar4*)f.torso, (const Rgb32*)f.bg, f.bg_const, i, (Rgb32*)f.out);
+}
+
 // utils.py:78-81.  The power goes through double and is rounded once: ocml's fp32 powf carries packed-fp32 forms the library's ISA scan refuses (mf_common.h
 // mf_opaque).  Out of line: the twelve calls per output pixel (four taps x three channels, converted in front of the blend as utils.py:1208-1212 orders it) share one
 // body.  That is twelve double-precision pows per pixel whenever color_space == 'linear' (DESIGN section 6 states the cost).  The exponent is the fp32 value torch's
@@ -61,10 +77,8 @@ __device__ __noinline__ float linear_to_srgb(float x) {
 
 // One lane per pixel of the [FH, FW] output.  Inside the [H, W] rectangle at (x0, y0): the render resized to the GUI size and converted, through the
 // device functions k_nerf_resize uses (mf_nerf_frame.h).  Outside it, and everywhere when there is no render: the body pixel, BGR -> RGB.
-__global__ __launch_bounds__(NT) void k_nerf_frame_out(const float* __restrict__ render, int h, int w, int H, int W, const uint8_t* __restrict__ body, int FH,
-                                                       int FW, int x0, int y0, int srgb, uint8_t* __restrict__ out) {
-    const int i = threadIdx.x + blockIdx.x * NT;
-    if (i >= FH * FW) return;
+__device__ __forceinline__ void nerf_frame_out_pixel(const float* __restrict__ render, int h, int w, int H, int W, const uint8_t* __restrict__ body, int FW, int x0,
+                                                     int y0, int srgb, int i, uint8_t* __restrict__ out) {
     const int fy = i / FW, fx = i - fy * FW;
     const int oy = fy - y0, ox = fx - x0;
     uint8_t* o = out + (size_t)i * 3;
@@ -84,9 +98,38 @@ __global__ __launch_bounds__(NT) void k_nerf_frame_out(const float* __restrict__
     }
 }
 
+__global__ __launch_bounds__(NT) void k_nerf_frame_out(const float* __restrict__ render, int h, int w, int H, int W, const uint8_t* __restrict__ body, int FH,
+                                                       int FW, int x0, int y0, int srgb, uint8_t* __restrict__ out) {
+    const int i = threadIdx.x + blockIdx.x * NT;
+    if (i >= FH * FW) return;
+    nerf_frame_out_pixel(render, h, w, H, W, body, FW, x0, y0, srgb, i, out);
+}
+
+// the frame in blockIdx.y; frame f writes out[f][FH][FW][3]
+__global__ __launch_bounds__(NT) void k_nerf_frame_out_batch(const NerfOutFrame* __restrict__ frames, int h, int w, int H, int W, int FH, int FW, int srgb,
+                                                             uint8_t* __restrict__ out) {
+    const int i = threadIdx.x + blockIdx.x * NT;
+    if (i >= FH * FW) return;
+    const NerfOutFrame f = frames[blockIdx.y];
+    nerf_frame_out_pixel(f.render, h, w, H, W, f.body, FW, f.x0, f.y0, srgb, i, out + (size_t)blockIdx.y * FH * FW * 3);
+}
+
 inline unsigned blocks(int64_t n) { return (unsigned)((n + NT - 1) / NT); }
 
 }  // namespace
+
+// the callers (mf_nerf_frame_batch.hip) have checked the sizes and every frame's pointers
+int mf_nerf_frame_background_batch_launch(const NerfBgFrame* tab_dev, int n_frames, int n, hipStream_t s) {
+    hipLaunchKernelGGL(k_nerf_frame_background_batch, dim3(blocks(n), (unsigned)n_frames), dim3(NT), 0, s, tab_dev, n);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+int mf_nerf_frame_out_batch_launch(const NerfOutFrame* tab_dev, int n_frames, int h, int w, int H, int W, int FH, int FW, int srgb, uint8_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_nerf_frame_out_batch, dim3(blocks((int64_t)FH * FW), (unsigned)n_frames), dim3(NT), 0, s, tab_dev, h, w, H, W, FH, FW, srgb, out);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
 
 extern "C" int mf_nerf_frame_background(const uint8_t* torso_rgba, const float* bg_image, float bg_const, int H, int W, int half_mode, float* bg_color,
                                         void* stream) {

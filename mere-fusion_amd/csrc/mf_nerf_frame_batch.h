@@ -1,0 +1,41 @@
+// The frame-indexed launches around the batched ER-NeRF head render (mf_nerf_frame_batch.hip): one table entry per frame as the kernels read it, the launchers
+// of the three kernels (each stands beside its single-frame kernel, whose per-pixel code it shares) and what mf_nerf_torso_forward_batch (mf_nerf_net.hip, where
+// the torso handle is defined) needs of the batch handle.
+#pragma once
+#include "mf_nerf_host.h"
+
+struct NerfBgFrame {                     // k_nerf_frame_background_batch (mf_nerf_frame.hip)
+    const uint8_t* torso;
+    const float* bg;
+    float* out;
+    float bg_const;
+    int half;
+};
+struct NerfOutFrame {                    // k_nerf_frame_out_batch (mf_nerf_frame.hip)
+    const float* render;
+    const uint8_t* body;
+    int x0, y0;
+};
+struct NerfTorsoFrame {                  // k_torso_fused<T_BATCH> (mf_nerf_torso.hip)
+    float bias_d[32], bias_t[32];        // mf_nerf_torso::frame_bias of the frame's constants
+    const float *bg_coords, *bg;
+    float *out, *alpha_out, *deform;
+    float thresh, bg_const;
+    int bg_per_ray, pad;
+};
+constexpr size_t NERF_FRAME_BATCH_ENTRY = sizeof(NerfTorsoFrame);       // the largest of the three: a ring entry holds max_frames of them
+static_assert(sizeof(NerfBgFrame) <= NERF_FRAME_BATCH_ENTRY && sizeof(NerfOutFrame) <= NERF_FRAME_BATCH_ENTRY, "ring entries are sized by the torso table");
+
+// n: pixels per frame
+int mf_nerf_frame_background_batch_launch(const NerfBgFrame* tab_dev, int n_frames, int n, hipStream_t s);
+int mf_nerf_frame_out_batch_launch(const NerfOutFrame* tab_dev, int n_frames, int h, int w, int H, int W, int FH, int FW, int srgb, uint8_t* out, hipStream_t s);
+int mf_nerf_torso_batch_launch(const NerfTorsoConsts& t, const NerfTorsoFrame* tab_dev, int n_frames, const float* density, int N, hipStream_t s);
+
+// ---- the handle's ring, for the entry points that fill a table ------------------------------------------------------------------------------------
+int mf_nerf_frame_batch_limits(const mf_nerf_frame_batch* h, int* max_frames, int* max_pixels);
+// the next ring entry (allocating the ring at the first call; waits only when every entry belongs to a call still in flight): its pinned table to fill
+int mf_nerf_frame_batch_acquire(mf_nerf_frame_batch* h, int* slot, void** tab_host);
+// the table's first `bytes` to the entry's device copy on `s`; *tab_dev is what the kernel reads
+int mf_nerf_frame_batch_upload(mf_nerf_frame_batch* h, int slot, size_t bytes, hipStream_t s, const void** tab_dev);
+// behind the call's last launch (also after a failed one: the copy is on the stream)
+int mf_nerf_frame_batch_release(mf_nerf_frame_batch* h, int slot, hipStream_t s);

@@ -16,6 +16,7 @@
 // sigma_net's last layer writes its 65 outputs straight into CI[0..64]; colour_net's weight columns are permuted to that layout
 // (and zero on h0), so geo_feat is never copied.
 #include "mf_nerf_host.h"
+#include "mf_nerf_frame_batch.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -556,6 +557,38 @@ extern "C" int mf_nerf_torso_forward(mf_nerf_torso* h, const float* bg_coords, c
                        bg_per_ray, bg_const, N, bg_out, torso_alpha);
     MF_HIP(hipGetLastError());
     return MF_OK;
+}
+
+// mf_nerf_torso_forward for the frames of a table in one launch: the biases are formed here exactly as above and travel in the batch handle's table
+extern "C" int mf_nerf_torso_forward_batch(mf_nerf_torso* torso, mf_nerf_frame_batch* h, const mf_nerf_torso_desc* descs, int n_frames, int n_pixels, void* stream) {
+    MF_REQUIRE(h && descs, "nerf_torso_forward_batch: null handle or descriptor table");
+    int max_frames = 0, max_pixels = 0, rc;
+    if ((rc = mf_nerf_frame_batch_limits(h, &max_frames, &max_pixels))) return rc;
+    MF_REQUIRE(n_frames >= 1 && n_frames <= max_frames, "nerf_torso_forward_batch: n_frames=%d (the handle holds 1..%d)", n_frames, max_frames);
+    MF_REQUIRE(n_pixels >= 1 && n_pixels <= max_pixels, "nerf_torso_forward_batch: n_pixels=%d (the handle's max_pixels is %d)", n_pixels, max_pixels);
+    MF_REQUIRE(torso, "nerf_torso_forward_batch: null torso handle");
+    MF_REQUIRE(torso->fused, "nerf_torso_forward_batch: needs the fused torso kernel (unset MF_TORSO=gemm)");
+    for (int i = 0; i < n_frames; ++i)
+        MF_REQUIRE(descs[i].bg_coords && descs[i].bg_out, "nerf_torso_forward_batch: frame %d: null bg_coords or bg_out", i);
+    hipStream_t s = (hipStream_t)stream;
+    int slot;
+    void* host;
+    if ((rc = mf_nerf_frame_batch_acquire(h, &slot, &host))) return rc;
+    NerfTorsoFrame* tab = (NerfTorsoFrame*)host;
+    for (int i = 0; i < n_frames; ++i) {
+        const mf_nerf_torso_desc& d = descs[i];
+        NerfTorsoFrame& t = tab[i];
+        float bias[64];
+        torso->frame_bias(d.frame_consts, bias);
+        for (int o = 0; o < 32; ++o) { t.bias_d[o] = bias[o]; t.bias_t[o] = bias[32 + o]; }
+        t.bg_coords = d.bg_coords; t.bg = d.bg_color; t.out = d.bg_out; t.alpha_out = d.torso_alpha; t.deform = d.deform;
+        t.thresh = d.density_thresh; t.bg_const = d.bg_const; t.bg_per_ray = d.bg_per_ray; t.pad = 0;
+    }
+    const void* dev;
+    if ((rc = mf_nerf_frame_batch_upload(h, slot, (size_t)n_frames * sizeof(NerfTorsoFrame), s, &dev))) return rc;
+    rc = mf_nerf_torso_batch_launch(torso->consts(), (const NerfTorsoFrame*)dev, n_frames, torso->sampled(), n_pixels, s);
+    const int rc2 = mf_nerf_frame_batch_release(h, slot, s);
+    return rc ? rc : rc2;
 }
 
 extern "C" int mf_nerf_torso_set_grid(mf_nerf_torso* h, const float* density_grid) {

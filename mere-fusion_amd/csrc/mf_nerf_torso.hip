@@ -12,6 +12,7 @@
 // nets than the bf16x3 GEMMs were.  Everything outside the dense layers rounds as written (contraction off), so the frequency
 // features, the warp and the grid features are bit-identical to mf_freq_encode_forward / mf_grid_encode_forward.
 #include "mf_nerf_host.h"
+#include "mf_nerf_frame_batch.h"
 #include "mf_nerf_grid.h"
 #include <cmath>
 
@@ -37,7 +38,12 @@ struct TorsoFusedArgs {
     const float* noise;
     float* xys_out;
     float inv_gm1, cell_scale, cell_half;
+    // several frames in one launch (k_torso_fused<T_BATCH>): the frame table; what is per frame above (bg_coords, bg, the biases, thresh, bg_const, bg_per_ray and
+    // the outputs) is then read from frames[blockIdx.y]
+    const NerfTorsoFrame* frames;
 };
+
+constexpr int T_FRAME = 0, T_SWEEP = 1, T_BATCH = 2;      // what a launch of k_torso_fused walks: one frame's pixels, the occupancy grid's cells, several frames' pixels
 
 // the frequency features' sine is the reference's own: freqencoder.cu:56 calls __sinf -- the hardware sine of x / 2 pi -- and so does k_freq_encode (mf_nerf.hip);
 // rounds 3 - 4 called the accurate sinf() here, 32 range reductions of ~50 instructions per pixel: a quarter of the kernel's VALU work for a feature the
@@ -127,10 +133,19 @@ __device__ __forceinline__ float torso_cell_position(int c, float inv_gm1, float
 // SWEEP off: one frame of `run_torso`, a lane per pixel of bg_coords.  SWEEP on: the torso branch of `update_extra_state` (renderer.py:506-519), a lane per
 // cell of the G x G occupancy grid -- lane n is cell (x, y) = (n % G, n / G), its point formed by torso_cell_position, the same per-point arithmetic, and the
 // raw alpha stored at alpha_out[y G + x] = alpha_out[n] (the reference's transposed index, :510) with no occupancy mask and no colour mix.
-template <bool SWEEP>
+// T_BATCH: T_FRAME for the frames of a table, the frame in blockIdx.y -- every frame has its own ceil(N / 256) workgroups (the last one partial), so a pixel
+// sits in the lane and the workgroup it has in a launch of its frame alone, and runs the same statements.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
+    constexpr bool SWEEP = MODE == T_SWEEP, BATCH = MODE == T_BATCH;
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= a.N) return;
+    // the frame's table entry: read-only for the whole launch, so its uniform loads may be scalar loads like the weights'
+    const NerfTorsoFrame* fr = BATCH ? a.frames + blockIdx.y : nullptr;
+    const float* bias_d = a.bias_d;
+    const float* bias_t = a.bias_t;
+    const float* bg_coords = a.bg_coords;
+    if constexpr (BATCH) { bias_d = fr->bias_d; bias_t = fr->bias_t; bg_coords = fr->bg_coords; }
     float2 bc;
     int sweep_row = 0;
     if constexpr (SWEEP) {
@@ -144,7 +159,7 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
         bc.x = torso_cell_position(cx, a.inv_gm1, a.cell_scale, a.cell_half, a.noise != nullptr, u0);
         bc.y = torso_cell_position(cy, a.inv_gm1, a.cell_scale, a.cell_half, a.noise != nullptr, u1);
     } else {
-        bc = *reinterpret_cast<const float2*>(a.bg_coords + 2 * (size_t)n);
+        bc = *reinterpret_cast<const float2*>(bg_coords + 2 * (size_t)n);
     }
     // TH / TX: [grid 32 | x 2 | sin, cos of 2^f x, f = 0..7 (freqencoder.cu:30-58: sinf(scalbnf(x, f) + phase)) ]
     f32x2 in[(TG + FQ) / 2];                      // pairs 0..15: grid features, 16..32: frequency features
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
         f32x2 fqv[FQ / 2], h[HID / 2];
 #pragma unroll
         for (int j = 0; j < FQ / 2; ++j) fqv[j] = in[TG / 2 + j];
-        dense_to_lds<FQ / 2, HID, true, true>(w + W_D1, a.bias_d, fqv, col);
+        dense_to_lds<FQ / 2, HID, true, true>(w + W_D1, bias_d, fqv, col);
         from_lds(col, h);
         dense_to_lds<HID / 2, HID, true, false>(w + W_D2, nullptr, h, col);
         from_lds(col, h);
@@ -226,7 +241,7 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
     float o4[4];
     {
         f32x2 h[HID / 2];
-        dense_to_lds<(TG + FQ) / 2, HID, true, true>(w + W_T1, a.bias_t, in, col);
+        dense_to_lds<(TG + FQ) / 2, HID, true, true>(w + W_T1, bias_t, in, col);
         from_lds(col, h);
         dense_to_lds<HID / 2, HID, true, false>(w + W_T2, nullptr, h, col);
         from_lds(col, h);
@@ -249,17 +264,25 @@ __global__ __launch_bounds__(256) void k_torso_fused(const TorsoFusedArgs a) {
     const float wx = gx - fx, wy = gy - fy;
     auto at = [&](int y, int x) { return (x >= 0 && x < G && y >= 0 && y < G) ? a.density[y * G + x] : 0.f; };   // zeros padding
     const float occ = at(y0, x0) * (1 - wx) * (1 - wy) + at(y0, x0 + 1) * wx * (1 - wy) + at(y0 + 1, x0) * (1 - wx) * wy + at(y0 + 1, x0 + 1) * wx * wy;
-    const bool m = occ > a.thresh;
+    float thresh = a.thresh, bg_const = a.bg_const;
+    int bg_per_ray = a.bg_per_ray;
+    const float* bg = a.bg;
+    float *out = a.out, *alpha_out = a.alpha_out, *deform = a.deform;
+    if constexpr (BATCH) {
+        thresh = fr->thresh; bg_const = fr->bg_const; bg_per_ray = fr->bg_per_ray; bg = fr->bg;
+        out = fr->out; alpha_out = fr->alpha_out; deform = fr->deform;
+    }
+    const bool m = occ > thresh;
     float sg[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) sg[k] = m ? (1.f / (1.f + __expf(-o4[k]))) * 1.002f - 0.001f : 0.f;
     // every store sits behind the last weight load: a load the compiler can prove unclobbered since kernel entry becomes a scalar load
-    if (a.deform) *reinterpret_cast<float2*>(a.deform + 2 * (size_t)n) = make_float2(dx[0], dx[1]);
-    if (a.alpha_out) a.alpha_out[n] = sg[0];
+    if (deform) *reinterpret_cast<float2*>(deform + 2 * (size_t)n) = make_float2(dx[0], dx[1]);
+    if (alpha_out) alpha_out[n] = sg[0];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float b = a.bg ? (a.bg_per_ray ? a.bg[3 * (size_t)n + k] : a.bg[k]) : a.bg_const;
-        a.out[3 * (size_t)n + k] = sg[1 + k] * sg[0] + b * (1.f - sg[0]);
+        const float b = bg ? (bg_per_ray ? bg[3 * (size_t)n + k] : bg[k]) : bg_const;
+        out[3 * (size_t)n + k] = sg[1 + k] * sg[0] + b * (1.f - sg[0]);
     }
 }
 
@@ -296,9 +319,10 @@ __global__ void k_torso_grid_mean(const double* __restrict__ partials, int n_par
     *mean_out = (float)(acc / cells);
 }
 
+// bias: null for a batch (the biases are in the frame table)
 int torso_args(TorsoFusedArgs& a, const NerfTorsoConsts& t, const float* bias, int N) {
     a.w = t.w; a.emb = t.emb;
-    for (int i = 0; i < HID; ++i) { a.bias_d[i] = bias[i]; a.bias_t[i] = bias[HID + i]; }
+    for (int i = 0; bias && i < HID; ++i) { a.bias_d[i] = bias[i]; a.bias_t[i] = bias[HID + i]; }
     GridLevels lv;
     if (const int rc = mf_grid_levels(lv, t.offsets, NLEV, t.log2_pls, (uint32_t)t.base_res)) return rc;
     for (int l = 0; l < NLEV; ++l) { a.scale[l] = lv.scale[l]; a.resolution[l] = lv.resolution[l]; a.offset[l] = lv.offset[l]; a.hashmap_size[l] = lv.hashmap_size[l]; }
@@ -319,7 +343,18 @@ int mf_nerf_torso_fused_launch(const NerfTorsoConsts& t, const float* bias, cons
     a.bg_coords = bg_coords; a.density = density; a.bg = bg;
     a.thresh = thresh; a.bg_const = bg_const; a.bg_per_ray = bg_per_ray;
     a.out = out; a.alpha_out = alpha_out; a.deform = deform;
-    hipLaunchKernelGGL(k_torso_fused<false>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_torso_fused<T_FRAME>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+// tab_dev: n_frames entries on the device (the caller has checked every frame's pointers, N > 0 and 1 <= n_frames <= 64)
+int mf_nerf_torso_batch_launch(const NerfTorsoConsts& t, const NerfTorsoFrame* tab_dev, int n_frames, const float* density, int N, hipStream_t s) {
+    TorsoFusedArgs a{};
+    int rc;
+    if ((rc = torso_args(a, t, nullptr, N))) return rc;
+    a.density = density; a.frames = tab_dev;
+    hipLaunchKernelGGL(k_torso_fused<T_BATCH>, dim3((unsigned)((N + 255) / 256), (unsigned)n_frames), dim3(256), 0, s, a);
     MF_HIP(hipGetLastError());
     return MF_OK;
 }
@@ -337,7 +372,7 @@ int mf_nerf_torso_grid_launch(const NerfTorsoConsts& t, const float* bias, const
     const double half = 1.0 / (double)G;
     a.inv_gm1 = 1.0f / (float)(G - 1); a.cell_scale = (float)(1.0 - half); a.cell_half = (float)half;
     const int nwg = cells / TG_T;
-    hipLaunchKernelGGL(k_torso_fused<true>, dim3((unsigned)nwg), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_torso_fused<T_SWEEP>, dim3((unsigned)nwg), dim3(256), 0, s, a);
     MF_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_torso_dilate_ema, dim3((unsigned)nwg), dim3(TG_T), 0, s, raw_grid, density_grid, G, decay, partials);
     MF_HIP(hipGetLastError());

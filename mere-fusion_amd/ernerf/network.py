@@ -151,11 +151,13 @@ class HipRenderMixin:
         r.enc_a = self.enc_a if self.smooth_lips else None
         return auds
 
-    def render_frames(self, jobs, dt_gamma=0, max_steps=1024, T_thresh=1e-4, reserve_frames=0, **kwargs):
+    FRAME_BATCH = True                 # render_frames takes torso_batch (nerf_serving.NerfBatcher asks before it passes it)
+
+    def render_frames(self, jobs, dt_gamma=0, max_steps=1024, T_thresh=1e-4, reserve_frames=0, torso_batch=False, **kwargs):
         """`run_cuda` for several frames of one ray count with ONE head call (HipHeadRenderer.render_frames): jobs is a list of dicts (rays_o, rays_d, auds,
         bg_coords, poses, eye, bg_color).  The per-frame refreshes of run_cuda happen once for the group; the audio windows, the EMA and the torso are taken per
         frame, in order.  Returns one result dict per frame, each the same bits as run_cuda gives for that frame alone.  Frames the device loop does not serve
-        (see _mf_fast_path) go through run_cuda one by one.  reserve_frames: see HipHeadRenderer.run_cuda_device_batch."""
+        (see _mf_fast_path) go through run_cuda one by one.  reserve_frames: see HipHeadRenderer.run_cuda_device_batch; torso_batch: see HipHeadRenderer.render_frames."""
         kw = dict(dt_gamma=dt_gamma, max_steps=max_steps, T_thresh=T_thresh)
         if not jobs:
             return []
@@ -185,7 +187,7 @@ class HipRenderMixin:
             else:
                 self._mf_audio_in(r, None)                              # the renderer applies the EMA frame by frame from the module's state
                 feed = jobs
-            outs = r.render_frames(feed, reserve_frames=reserve_frames, dt_gamma=float(dt_gamma), max_steps=int(max_steps), T_thresh=float(T_thresh))
+            outs = r.render_frames(feed, reserve_frames=reserve_frames, torso_batch=torso_batch, dt_gamma=float(dt_gamma), max_steps=int(max_steps), T_thresh=float(T_thresh))
             if self.smooth_lips and not self.emb:
                 self.enc_a = r.enc_a
         self.__dict__["_mf_frame_id"] = self._mf_frame_id + 1

@@ -253,13 +253,16 @@ class HipHeadRenderer:
                                                            p(out["frame_u8"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_batch_finish")
         return outs
 
+    FRAME_BATCH = True                  # render_frames takes torso_batch (nerf_serving.NerfBatcher asks before it passes it)
+
     @torch.no_grad()
-    def render_frames(self, jobs, reserve_frames=0, **kw):
+    def render_frames(self, jobs, reserve_frames=0, torso_batch=False, **kw):
         """`render(..., loop="device")` for several frames with ONE head call: jobs is a list of dicts (rays_o, rays_d, auds, bg_coords, poses, eye, bg_color), kw
         the render keywords they share (dt_gamma, max_steps, T_thresh, want_u8).  Per frame and in order: audio window -> enc_a with the lip-smoothing EMA; then the
         batched head, left unfinished when there is a torso net; then per frame the torso and the finish.  Same kernels per frame, same bits.
         A job may carry `ema`, a one-element list: the EMA value its frame continues (installed before the frame's audio, written back after it), so that frames of
-        several sessions -- each with its own lip-smoothing state -- share one call (nerf_serving.NerfBatcher)."""
+        several sessions -- each with its own lip-smoothing state -- share one call (nerf_serving.NerfBatcher).
+        torso_batch: the frames' torso branches go out as one launch too (HipTorso.run_torso_batch: mf_nerf_torso_forward_batch), the same bits per frame."""
         frames = []
         for j in jobs:
             box = j.get("ema")
@@ -272,7 +275,11 @@ class HipHeadRenderer:
         if self.torso is None:
             return self.run_cuda_device_batch(frames, reserve_frames=reserve_frames, **kw)
         outs = self.run_cuda_device_batch(frames, finish=False, reserve_frames=reserve_frames, **kw)
-        return self.finish_device_batch(outs, [self.torso.run_torso(j["bg_coords"], j["poses"], j.get("bg_color"))["bg_color"] for j in jobs])
+        if torso_batch and os.environ.get("MF_TORSO") != "gemm":
+            bgs = [t["bg_color"] for t in self.torso.run_torso_batch([(j["bg_coords"], j["poses"], j.get("bg_color")) for j in jobs])]
+        else:
+            bgs = [self.torso.run_torso(j["bg_coords"], j["poses"], j.get("bg_color"))["bg_color"] for j in jobs]
+        return self.finish_device_batch(outs, bgs)
 
     GRID_SIZES = (32, 64, 128)          # what the grid-maintenance entry points serve (the reference always uses 128); the library's rule: mf_nerf_occupancy_shape
 

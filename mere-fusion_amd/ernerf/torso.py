@@ -81,6 +81,10 @@ class HipTorso:
         if h:
             self._lib.mf_nerf_torso_destroy(h)
             self._h = None
+        fb = getattr(self, "_fb", None)
+        if fb:
+            self._lib.mf_nerf_frame_batch_destroy(fb)
+            self._fb = None
 
     @torch.no_grad()
     def run_torso(self, bg_coords, poses, bg_color=None, density_grid=None):
@@ -104,6 +108,52 @@ class HipTorso:
                                                    self.thresh, N, p(out), p(alpha), p(deform), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                    "mf_nerf_torso_forward")
         return {"bg_color": out, "torso_alpha": alpha.view(N, 1), "deform": deform}
+
+    MAX_BATCH_FRAMES = 64               # the library's limit per call
+
+    @torch.no_grad()
+    def run_torso_batch(self, frames, density_grid=None):
+        """`run_torso` for several frames of one pixel count in ONE launch (mf_nerf_torso_forward_batch): frames is a list of (bg_coords, poses, bg_color) as
+        run_torso takes them; returns the list of the dicts run_torso returns, each the same bits as run_torso gives for that frame alone.  The frame constants
+        travel in the call's descriptor table.  All frames sample one grid."""
+        F = len(frames)
+        if not 1 <= F <= self.MAX_BATCH_FRAMES:
+            raise RuntimeError(f"HipTorso.run_torso_batch: {F} frames (1..{self.MAX_BATCH_FRAMES} per call)")
+        p = lambda t: t.data_ptr() if t is not None else None
+        descs = (_lib.MfNerfTorsoDesc * F)()
+        keep, outs, N = [], [], None
+        for i, (bg_coords, poses, bg_color) in enumerate(frames):
+            if not (torch.is_tensor(bg_coords) and bg_coords.is_cuda):
+                raise RuntimeError("HipTorso.run_torso_batch: bg_coords must be a CUDA tensor (there is no CPU path)")
+            xy = bg_coords.contiguous().view(-1, 2).float()
+            if N is None:
+                N = xy.shape[0]
+            elif xy.shape[0] != N:
+                raise RuntimeError(f"HipTorso.run_torso_batch: frame {i} has {xy.shape[0]} pixels, frame 0 has {N} (one pixel count per call)")
+            consts = wrapped_anchor_code(self.anchor_points, poses, self.ind_code)
+            out, alpha, deform = torch.empty(N, 3, device=xy.device), torch.empty(N, device=xy.device), torch.empty(N, 2, device=xy.device)
+            bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
+            d = descs[i]
+            d.frame_consts[:len(consts)] = consts.tolist()
+            d.bg_coords, d.bg_color, d.bg_per_ray = p(xy), p(bg), int(bg is not None and bg.numel() == 3 * N)
+            d.bg_const, d.density_thresh = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color)), self.thresh
+            d.bg_out, d.torso_alpha, d.deform = p(out), p(alpha), p(deform)
+            keep.append((xy, bg))
+            outs.append({"bg_color": out, "torso_alpha": alpha.view(N, 1), "deform": deform})
+        fb = getattr(self, "_fb", None)
+        if fb is None or self._fb_pixels < N:
+            if fb:
+                self._lib.mf_nerf_frame_batch_destroy(fb)
+                self._fb = None
+            fb = C.c_void_p()
+            _lib.check(self._lib.mf_nerf_frame_batch_create(self.MAX_BATCH_FRAMES, N, C.byref(fb)), "mf_nerf_frame_batch_create")
+            self._fb, self._fb_pixels = fb, N
+        grid = self._grid(self.density_grid if density_grid is None else density_grid, "run_torso_batch")
+        _lib.check(self._lib.mf_nerf_torso_set_grid(self._h, C.c_void_p(grid.data_ptr())), "mf_nerf_torso_set_grid")
+        _lib.check(self._lib.mf_nerf_torso_forward_batch(self._h, fb, descs, F, N, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "mf_nerf_torso_forward_batch")
+        del keep
+        return outs
 
     @torch.no_grad()
     def update_density_grid(self, grid, poses, ind_code, noise, decay=0.95, raw_out=None, xys_out=None):

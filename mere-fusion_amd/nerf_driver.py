@@ -11,6 +11,9 @@ enqueue on the caller's stream that ends in the uint8 RGB frame a `VideoFrame` t
     model.render / HipHeadRenderer.render  the device loop (mf_nerf_head_render), as the drop-in runs it
     mf_nerf_frame_out                      utils.py:1208-1212 + nerfreal.py:110-122 (or :98-107 for a custom-video frame)
 
+`NerfFrameBatch` is the first and the last of these for the frames of many sessions in one launch each (mf_nerf_frame_batch_background / _out), the same bits per
+frame; `nerf_serving.NerfBatcher` uses it around its batched head call.
+
 No synchronisation, no graph of its own, no side stream.  `step_to_ring` hands the frame to a `transport.FrameRing` as the other two drivers do."""
 import ctypes as C
 
@@ -31,6 +34,67 @@ def loader_indices(size, index):
 
 def _refuse(msg):
     refuse("NerfSession", msg)
+
+
+class NerfFrameBatch:
+    """mf_nerf_frame_batch: `NerfSession.background` and `.frame_out` for a list of frames in ONE launch each.  The sessions of a call have the same sizes (`bg_key` /
+    `out_key`); a call takes at most `max_frames` frames of at most `max_pixels` rendered pixels each.  Nothing synchronises."""
+
+    MAX_FRAMES = 64                     # the library's limit per call
+
+    def __init__(self, max_frames, max_pixels):
+        self._lib = _lib.lib()
+        self.max_frames, self.max_pixels = int(max_frames), int(max_pixels)
+        self._h = C.c_void_p()
+        _lib.check(self._lib.mf_nerf_frame_batch_create(self.max_frames, self.max_pixels, C.byref(self._h)), "mf_nerf_frame_batch_create")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._lib.mf_nerf_frame_batch_destroy(h)
+            self._h = None
+
+    def background(self, sessions, mis):
+        """bg_color [F, H * W, 3] fp32: row i is `sessions[i].background(mis[i])` (sessions with torso images, of one `bg_key`)"""
+        s0, F = sessions[0], len(sessions)
+        if any(s.torso_imgs is None or s.bg_key() != s0.bg_key() for s in sessions):
+            refuse("NerfFrameBatch", "background: the sessions of a call have torso images and one render size")
+        out = torch.empty(F, s0.H * s0.W, 3, dtype=torch.float32, device=s0.poses.device)
+        descs = (_lib.MfNerfBgDesc * F)()
+        for i, (s, mi) in enumerate(zip(sessions, mis)):
+            d = descs[i]
+            d.torso_rgba, d.bg_image = s.torso_imgs[mi].data_ptr(), (s.bg_image.data_ptr() if s.bg_image is not None else None)
+            d.bg_const, d.half_mode, d.bg_color = s.bg_const, int(s.half), out[i].data_ptr()
+        _lib.check(self._lib.mf_nerf_frame_batch_background(self._h, descs, F, s0.H, s0.W, s0._stream()), "mf_nerf_frame_batch_background")
+        return out
+
+    def frame_out(self, sessions, images, bodies, out):
+        """`sessions[i].frame_out(images[i], bodies[i])` into out[i]: out is a contiguous uint8 block [F, FH, FW, 3] (sessions of one `out_key`).  images[i] None:
+        the custom-video frame bodies[i]."""
+        s0, F = sessions[0], len(sessions)
+        key = s0.out_key()
+        FH, FW = key[4], key[5]
+        if any(s.out_key() != key for s in sessions):
+            refuse("NerfFrameBatch", "frame_out: the sessions of a call have one render size, GUI size, frame size and colour space")
+        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (F, FH, FW, 3)):
+            refuse("NerfFrameBatch", f"frame_out: out must be a contiguous uint8 CUDA tensor [{F}, {FH}, {FW}, 3]")
+        descs = (_lib.MfNerfOutDesc * F)()
+        keep = []
+        for i, (s, image, body) in enumerate(zip(sessions, images, bodies)):
+            if image is not None:
+                image = image.reshape(s.H, s.W, 3)
+                if image.dtype != torch.float32 or not image.is_contiguous():
+                    image = image.float().contiguous()
+            if body is not None and tuple(body.shape) != (FH, FW, 3):
+                refuse("NerfFrameBatch", f"frame_out: frame {i} is {tuple(body.shape)}, the block's frames are ({FH}, {FW}, 3)")
+            keep.append(image)
+            d = descs[i]
+            d.render, d.body_bgr = (image.data_ptr() if image is not None else None), (body.data_ptr() if body is not None else None)
+            d.x0, d.y0 = (s.x0, s.y0) if (image is not None and body is not None) else (0, 0)
+        _lib.check(self._lib.mf_nerf_frame_batch_out(self._h, descs, F, s0.H, s0.W, s0.GH, s0.GW, FH, FW, int(s0.linear_to_srgb), C.c_void_p(out.data_ptr()),
+                                                     s0._stream()), "mf_nerf_frame_batch_out")
+        del keep
+        return out
 
 
 class NerfSession:
@@ -138,6 +202,15 @@ class NerfSession:
                    "mf_nerf_frame_background")
         return out
 
+    # ---- what the frames of one NerfFrameBatch call share ----------------------------------------------------------------------------
+    def bg_key(self):
+        return (self.H, self.W)
+
+    def out_key(self):
+        """(render size, GUI size, frame size, colour space): the sizes one mf_nerf_frame_batch_out call shares"""
+        FH, FW = (int(self.fullbody_frames.shape[1]), int(self.fullbody_frames.shape[2])) if self.fullbody_frames is not None else (self.GH, self.GW)
+        return (self.H, self.W, self.GH, self.GW, FH, FW, self.linear_to_srgb)
+
     def frame_out(self, image, body=None, out=None, i420=False):
         """The uint8 RGB frame: `image` [H, W, 3] fp32 (or None: `body` alone, channels reversed) resized to the GUI size, over `body` at the offset.
         out: the contiguous uint8 device tensor of the frame's size to write instead of a new one (nerf_serving.NerfBatcher: one block per step).
@@ -186,22 +259,31 @@ class NerfSession:
 
     # ---- the same frame in two halves, so that a batcher can render the frames of many sessions in one call between them (nerf_serving.NerfBatcher) ----------
     @torch.no_grad()
-    def begin(self, auds, audiotype=(0, 0), out=None):
+    def begin(self, auds, audiotype=(0, 0), out=None, defer=False):
         """The part of step() in front of the render: advances the loader and returns either the finished custom-video frame (`out` as in step) or the
         frame's render job -- a dict of what `model.render` / `render_frames` take (rays_o, rays_d, auds, bg_coords, poses, eye, bg_color) plus `mi`, the mirrored
-        index, and `body`, the body frame or None."""
+        index, and `body`, the body frame or None.
+        defer: nothing is launched for the two ends of the frame, a NerfFrameBatch call does them for many frames later: a custom-video frame comes back as
+        {"custom": image}, and a job whose background is the torso image over the background carries bg_color None until `set_background`."""
         ai, mi = loader_indices(self.size, self.index)          # the loader advances on every frame, a custom-video one included (nerfreal.py:72-76)
         self.index += 1
         self.last_audio_index, self.last_index = ai, mi
         custom = self.next_custom(audiotype)
         if custom is not None:
+            if defer:
+                return {"custom": custom, "mi": mi}
             return self.frame_out(None, custom, **({} if out is None else {"out": out}))
         pose = self.poses[mi:mi + 1]
         rays = frontend.get_rays(self._ref_get_rays, pose, self.intrinsics, self.H, self.W)
         eye = None if self.eye_area is None else self.eye_area[mi:mi + 1]
-        bg = self.background(mi)
+        bg = None if (defer and self.torso_imgs is not None) else self.background(mi)
         return {"rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "auds": auds, "bg_coords": self.bg_coords, "poses": pose, "eye": eye,
-                "bg_color": bg[None] if self._is_module else bg, "mi": mi, "body": None if self.fullbody_frames is None else self.fullbody_frames[mi]}
+                "bg_color": None if bg is None else (bg[None] if self._is_module else bg), "mi": mi, "body": None if self.fullbody_frames is None else self.fullbody_frames[mi],
+                "bg_pending": bg is None}
+
+    def set_background(self, job, bg):
+        """the deferred background of `job`: bg [H * W, 3] fp32, a row of NerfFrameBatch.background"""
+        job["bg_color"], job["bg_pending"] = (bg[None] if self._is_module else bg), False
 
     def bind_aabb(self):
         """a bare HipHeadRenderer reads the session's box (renderer.py:226 reads the buffer every frame)"""

@@ -213,7 +213,14 @@ class NerfBatcher:
     A step has three stages: `NerfSession.begin` for every frame of every picked session; the render jobs that leaves, grouped by model, ray count and render_kw,
     rendered `frames_per_render` at a time by ONE head call each (`render_frames`: mf_nerf_head_batch_render); `NerfSession.end` into the step's output blocks.  Each
     job carries its session's EMA value in a box the renderer reads before and writes after the frame's audio, so sessions that share a model share a head call
-    and still keep their own EMA.  A session or model without these entry points, and everyone under MF_NERF_BATCH=0, takes one `step` per frame."""
+    and still keep their own EMA.  A session or model without these entry points, and everyone under MF_NERF_BATCH=0, takes one `step` per frame.
+
+    frame_batch: the stages around the head call go out once per step too (nerf_driver.NerfFrameBatch, HipTorso.run_torso_batch): `begin` defers the torso image
+    over the background and the custom-video frames, ONE background launch serves every frame of a render size in front of the head calls, and ONE frame-out
+    launch per output size writes the finished frames -- rendered and custom-video ones -- into a block the
+    sessions' [B, h, w, 3] results are views of.  Frames of unequal size never share a call (`_frame_groups`).  Same bits per frame as the per-frame launches; a
+    session without `out_key` keeps them.  torso_batch: the torso branches of a head call's frames are one launch as well; off by default, because alone it
+    measured faster at 64 x 64 and slower at 512 x 512 than one launch per frame (profiles/nerf_frame_batch_timing.md)."""
 
     MAX_FRAMES_PER_RENDER = 64          # mf_nerf_head_batch's limit per call
     frame_order = "rgb"                 # channel 0 of the uint8 frames a step returns (mf_nerf_frame_out)
@@ -222,7 +229,7 @@ class NerfBatcher:
         """(H, W) of session k's frames"""
         return self.out_shape[k][:2]
 
-    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32):
+    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32, frame_batch=True, torso_batch=False):
         who = "NerfBatcher"
         self.sessions, self.batch_size, self.pool, self.device = list(sessions), int(batch_size), pool, torch.device(device)
         if not self.sessions:
@@ -245,6 +252,7 @@ class NerfBatcher:
                                      f"(a step's {self.batch_size} frames leave as one block)")
             self.out_shape.append(hw + (3,))
         self.enc_a = [None] * len(self.sessions)
+        self.frame_batch, self.torso_batch, self._fb = bool(frame_batch), bool(torso_batch), None
 
     def _check_input(self, k, inp):
         B = self.batch_size
@@ -275,20 +283,27 @@ class NerfBatcher:
         batched = os.environ.get("MF_NERF_BATCH", "1") != "0"           # read per step; "0": one NerfSession.step per frame for everyone (A/B, cross-checks)
         out = [None] * len(self.sessions)
         jobs, ema = [], {}              # jobs: (session, frame, render job) in session order then frame order; ema: per session, the one-element box its jobs carry
+        fb = batched and self.frame_batch
+        ends = []                       # frame_batch: (session, slot of the frame in its size's block, job) for every deferred frame, custom-video ones included
+        blocks = self._blocks([k for k in picked if fb and self._can_frame_batch(self.sessions[k])], inputs) if fb else {}
         try:
             # ---- begin: every frame of every picked session (loader, custom-video frames, rays, background); nothing is rendered yet
             for k in picked:
                 s, (auds, types) = self.sessions[k], inputs[k]
-                frames = torch.empty((B,) + self.out_shape[k], dtype=torch.uint8, device=auds.device)
+                defer = k in blocks
+                frames = blocks[k][0][blocks[k][1]:blocks[k][1] + B] if defer else torch.empty((B,) + self.out_shape[k], dtype=torch.uint8, device=auds.device)
                 idx = []
                 shared = hasattr(s.model, "enc_a")
                 if batched and self._can_batch(s):
                     if shared:
                         ema[k] = [self.enc_a[k]]
                     for b in range(B):
-                        job = s.begin(auds[b], (int(types[b][0]), int(types[b][1])), out=frames[b])
+                        at = (int(types[b][0]), int(types[b][1]))
+                        job = s.begin(auds[b], at, defer=True) if defer else s.begin(auds[b], at, out=frames[b])
                         idx.append(s.last_index)
-                        if isinstance(job, dict):                        # (anything else: the finished custom-video frame, already in frames[b])
+                        if defer:
+                            ends.append((k, blocks[k][1] + b, job))
+                        if isinstance(job, dict) and "custom" not in job:   # (anything else: a custom-video frame, finished in frames[b] or deferred)
                             if shared:
                                 job["ema"] = ema[k]
                             jobs.append((k, b, job))
@@ -303,19 +318,76 @@ class NerfBatcher:
                         if shared:
                             self.enc_a[k] = s.model.enc_a
                 out[k] = (frames, idx)
+            # ---- the deferred backgrounds: one launch per render size
+            for group in self._frame_groups([(k, job) for k, _, job in jobs if job.get("bg_pending") and k in blocks], lambda s: s.bg_key()):
+                for c in range(0, len(group), self._frame_batch().max_frames):
+                    chunk = group[c:c + self._frame_batch().max_frames]
+                    bgs = self._frame_batch().background([self.sessions[k] for k, _ in chunk], [job["mi"] for _, job in chunk])
+                    for (k, job), bg in zip(chunk, bgs):
+                        self.sessions[k].set_background(job, bg)
             # ---- group and render, then end into the step's output blocks
             for group in self._groups(jobs):
                 s0 = self.sessions[group[0][0]]
+                extra = {"torso_batch": True} if (fb and self.torso_batch and getattr(s0.model, "FRAME_BATCH", False)) else {}
                 for c in range(0, len(group), self.frames_per_render):
                     chunk = group[c:c + self.frames_per_render]
                     s0.bind_aabb()
-                    res = s0.model.render_frames([job for _, _, job in chunk], reserve_frames=self._most_frames(s0.model), **s0.render_kw)
+                    res = s0.model.render_frames([job for _, _, job in chunk], reserve_frames=self._most_frames(s0.model), **extra, **s0.render_kw)
                     for (k, b, job), r in zip(chunk, res):
-                        self.sessions[k].end(job, r["image"], out=out[k][0][b])
+                        if k in blocks:
+                            job["image"] = r["image"]
+                        else:
+                            self.sessions[k].end(job, r["image"], out=out[k][0][b])
+            # ---- the deferred frames: one launch per output size and run of neighbouring slots of its block
+            for run in self._out_runs(ends, blocks):
+                k0, slot0, _ = run[0]
+                self._frame_batch().frame_out([self.sessions[k] for k, _, _ in run], [job.get("image") for _, _, job in run],
+                                              [job["custom"] if "custom" in job else job["body"] for _, _, job in run], blocks[k0][0][slot0:slot0 + len(run)])
         finally:
             for k, box in ema.items():
                 self.enc_a[k] = box[0]
         return out
+
+    # ---- the stages around the head call, once per step (frame_batch) ---------------------------------------------------------------------
+    @staticmethod
+    def _can_frame_batch(s):
+        return NerfBatcher._can_batch(s) and all(hasattr(s, n) for n in ("out_key", "bg_key", "set_background"))
+
+    def _frame_batch(self):
+        if self._fb is None:
+            from .nerf_driver import NerfFrameBatch
+            self._fb = NerfFrameBatch(NerfFrameBatch.MAX_FRAMES, max(s.H * s.W for s in self.sessions if self._can_frame_batch(s)))
+        return self._fb
+
+    def _frame_groups(self, items, key):
+        """items: (session number, anything) in step order, grouped by key(session): frames of unequal size land in different calls; a group keeps the order of
+        `items`, the groups the order in which their first item appears"""
+        groups = {}
+        for it in items:
+            groups.setdefault(key(self.sessions[it[0]]), []).append(it)
+        return list(groups.values())
+
+    def _blocks(self, ks, inputs):
+        """{session: (block, first slot)}: per output size one uint8 block [n * B, h, w, 3] for the n sessions of `ks` with that size; session k's B frames are the
+        slots from its first slot on, so its result is a view and neighbours in `ks` of one size are neighbours in the block"""
+        B, by_key = self.batch_size, {}
+        for k in ks:
+            by_key.setdefault(self.sessions[k].out_key(), []).append(k)
+        blocks = {}
+        for key, members in by_key.items():
+            block = torch.empty((len(members) * B,) + self.out_shape[members[0]], dtype=torch.uint8, device=inputs[members[0]][0].device)
+            for i, k in enumerate(members):
+                blocks[k] = (block, i * B)
+        return blocks
+
+    def _out_runs(self, ends, blocks):
+        """the deferred frames as the frame-out calls take them: per output size (one block each) in slot order, cut into runs of at most max_frames frames"""
+        runs = []
+        for group in self._frame_groups(ends, lambda s: s.out_key()):
+            group = sorted(group, key=lambda e: e[1])
+            cap = self._frame_batch().max_frames
+            runs += [group[c:c + cap] for c in range(0, len(group), cap)]
+        return runs
 
     @staticmethod
     def _can_batch(s):
