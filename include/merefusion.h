@@ -786,6 +786,21 @@ int mf_resize_linear_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh
  * accesses; the bytes are the same.  Refuses null pointers, n_frames < 1, non-positive or odd H / W and an rgb_order other
  * than 0 / 1 (MF_ERR_INVALID, the value named in mf_last_error) before anything is launched. */
 int mf_frames_to_i420(const uint8_t* frames, int n_frames, int H, int W, int rgb_order, uint8_t* out, void* stream);
+/* Finished frames from anywhere into chosen frames of one block (csrc/mf_frame_gather.hip): the idle and custom-video frames
+ * a session shows while it listens (lipreal.py:198-205, musereal.py:229-236), delivered like the generated ones. */
+typedef struct mf_frame_src {
+    const uint8_t* frame;     /* device, contiguous uint8 [H][W][3]: a cached avatar frame, a frame of a custom cycle, ... */
+    int dst;                  /* frame number inside `out` */
+} mf_frame_src;
+/* srcs: HOST array of n entries, read during the call only (the table travels in the launch arguments, 64 sources per
+ * launch; a longer list goes out as several launches).  out: device uint8 [out_frames][H][W][3] (format 0: a copy; odd H and
+ * W are fine) or [out_frames][H * 3 / 2][W] (format 1: the layout and the bytes of mf_frames_to_i420 for the same pixels,
+ * rgb_order as there; H and W even).  Frames of `out` that no source names keep their bytes.  One path per call: 8-pixel
+ * strips (format 1, W % 8 == 0) or 16-byte units (format 0, H * W * 3 % 4 == 0) when `out` and EVERY source are 4-byte
+ * aligned, byte accesses otherwise; the bytes are the same.  Refuses null pointers, n < 1, out_frames < 1, non-positive H / W,
+ * odd H / W in format 1, a format or rgb_order other than 0 / 1, a dst outside [0, out_frames), two sources with one dst and a
+ * source that lies inside `out` (MF_ERR_INVALID, the value named in mf_last_error) before anything is launched. */
+int mf_frames_gather(const mf_frame_src* srcs, int n, int H, int W, int format, int rgb_order, uint8_t* out, int out_frames, void* stream);
 
 /* ---- ER-NeRF audio front-end: wav2vec2 / HuBERT CTC network ----------------------------------- */
 /* Replaces `self.processor(frame, ...)` + `self.model(inputs.input_values)` of NerfASR.__frame_to_text (nerfasr.py:128-143):

@@ -87,6 +87,11 @@ class MfPasteJob(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("frame_index", "x1", "y1", "x2", "y2", "cx1", "cy1", "cx2", "cy2")] + [("mask", C.c_void_p)]
 
 
+class MfFrameSrc(C.Structure):
+    """mf_frame_src: one source frame of mf_frames_gather"""
+    _fields_ = [("frame", C.c_void_p), ("dst", C.c_int)]
+
+
 class MfCropJob(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("frame_index", "x1", "y1", "x2", "y2")]
 
@@ -288,6 +293,7 @@ SIGNATURES = {
     "mf_stream_synchronize": (C.c_int, [C.c_void_p]),
     "mf_resize_linear_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mf_frames_to_i420": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mf_frames_gather": (C.c_int, [C.POINTER(MfFrameSrc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 _lib = None

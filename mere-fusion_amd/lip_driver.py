@@ -74,14 +74,16 @@ class LipASRFrontend:
 class LipSession(SessionWalk):
     """One talking-head session: cached uint8 face crops on the device + the generator.  With `avatar_frames`
     (mere_fusion_amd.paste.AvatarFrames built from frame_list_cycle / coord_list_cycle with lip_order=True) `step_pasted` also does
-    process_frames' paste-back (lipreal.py:207-214) on the device."""
+    process_frames' paste-back (lipreal.py:207-214) on the device.  custom_videos (paste.CustomVideos): what the session shows for non-speech frames of a custom
+    audio type when its scheduler runs with idle_frames=True; frames of another size than the avatar's are refused here."""
 
-    def __init__(self, model, faces_u8, avatar_frames=None):
+    def __init__(self, model, faces_u8, avatar_frames=None, custom_videos=None):
         self.model = model
         self.faces = faces_u8 if torch.is_tensor(faces_u8) else torch.from_numpy(np.asarray(faces_u8))
         self.faces = self.faces.to(next(model.parameters()).device)
         self.avatar_frames = avatar_frames
         self.length = self.faces.shape[0]                           # (pool_offset: first row of this session's crops in a LipBatcher's pool)
+        self.attach_custom_videos(custom_videos)
 
     def step(self, mel_batch):
         """lipreal.py:109-137 for one non-silent batch: returns fp32 frames [B,96,96,3] (pred*255) and
@@ -245,7 +247,8 @@ class LipEndToEndScheduler(PipelinedScheduler):
     Everything else (picking, reservation, deferral episodes in `ring_full`, publish order, the waiter thread, close(), single_stream) is PipelinedScheduler's code.
     A window slides when its batch is PICKED, not when it is submitted, and once (`_advance`): it is one device row per session, and several batches may be queued."""
 
-    def __init__(self, batcher, frontends=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed"):
+    def __init__(self, batcher, frontends=None, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed",
+                 idle_frames=False):
         fes = batcher.frontends() if frontends is None else list(frontends)
         if len(fes) != len(batcher.sessions):                             # before anything (streams, the parent's state) is created
             raise RuntimeError("one LipASRDeviceFrontend per session is required")
@@ -254,7 +257,8 @@ class LipEndToEndScheduler(PipelinedScheduler):
                 raise RuntimeError(f"frontend {k}: one LipASRDeviceFrontend per session, row k of one pool, is required (LipBatcher.frontends())")
         if frame_format == "i420" and not batcher.paste:
             raise RuntimeError("LipEndToEndScheduler: frame_format='i420' converts the pasted uint8 frames; the batcher was built with paste=False (fp32 crops)")
-        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format,
+                         idle_frames=idle_frames)
         self.frontends, self.windows = fes, fes[0].pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):

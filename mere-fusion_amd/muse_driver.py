@@ -81,15 +81,18 @@ class MuseASRFrontend:
 
 class MuseSession(SessionWalk):
     """One talking-head session: the avatar's cached latents (musereal.py:64 `torch.load(latents.pt)`: a list of [1, 8, 32, 32] tensors)
-    and its position in the ping-pong walk.  `avatar_frames` (mere_fusion_amd.paste.AvatarFrames) enables the GPU paste-back."""
+    and its position in the ping-pong walk.  `avatar_frames` (mere_fusion_amd.paste.AvatarFrames) enables the GPU paste-back.  custom_videos
+    (paste.CustomVideos): what the session shows for non-speech frames of a custom audio type when its scheduler runs with idle_frames=True; frames of another
+    size than the avatar's are refused here."""
 
-    def __init__(self, latents, avatar_frames=None):
+    def __init__(self, latents, avatar_frames=None, custom_videos=None):
         lat = latents if torch.is_tensor(latents) else torch.cat([torch.as_tensor(x).reshape(1, *torch.as_tensor(x).shape[-3:]) for x in latents], dim=0)
         self.latents = lat.float().contiguous()
         self.length = self.latents.shape[0]
         self.avatar_frames = avatar_frames
         if avatar_frames is not None and avatar_frames.n != self.length:
             raise RuntimeError("one cached full frame per cached latent is required (frame_list_cycle / input_latent_list_cycle)")
+        self.attach_custom_videos(custom_videos)
 
 
 class MuseBatcher(PooledBatcher):
@@ -154,10 +157,11 @@ class EndToEndScheduler(PipelinedScheduler):
     Stages can be switched off individually to price them (bench.py `paced_sessions.stages`)."""
 
     def __init__(self, batcher, frontends, audio_processor, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, fixed_chunks=None,
-                 asr_stream=True, single_stream=False, frame_format="packed"):
+                 asr_stream=True, single_stream=False, frame_format="packed", idle_frames=False):
         if len(frontends) != len(batcher.sessions):
             raise RuntimeError("one MuseASRFrontend per session is required")
-        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
+        super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format,
+                         idle_frames=idle_frames)
         # (fixed_chunks: measurement only, this [B, 50, 384] tensor instead of the Whisper stage)
         self.fixed_chunks, self.frontends, self.audio_processor = fixed_chunks, list(frontends), audio_processor
         # The Whisper front-end of a step on its OWN stream: with two steps in flight it runs beside the previous step's VAE instead of between that VAE and

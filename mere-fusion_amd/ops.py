@@ -168,6 +168,51 @@ def frames_to_i420(frames, order="bgr", out=None):
     return out
 
 
+FRAME_FORMATS = {"packed": 0, "i420": 1}
+
+
+def gather_frames(sources, dst, out, fmt="packed", order="bgr"):
+    """Finished frames from anywhere into chosen frames of one block, in one call (mf_frames_gather, csrc/mf_frame_gather.hip): sources a list of contiguous uint8
+    [H, W, 3] device tensors or views -- a cached avatar frame, a frame of a custom cycle; they need not share an allocation -- and dst, one int per source: source i
+    becomes frame dst[i] of `out`, contiguous uint8 [N, H, W, 3] (fmt "packed": a copy) or [N, H * 3 / 2, W] (fmt "i420": the bytes frames_to_i420 gives for the
+    same pixels, channels in `order`; H and W even).  Frames of `out` that dst does not name keep their bytes; two sources with one dst are refused.  Returns out."""
+    if fmt not in FRAME_FORMATS:
+        raise RuntimeError(f"gather_frames: fmt must be 'packed' or 'i420', got {fmt!r}")
+    if order not in FRAME_ORDERS:
+        raise RuntimeError(f"gather_frames: order must be 'bgr' or 'rgb', got {order!r}")
+    sources, dst = list(sources), [int(d) for d in dst]
+    if not sources or len(sources) != len(dst):
+        raise RuntimeError(f"gather_frames: {len(sources)} sources for {len(dst)} destination frames (at least one, and one dst per source)")
+    if not torch.is_tensor(out):
+        raise RuntimeError(f"gather_frames: out must be a uint8 device tensor, got {type(out).__name__}")
+    _require_cuda("gather_frames", out)
+    for i, t in enumerate(sources):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f"gather_frames: source {i}: expected a uint8 device tensor, got {type(t).__name__}")
+        _require_cuda("gather_frames", t)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous() or t.shape != sources[0].shape or t.device != out.device:
+            raise RuntimeError(f"gather_frames: source {i} must be contiguous uint8 [H, W, 3] on {out.device} like source 0 {tuple(sources[0].shape)}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    H, W = int(sources[0].shape[0]), int(sources[0].shape[1])
+    if fmt == "i420" and (H % 2 or W % 2):
+        raise RuntimeError(f"gather_frames: frame size {H} x {W} (H x W) is odd; 4:2:0 chroma covers 2 x 2 blocks")
+    want = (H * 3 // 2, W) if fmt == "i420" else (H, W, 3)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != len(want) + 1 or tuple(out.shape[1:]) != want or out.shape[0] < 1:
+        raise RuntimeError(f"gather_frames: out must be a contiguous uint8 tensor [N, {', '.join(str(v) for v in want)}] for {H} x {W} frames as {fmt}, got {out.dtype} "
+                           f"{tuple(out.shape)}{'' if out.is_contiguous() else ' (not contiguous)'}")
+    N = int(out.shape[0])
+    bad = [d for d in dst if not 0 <= d < N]
+    if bad or len(set(dst)) != len(dst):
+        raise RuntimeError(f"gather_frames: dst {dst} must name distinct frames of out, 0 to {N - 1}")
+    srcs = (_lib.MfFrameSrc * len(sources))()
+    for s, t, d in zip(srcs, sources, dst):
+        s.frame, s.dst = t.data_ptr(), d
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().mf_frames_gather(srcs, len(sources), H, W, FRAME_FORMATS[fmt], FRAME_ORDERS[order], out.data_ptr(), N, _stream_ptr(out.device)),
+                   "frames_gather")
+    return out
+
+
 def lanczos4_tables(ssize, dsize):
     """One axis of cv::resize's INTER_LANCZOS4 tables for 8-bit images (imgproc/src/resize.cpp, OpenCV 4.x as published): -> (ofs int32 [dsize], coef int16
     [dsize, 8]).  Position fx = (float)((d + 0.5) * scale - 0.5), scale = 1 / (dsize / ssize) in double; s = floor(fx); tap k reads source index ofs + k with

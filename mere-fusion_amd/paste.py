@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import frames_to_i420                                      # noqa: F401  (re-exported: the frames' last launch before the ring)
+from .ops import frames_to_i420, gather_frames                       # noqa: F401  (re-exported: the frames' last launches before the ring)
 
 
 def _dev_u8(x, device):
@@ -51,6 +51,13 @@ class AvatarFrames:
                 if tuple(m.shape) != (ye - ys, xe - xs, 3):
                     raise RuntimeError(f"mask shape {tuple(m.shape)} does not match its crop box {(xs, ys, xe, ye)}")
 
+    def source(self, i):
+        """the device view of cached full frame i, uint8 [H, W, 3]: what a listening session shows (`frame_list_cycle[idx]`, lipreal.py:205 / musereal.py:236) and
+        what ops.gather_frames takes as a source"""
+        if not 0 <= int(i) < self.n:
+            raise RuntimeError(f"AvatarFrames.source: frame {i} of {self.n}")
+        return self.frames[int(i)]
+
     def jobs(self, indices):
         arr = (_lib.MfPasteJob * len(indices))()
         for k, i in enumerate(indices):
@@ -88,6 +95,42 @@ class AvatarFrames:
         if self.H % 2 or self.W % 2:
             raise RuntimeError(f"paste_i420: the avatar's frames are {self.H} x {self.W} (H x W); 4:2:0 needs even sizes")
         return frames_to_i420(self.paste(res, indices), order="bgr", out=out)
+
+
+class CustomVideos:
+    """Device-resident copy of a session's custom videos (basereal.py:52-68): cycles {audiotype: uint8 [n, H, W, 3] BGR} is `custom_img_cycle`, uploaded once;
+    custom_index is the dict the deployment's `BaseReal` holds, taken BY REFERENCE -- the scheduler walks it (serving.choose_frames), the deployment resets it
+    (`set_curr_state(audiotype, reinit=True)`, `init_customindex()`).  One dict per session, as one `BaseReal` per session holds one.
+
+    lengths                {audiotype: n}
+    source(audiotype, i)   the device view of frame i of that video, uint8 [H, W, 3]
+    check_size(H, W, who)  refuses a video whose frames are not H x W: the reference would hand the encoder a frame of another size, a ring has fixed slots"""
+
+    def __init__(self, cycles, custom_index, device="cuda"):
+        if not torch.cuda.is_available():
+            raise RuntimeError("CustomVideos needs a HIP device; no CPU path exists here")
+        if not isinstance(custom_index, dict):
+            raise RuntimeError(f"CustomVideos: custom_index must be the dict the deployment holds, got {type(custom_index).__name__}")
+        self.device, self.custom_index, self.cycles = torch.device(device), custom_index, {}
+        for t, cyc in dict(cycles).items():
+            fr = cyc if torch.is_tensor(cyc) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in cyc])))
+            fr = _dev_u8(fr, self.device)
+            if fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+                raise RuntimeError(f"CustomVideos: cycles[{t!r}] must be [n, H, W, 3] with n >= 1, got {tuple(fr.shape)}")
+            self.cycles[t] = fr
+        self.lengths = {t: int(fr.shape[0]) for t, fr in self.cycles.items()}
+
+    def source(self, audiotype, i):
+        fr = self.cycles.get(audiotype)
+        if fr is None or not 0 <= int(i) < fr.shape[0]:
+            raise RuntimeError(f"CustomVideos.source: frame {i} of custom video {audiotype!r} ({'no such video' if fr is None else f'{fr.shape[0]} frames'})")
+        return fr[int(i)]
+
+    def check_size(self, H, W, who="CustomVideos"):
+        for t, fr in self.cycles.items():
+            if (int(fr.shape[1]), int(fr.shape[2])) != (int(H), int(W)):
+                raise RuntimeError(f"{who}: custom video {t!r} holds {fr.shape[1]} x {fr.shape[2]} frames (H x W), the avatar's frames are {H} x {W}; a ring's slots "
+                                   f"have one size")
 
 
 def resize_linear_u8(src, dw, dh):

@@ -26,9 +26,44 @@ def mirror_index(size, index):
     return res if turn % 2 == 0 else size - res - 1
 
 
+def choose_frames(pairs, idx, custom_index, custom_lengths):
+    """What each frame of one batch shows, decided per FRAME as the reference's `process_frames` does (lipreal.py:198-205, musereal.py:229-236).  pairs: the
+    batch's 2B (pcm, type) pairs, two per frame; idx: its B walk indices; custom_index: the dict the deployment's `BaseReal` holds ({audiotype: frames shown so
+    far}), read, NOT modified; custom_lengths: {audiotype: n_frames} of the custom videos.  Returns (choices, increments):
+      choices      one entry per frame -- ("speech", idx_i): the generated frame; ("idle", idx_i): the avatar's cached frame idx_i; ("custom", audiotype, j): frame
+                   j = mirror_index(n, custom_index[audiotype] + the custom frames of that type earlier in this batch) of that video
+      increments   {audiotype: custom frames shown}: what the caller adds to custom_index once the batch is on its way (a batch that is retried moves it once)
+    A frame is non-speech when BOTH of its chunks have type != 0; its audiotype is the FIRST chunk's; a custom video is used when custom_index.get(audiotype) is not
+    None."""
+    B = len(idx)
+    if len(pairs) != 2 * B:
+        refuse("choose_frames", f"{len(pairs)} (pcm, type) pairs for {B} frames (two per frame)")
+    choices, inc = [], {}
+    for i in range(B):
+        t0, t1 = pairs[2 * i][1], pairs[2 * i + 1][1]
+        if t0 != 0 and t1 != 0:                                      # lipreal.py:198
+            if custom_index.get(t0) is not None:                     # :199-203
+                if t0 not in custom_lengths:
+                    refuse("choose_frames", f"custom_index names audio type {t0!r}, but no custom video of that type is attached (types: {sorted(custom_lengths)})")
+                choices.append(("custom", t0, mirror_index(custom_lengths[t0], custom_index[t0] + inc.get(t0, 0))))
+                inc[t0] = inc.get(t0, 0) + 1
+            else:
+                choices.append(("idle", idx[i]))                     # :205
+        else:
+            choices.append(("speech", idx[i]))
+    return choices, inc
+
+
 class SessionWalk:
-    """A session's place in the ping-pong walk over its `length` cached frames (the session sets it), and where those frames start in its batcher's pool."""
-    index, pool_offset = 0, None
+    """A session's place in the ping-pong walk over its `length` cached frames (the session sets it), and where those frames start in its batcher's pool.
+    custom_videos: the session's paste.CustomVideos, or None (attach_custom_videos checks their size against the avatar's frames)."""
+    index, pool_offset, custom_videos = 0, None, None
+
+    def attach_custom_videos(self, custom_videos):
+        av = getattr(self, "avatar_frames", None)
+        if custom_videos is not None and av is not None:
+            custom_videos.check_size(av.H, av.W, type(self).__name__)
+        self.custom_videos = custom_videos
 
     def next_indices(self, n):
         """the next n indices of the walk; the walk moves on (silent batch or spoken one: musereal.py:82-97, lipreal.py:102-105, 112-114)"""
@@ -77,6 +112,13 @@ class PooledBatcher:
         """(H, W) of session k's pasted frames; None where the size is not known before a step (paste=False)"""
         av = self.sessions[k].avatar_frames if self.paste else None
         return None if av is None else (av.H, av.W)
+
+    def idle_source(self, k, i):
+        """the device view of session k's cached full frame i, uint8 [H, W, 3] in `frame_order`: what the session shows while it listens"""
+        av = self.sessions[k].avatar_frames
+        if av is None:
+            raise RuntimeError(f"session {k} has no AvatarFrames: no idle frame to show")
+        return av.source(i)
 
     def _lay_out_pool(self):
         for k, s in enumerate(self.sessions):                            # every session's first row in the pool its frames are concatenated into
@@ -206,15 +248,28 @@ class PipelinedScheduler(SessionScheduler):
     latency = arrival -> descriptors published (rings given) or frames complete in HBM (rings=None).  With rings=None or single_stream=True no stream is created.
     frame_format="i420": each session's uint8 [B, H, W, 3] block is converted to planar YUV 4:2:0 (ops.frames_to_i420, the batcher's `frame_order`) on the step's
     stream right before its begin_batch, so the rings (built with transport.i420_shape) and the D2H carry 1.5 bytes per pixel and the consumer's line is
-    `VideoFrame.from_ndarray(frame, format="yuv420p")`; run_once then reports those frames.  Nothing else changes: silent batches still travel as None."""
+    `VideoFrame.from_ndarray(frame, format="yuv420p")`; run_once then reports those frames.  Nothing else changes: silent batches still travel as None.
+    idle_frames=True (default False: nothing changes): EVERY tuple a ring carries holds a finished frame in the ring's format.  The choice the reference's
+    `process_frames` makes per frame (lipreal.py:198-205, musereal.py:229-236: a frame whose two chunks are both non-speech shows the avatar's cached frame, or
+    a frame of a custom video) is made here (`choose_frames`), and the chosen frames are written by ops.gather_frames on the step's stream: a batch that generated
+    nothing (silent, or a context that is still filling) gets a new block of B frames filled by one gather -- a frame typed speech for which nothing was generated
+    shows the cached frame idx, where the reference drops it -- and in a batch that did, the non-speech frames of the delivered block are overwritten (after the I420
+    conversion).  Needs rings, a batcher with `idle_source(k, i)` that pastes, and AvatarFrames on every session; a session's custom videos are its
+    `custom_videos` (paste.CustomVideos).  THE WALK: the scheduler owns `custom_index`, the deployment only resets it.  It moves once per batch, after every
+    begin_batch of the step has succeeded, so a batch whose step raises and is retried moves it once.  A `set_curr_state(audiotype, reinit=True)` or
+    `init_customindex()` on the deployment's side is seen by the next batch PICKED: up to `depth` batches already in flight keep the old walk."""
 
     FRAME_FORMATS = ("packed", "i420")
 
-    def __init__(self, batcher, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed"):
+    def __init__(self, batcher, rings=None, period_s=None, hold_s=None, clock=time.perf_counter, depth=2, single_stream=False, frame_format="packed",
+                 idle_frames=False):
         self._check_frame_format(batcher, rings, frame_format)       # before anything (streams, the parent's state) is created
+        if idle_frames:
+            self._check_idle_frames(batcher, rings)
         super().__init__(batcher, period_s=period_s, hold_s=hold_s, clock=clock)
         self.rings = rings
         self.frame_format = frame_format
+        self.idle_frames = bool(idle_frames)
         self.depth = max(int(depth), 1)                              # steps in flight: the one computing + the one whose frames are being copied
         # single_stream: a model's audio stage, the step and the D2H of its frames all on the caller's stream -- no cross-stream event wait anywhere (with handles
         # created under MF_NO_GRAPH=2 the whole rank is one launch chain: no runtime thread spins, see mf_musetalk.hip); costs the copy / Whisper overlap
@@ -259,6 +314,59 @@ class PipelinedScheduler(SessionScheduler):
                             f"(FrameRing(slots, transport.i420_shape(H, W)))")
             if not is_i420_shape(have):
                 refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}, which is no [H * 3 / 2, W] plane block (FrameRing(slots, transport.i420_shape(H, W)))")
+
+    @classmethod
+    def _check_idle_frames(cls, batcher, rings):
+        """idle_frames=True: what the gather needs is there before a step runs -- a ring to deliver into, a batcher that hands out its sessions' cached frames
+        and pastes (the frame size of a batch that runs no network must be known), custom videos of the avatar's size"""
+        who, name = cls.__name__, type(batcher).__name__
+        if rings is None:
+            refuse(who, "idle_frames=True fills the tuples the rings carry; without rings a silent batch stays None")
+        if len(rings) != len(batcher.sessions):
+            refuse(who, f"{len(rings)} rings for {len(batcher.sessions)} sessions")
+        if not callable(getattr(batcher, "idle_source", None)):
+            refuse(who, f"idle_frames=True: {name} has no idle_source(k, i) (cached full frames to show while a session listens)")
+        if getattr(batcher, "frame_order", None) not in ("bgr", "rgb"):
+            refuse(who, f"idle_frames=True: {name} does not state its frames' channel order (frame_order = 'bgr' or 'rgb')")
+        if not getattr(batcher, "paste", False):
+            refuse(who, f"idle_frames=True: {name} was built with paste=False; the frames of a batch that runs no network have the pasted frames' size")
+        for k, s in enumerate(batcher.sessions):
+            hw = batcher.frame_hw(k) if callable(getattr(batcher, "frame_hw", None)) else None
+            if hw is None:
+                refuse(who, f"idle_frames=True: session {k} has no AvatarFrames (its frame size is not known before a step)")
+            cv = getattr(s, "custom_videos", None)
+            if cv is not None:
+                cv.check_size(hw[0], hw[1], f"{who}: session {k}")
+
+    def _finish_frames(self, ks, out, audio):
+        """idle_frames: every picked session's block of B finished frames in the ring's format, on the step's stream (one gather per session that has a non-speech
+        or ungenerated frame).  Returns {session: (custom_index, increments)}: the moves of the custom walks, applied by the caller once the step is on its way."""
+        from . import ops
+        bat, moves = self.batcher, {}
+        B, dev = bat.batch_size, bat.device
+        for k in ks:
+            fr, idx = out[k]
+            cv = getattr(bat.sessions[k], "custom_videos", None)
+            ci, lengths = ({}, {}) if cv is None else (cv.custom_index, cv.lengths)
+            choices, inc = choose_frames(audio[k], idx, ci, lengths)
+            srcs, dst = [], []
+            for i, c in enumerate(choices):
+                if c[0] == "custom":
+                    srcs.append(cv.source(c[1], c[2]))
+                elif c[0] == "idle" or fr is None:                   # (typed speech, nothing generated: a context that is still filling shows the cached frame)
+                    srcs.append(bat.idle_source(k, c[1]))
+                else:
+                    continue
+                dst.append(i)
+            if fr is None:
+                H, W = bat.frame_hw(k)
+                fr = torch.empty((B,) + (i420_shape(H, W) if self.frame_format == "i420" else (H, W, 3)), dtype=torch.uint8, device=dev)
+            if srcs:
+                ops.gather_frames(srcs, dst, fr, fmt=self.frame_format, order=bat.frame_order)
+            out[k] = (fr, idx)
+            if inc:
+                moves[k] = (ci, inc)
+        return moves
 
     def _delivered(self, fr):
         """the frames of one session as they enter its ring: as they are, or (frame_format "i420") converted on the step's stream, one launch for the block"""
@@ -315,6 +423,9 @@ class PipelinedScheduler(SessionScheduler):
 
     def submit(self, k, payload, t_arrival=None, pairs=()):
         """(a model's submit takes PCM chunks and ends here.)  A queue entry is (arrival, (payload, pairs)); a third item marks a batch that has advanced"""
+        if self.idle_frames and len(pairs) != 2 * self.batcher.batch_size:
+            refuse(type(self).__name__ + ".submit", f"idle_frames=True chooses every frame from its two (pcm, type) pairs: {len(pairs)} pairs for "
+                                                    f"{self.batcher.batch_size} frames")
         self.queues[k].append((self.clock() if t_arrival is None else t_arrival, (payload, list(pairs))))
 
     def _retire(self, block=False):
@@ -403,7 +514,7 @@ class PipelinedScheduler(SessionScheduler):
         # Everything from here to the last begin_batch sits in ONE try: the rings publish in begin order, so a reservation left open by an exception anywhere
         # on the way (the queue pop, the H2D copy, the audio stage, the step, a begin_batch) would wedge its ring for good -- every later batch queued behind
         # an entry that never completes.  On any exception the reservations go back and the popped batches return to the HEAD of their queues.
-        arrival, audio, wins, tokens, popped, advanced = {}, {}, {}, {}, [], set()
+        arrival, audio, wins, tokens, popped, advanced, moves = {}, {}, {}, {}, [], set(), {}
         try:
             for k in ks:
                 item = self.queues[k].popleft()
@@ -418,6 +529,8 @@ class PipelinedScheduler(SessionScheduler):
                 cur = torch.cuda.current_stream(dev)
                 for k in ks:                                             # (i420: each session's block is converted on the step's stream, before the copy stream waits)
                     out[k] = (self._delivered(out[k][0]), out[k][1])
+                if self.idle_frames:                                     # (every block complete on the step's stream: begin_batch below always gets frames)
+                    moves = self._finish_frames(ks, out, audio)
                 if self.copy_stream is not None:
                     self.copy_stream.wait_stream(cur)
                 for k in ks:
@@ -438,6 +551,10 @@ class PipelinedScheduler(SessionScheduler):
             raise
         if self.rings is None:
             ev.record(torch.cuda.current_stream(dev))
+        for ci, inc in moves.values():                                   # the custom walks move ONCE per batch: only here, behind everything that can raise
+            for ty, n in inc.items():
+                if ci.get(ty) is not None:                               # (a video the deployment has detached since the choice: nothing to move)
+                    ci[ty] += n
         self.inflight.append({"ks": ks, "out": out, "tokens": tokens, "audio": audio, "arrival": arrival, "event": ev, "t0": t0})
         self._start_waiter()
         self._evq.put(ev)
