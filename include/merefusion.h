@@ -190,6 +190,16 @@ int mf_melspec_frames(int n);
  * mf_melspec(row)[:, s : s + 16] for every start s, bit for bit.  Padding happens at each row's own ends.  n_starts <= 256. */
 int mf_melspec_windows(const float* wav, int n, int n_windows, const int* starts, int n_starts,
                        float* chunks, int pad_mode, void* stream);
+/* The sliding windows of the sessions of one step, pushed by one launch (lipasr.py:17-21 + :36; csrc/mf_window_push.hip).
+ * buf: device fp32 [n_rows][n], every session's window; new_samples: device fp32 [m][n_new], the step's new samples;
+ * rows: HOST array of m distinct pool rows, read during the call only (the table travels in the launch arguments, 64 rows
+ * per launch; a longer list goes out as several launches); win: device fp32 [m][n].  For i in [0, m), r = rows[i]:
+ * buf[r] <- concat(buf[r][n_new:], new_samples[i]) and win[i] <- the same n values; rows the table does not name keep
+ * their bytes.  One workgroup per row: the kept context of n - n_new floats goes through LDS, so the overlapping shift
+ * (n_new < n - n_new) is exact.  Refuses null pointers, m < 1, n_rows < 1, an n_new outside [1, n], a row outside
+ * [0, n_rows), a row named twice, a context of more than 160 KB and win / new_samples that overlap buf or each other
+ * (MF_ERR_INVALID, the value named in mf_last_error) before anything is launched. */
+int mf_windows_push(float* buf, int n_rows, int n, const float* new_samples, int n_new, const int* rows, int m, float* win, void* stream);
 
 /* ---- fused multi-head attention (test seam of the kernel both transformer stages run on) ---- */
 /* out = softmax(q k^T / sqrt(head_dim)) v per (batch, head): the `Attention` of the diffusers

@@ -213,6 +213,7 @@ SIGNATURES = {
     "mf_melspec": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "mf_melspec_frames": (C.c_int, [C.c_int]),
     "mf_melspec_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "mf_windows_push": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
     "mf_attention_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "mf_rows_roundtrip": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] + [C.c_int] * 5 + [C.c_void_p] * 2),
     "mf_layernorm_forward": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(MfRowsGeom)] * 2 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 2),

@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .serving import (PipelinedScheduler, PooledBatcher, SessionScheduler, SessionWalk, all_silent, mirror_index, pick_sessions,  # noqa: F401  (re-exported)
-                      split_batch)
+from .serving import (PipelinedScheduler, PooledBatcher, SessionScheduler, SessionWalk, all_silent, live_sessions, mirror_index,  # noqa: F401  (re-exported)
+                      pick_sessions, split_batch)
 from .wav2lip import audio
 
 
@@ -105,15 +105,70 @@ class LipWindowPool:
     """The sliding audio windows of N sessions, resident on the device: buf fp32 [N, (2B + l + r) * chunk], row k = session k's window as lipasr.py:17-23
     concatenates it.  A fresh pool (and a row after `warm_up`) holds silence, which is the state baseasr.py:53-59 leaves: l + r zero chunks of context."""
 
-    def __init__(self, n_sessions, batch_size, fps=50, stride_left=10, stride_right=10, chunk=320, device="cuda"):
+    STAGING_ROWS = 64                                                  # the pinned staging block of a pool built with max_sessions=: one mf_windows_push launch
+
+    def __init__(self, n_sessions, batch_size, fps=50, stride_left=10, stride_right=10, chunk=320, device="cuda", max_sessions=None):
+        """max_sessions (None: a fixed set of n_sessions windows, pushed as ever): buf has max_sessions rows, for sessions that come and go, and `push` takes the
+        route built for a subset of the rows -- the new samples go through one pinned staging block in one asynchronous copy and ONE mf_windows_push launch
+        slides the rows and writes the step's windows: no index tensor, no cat, no scatter."""
         self.batch_size, self.fps, self.l, self.r, self.chunk = int(batch_size), fps, int(stride_left), int(stride_right), int(chunk)
         self.device = torch.device(device)
         self.n_chunks = 2 * self.batch_size + self.l + self.r
         self.n, self.n_new = self.n_chunks * self.chunk, 2 * self.batch_size * self.chunk
-        self.buf = torch.zeros((int(n_sessions), self.n), dtype=torch.float32, device=self.device)
+        if max_sessions is not None and int(max_sessions) < int(n_sessions):
+            raise RuntimeError(f"LipWindowPool: max_sessions={max_sessions} for {n_sessions} sessions")
+        self.buf = torch.zeros((int(n_sessions if max_sessions is None else max_sessions), self.n), dtype=torch.float32, device=self.device)
         self.starts = mel_chunk_starts(self.n_chunks, self.l, self.r, fps, 1 + self.n // 200)       # the same for every row: all windows have n samples
         if len(self.starts) != self.batch_size:
             raise RuntimeError(f"{len(self.starts)} mel windows for {self.batch_size} frames: l + r + 2B chunks must give B windows (lipasr.py:24-35)")
+        self.staging = None
+        if max_sessions is not None:
+            if self.device.type != "cuda":
+                raise RuntimeError("LipWindowPool(max_sessions=) pushes through mf_windows_push and needs a HIP device; no CPU path exists here")
+            # rows of the block are handed out round robin; a push waits only for the copy that last read the rows it is about to refill (`_staged`), which
+            # lies a whole turn of the block back
+            self.staging = torch.empty((self.STAGING_ROWS, self.n_new), dtype=torch.float32).pin_memory()
+            self._stage_at, self._staged = 0, []                      # next free staging row; [(first, end, event)] of the copies that may still be reading
+
+    def reset_row(self, k):
+        """row k holds silence again, the state warm_up leaves (baseasr.py:53-59): what a joiner's window starts from.  Stream-ordered."""
+        self.buf[int(k)].zero_()
+
+    def _stage(self, blocks):
+        """blocks (at most STAGING_ROWS host_blocks) -> their device copy [len(blocks), n_new], through the pinned block, one asynchronous copy"""
+        m = len(blocks)
+        if self._stage_at + m > self.STAGING_ROWS:
+            self._stage_at = 0
+        a, b = self._stage_at, self._stage_at + m
+        keep = []
+        for first, end, ev in self._staged:
+            if first < b and a < end:
+                ev.synchronize()                                      # (a copy issued a turn of the block ago: done long since)
+            else:
+                keep.append((first, end, ev))
+        host = self.staging[a:b]
+        np.stack(blocks, out=host.numpy())
+        new = host.to(self.device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._staged, self._stage_at = keep + [(a, b, ev)], b
+        return new
+
+    def push_rows(self, ks, blocks):
+        """`push` for a pool built with max_sessions=: returns the pushed windows [len(ks), n] in the order of ks, which `mel` takes as they are"""
+        ks = [int(k) for k in ks]
+        if len(set(ks)) != len(ks):
+            raise RuntimeError(f"push: a session appears twice in {ks}")
+        if not ks or len(blocks) != len(ks):
+            raise RuntimeError(f"push: {len(blocks)} blocks for {len(ks)} sessions (at least one, and one block per session)")
+        bad = [k for k in ks if not 0 <= k < self.buf.shape[0]]
+        if bad:
+            raise RuntimeError(f"push: sessions {bad} are out of range: the pool has rows 0 to {self.buf.shape[0] - 1}")
+        win = torch.empty((len(ks), self.n), dtype=torch.float32, device=self.device)
+        for i in range(0, len(ks), self.STAGING_ROWS):
+            part = slice(i, i + self.STAGING_ROWS)
+            ops.windows_push(self.buf, ks[part], self._stage(blocks[part]), out=win[part])
+        return win
 
     def host_block(self, new_chunks):
         """the 2B new 20 ms chunks of one session as one fp32 [2B * chunk] array; refuses anything else (before any window moves)"""
@@ -135,12 +190,14 @@ class LipWindowPool:
 
     def push(self, ks, blocks):
         """lipasr.py:17-21 + :36 for sessions ks at once: blocks[i] (host_block) is appended to session ks[i]'s window and the oldest 2B chunks fall out.
-        One upload of the new samples; the l + r context moves on the device."""
+        One upload of the new samples; the l + r context moves on the device.  (A pool built with max_sessions=: push_rows, which also returns the windows.)"""
+        if self.staging is not None:
+            return self.push_rows(ks, blocks)
         ks = list(ks)
         if len(set(ks)) != len(ks):
             raise RuntimeError(f"push: a session appears twice in {ks}")
         # (the block is pageable host memory, so this copy is in effect synchronous; a subset of sessions also uploads a small index tensor below.  Both are
-        # inside the step times of DESIGN.md section 4: pinned staging buffers and a device-side row table are what is left to take out of them)
+        # inside the step times of DESIGN.md section 4: a pool built with max_sessions= takes them out -- a pinned staging block, the row table in mf_windows_push's launch arguments: push_rows)
         new = torch.from_numpy(np.stack(blocks)).to(self.device, non_blocking=True)
         win = torch.cat([self.rows(ks)[:, self.n_new:], new], dim=1)
         if ks == list(range(self.buf.shape[0])):
@@ -179,7 +236,10 @@ class LipBatcher(PooledBatcher):
     """N Wav2Lip sessions through one generator handle per step (BASELINE.json configs[3]: per-GPU batching).  The argument list is MuseBatcher's, with the
     generator in the place of the UNet / VAE pair."""
 
-    def __init__(self, model, sessions, batch_size=16, paste=False, device="cuda", max_sessions_per_step=None):
+    def __init__(self, model, sessions, batch_size=16, paste=False, device="cuda", max_sessions_per_step=None, max_sessions=None, pool_rows=None):
+        """max_sessions, pool_rows (both None: a fixed session list, as ever): sessions may join and leave (add_session / remove_session, serving.PooledBatcher).
+        `sessions` is then a list of max_sessions slots (None: vacant) and the pool ONE allocation of pool_rows rows (default: the initial sessions' rows) whose
+        address never changes; a step still holds at most max_sessions_per_step sessions (default here: the initial number)."""
         self.model, self.sessions, self.batch_size, self.paste = model, list(sessions), int(batch_size), bool(paste)
         self.device = torch.device(device)
         if not self.sessions:
@@ -187,22 +247,31 @@ class LipBatcher(PooledBatcher):
         # more sessions than one step holds: step(..., only=[...]) serves a subset (LipSessionScheduler)
         self.max_sessions_per_step = len(self.sessions) if max_sessions_per_step is None else int(max_sessions_per_step)
         for k, s in enumerate(self.sessions):
-            if s.faces.dtype != torch.uint8 or s.faces.dim() != 4 or tuple(s.faces.shape[1:]) != (96, 96, 3):
-                raise RuntimeError(f"session {k}: the cached crops must be uint8 [n,96,96,3], got {s.faces.dtype} {tuple(s.faces.shape)}")
-            if s.avatar_frames is not None and s.avatar_frames.n != s.length:
-                raise RuntimeError(f"session {k}: one cached full frame per cached crop is required (frame_list_cycle / face_list_cycle)")
-        self._lay_out_pool()
+            self._check_session(k, s)
         # every session's cached crops in one pool: the generator's input kernel reads a batch's faces from it by row
-        self.pool = torch.cat([s.faces.to(self.device) for s in self.sessions], dim=0).contiguous()
+        self.pool = self._build_pool(max_sessions, pool_rows)
         self.window_pool = None
 
+    @staticmethod
+    def _check_session(k, s):
+        if s.faces.dtype != torch.uint8 or s.faces.dim() != 4 or tuple(s.faces.shape[1:]) != (96, 96, 3):
+            raise RuntimeError(f"session {k}: the cached crops must be uint8 [n,96,96,3], got {s.faces.dtype} {tuple(s.faces.shape)}")
+        if s.avatar_frames is not None and s.avatar_frames.n != s.length:
+            raise RuntimeError(f"session {k}: one cached full frame per cached crop is required (frame_list_cycle / face_list_cycle)")
+
+    @staticmethod
+    def _session_rows(s):
+        return s.faces
+
     def frontends(self, fps=50, stride_left=10, stride_right=10):
-        """One LipASRDeviceFrontend per session over a window pool this batcher owns (created here, once)."""
+        """One LipASRDeviceFrontend per session over a window pool this batcher owns (created here, once).  Sessions that come and go: the pool has a window for
+        every slot and pushes through mf_windows_push (LipWindowPool(max_sessions=)); a vacant slot's entry is None."""
         if self.window_pool is None:
-            self.window_pool = LipWindowPool(len(self.sessions), self.batch_size, fps, stride_left, stride_right, device=self.device)
+            self.window_pool = LipWindowPool(len(self.live()), self.batch_size, fps, stride_left, stride_right, device=self.device,
+                                             max_sessions=None if self.row_pool is None else len(self.sessions))
         elif (self.window_pool.fps, self.window_pool.l, self.window_pool.r) != (fps, stride_left, stride_right):
             raise RuntimeError("this batcher's window pool was built with another fps / stride")
-        return [LipASRDeviceFrontend(self.window_pool, k) for k in range(len(self.sessions))]
+        return [None if s is None else LipASRDeviceFrontend(self.window_pool, k) for k, s in enumerate(self.sessions)]
 
     @torch.no_grad()
     def prewarm(self, tune=False):
@@ -252,31 +321,72 @@ class LipEndToEndScheduler(PipelinedScheduler):
         fes = batcher.frontends() if frontends is None else list(frontends)
         if len(fes) != len(batcher.sessions):                             # before anything (streams, the parent's state) is created
             raise RuntimeError("one LipASRDeviceFrontend per session is required")
+        live = live_sessions(batcher)
+        pool = fes[live[0]].pool if isinstance(fes[live[0]], LipASRDeviceFrontend) else None
         for k, fe in enumerate(fes):
-            if not isinstance(fe, LipASRDeviceFrontend) or fe.pool is not fes[0].pool or fe.row != k or fe.batch_size != batcher.batch_size:
+            if k not in live and fe is None:                              # (a vacant slot of a batcher whose sessions come and go)
+                continue
+            if not isinstance(fe, LipASRDeviceFrontend) or fe.pool is not pool or fe.row != k or fe.batch_size != batcher.batch_size:
                 raise RuntimeError(f"frontend {k}: one LipASRDeviceFrontend per session, row k of one pool, is required (LipBatcher.frontends())")
+        if getattr(batcher, "row_pool", None) is not None and (pool.staging is None or pool.buf.shape[0] < len(batcher.sessions)):
+            raise RuntimeError(f"LipEndToEndScheduler: a batcher whose sessions come and go needs a window for every slot: LipWindowPool(..., "
+                               f"max_sessions={len(batcher.sessions)}) (LipBatcher.frontends())")
         if frame_format == "i420" and not batcher.paste:
             raise RuntimeError("LipEndToEndScheduler: frame_format='i420' converts the pasted uint8 frames; the batcher was built with paste=False (fp32 crops)")
         super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format,
                          idle_frames=idle_frames)
-        self.frontends, self.windows = fes, fes[0].pool
+        self.frontends, self.windows = fes, pool
 
     def submit(self, k, pcm_chunks, t_arrival=None):
         """pcm_chunks: the batch's 2B 20 ms chunks (serving.split_batch).  An all-silent batch skips the network (lipreal.py:96-105): its B (None, idx,
         audio_frames) tuples still reach the ring, and its samples still enter the window (lipasr.py:17-21 does not look at the type)."""
+        self._check_slot(k, "submit")
         chunks, pairs, types = split_batch(pcm_chunks, "LipEndToEndScheduler.submit")
         block = self.windows.host_block(chunks)                          # refuses a malformed batch here, before it is queued
         super().submit(k, {"block": block, "silent": all_silent(types)}, t_arrival, pairs)
 
     def _advance(self, ks, batches):
-        self.windows.push(ks, [batches[k]["block"] for k in ks])         # lipasr.py:17-21 + :36: the picked sessions' windows slide, one upload
+        if self.windows.staging is None:
+            self.windows.push(ks, [batches[k]["block"] for k in ks])     # lipasr.py:17-21 + :36: the picked sessions' windows slide, one upload
+            return
+        # sessions that come and go: one mf_windows_push launch slides the rows and writes the step's windows, the speaking sessions' first -- they are what the
+        # mel launch of _inputs takes, as they lie.  A batch keeps its window (a view) for a retry.
+        order = [k for k in ks if not batches[k]["silent"]] + [k for k in ks if batches[k]["silent"]]
+        win = self.windows.push(order, [batches[k]["block"] for k in order])
+        for i, k in enumerate(order):
+            batches[k]["win"] = (win, i)
+
+    def _step_windows(self, speaking, batches):
+        """the windows of the speaking sessions as one [len(speaking), n] tensor"""
+        if self.windows.staging is None:
+            return self.windows.rows(speaking)
+        wins = [batches[k]["win"] for k in speaking]
+        if all(w is wins[0][0] and i == j for j, (w, i) in enumerate(wins)):
+            return wins[0][0][:len(speaking)]                            # one push, speaking sessions first: no copy
+        return torch.stack([w[i] for w, i in wins])                      # (a retried step whose sessions were pushed by different launches)
+
+    def _check_join(self, k, session, ring, frontend):
+        if frontend is not None:
+            raise RuntimeError("LipEndToEndScheduler: add_session makes the joiner's LipASRDeviceFrontend itself (row k of the scheduler's window pool): frontend=None")
+        if self.windows.staging is None or k >= self.windows.buf.shape[0]:
+            raise RuntimeError(f"LipEndToEndScheduler: add_session needs a window pool with a row for slot {k} (LipWindowPool(..., max_sessions=))")
+        super()._check_join(k, session, ring, frontend)
+
+    def _store(self, k, session, ring, frontend):
+        super()._store(k, session, ring, frontend)
+        self.windows.reset_row(k)                                        # silence, as warm_up leaves it (baseasr.py:53-59)
+        self.frontends[k] = LipASRDeviceFrontend(self.windows, k)
+
+    def _drop(self, k):
+        super()._drop(k)
+        self.frontends[k] = None
 
     def _inputs(self, ks, batches, dev):
         chunks = [None] * len(self.queues)
         speaking = sorted(k for k in ks if not batches[k]["silent"])
         if speaking:
             B = self.batcher.batch_size
-            mel = self.windows.mel(self.windows.rows(speaking))          # every speaking session's B chunks in one launch
+            mel = self.windows.mel(self._step_windows(speaking, batches))  # every speaking session's B chunks in one launch
             for i, k in enumerate(speaking):
                 chunks[k] = mel[i * B:(i + 1) * B]
         return chunks

@@ -98,7 +98,10 @@ class MuseSession(SessionWalk):
 class MuseBatcher(PooledBatcher):
     """N sessions through one UNet / VAE handle per step (BASELINE.json north star: 8 sessions per GPU)."""
 
-    def __init__(self, unet, vae, sessions, batch_size=8, paste=False, device="cuda", max_sessions_per_step=None):
+    def __init__(self, unet, vae, sessions, batch_size=8, paste=False, device="cuda", max_sessions_per_step=None, max_sessions=None, pool_rows=None):
+        """max_sessions, pool_rows (both None: a fixed session list, as ever): sessions may join and leave (add_session / remove_session, serving.PooledBatcher).
+        `sessions` is then a list of max_sessions slots (None: vacant) and the pool ONE allocation of pool_rows rows (default: the initial sessions' rows) whose
+        address never changes; a step still holds at most max_sessions_per_step sessions (default here: the initial number)."""
         if not torch.cuda.is_available():
             raise RuntimeError("MuseBatcher needs a HIP device; no CPU path exists here")
         self.unet, self.vae, self.sessions, self.batch_size, self.paste = unet, vae, list(sessions), batch_size, paste
@@ -109,12 +112,24 @@ class MuseBatcher(PooledBatcher):
         for h, what in ((unet.model.max_batch, "UNet"), (getattr(vae, "max_batch", need), "VAE")):
             if h < need:
                 raise RuntimeError(f"{what} handle was created with max_batch {h}; {self.max_sessions_per_step} sessions x {batch_size} frames need {need}")
-        self._lay_out_pool()
-        # every session's cached latents in one pool: a batch is one gather
-        self.pool = torch.cat([s.latents.reshape(s.length, -1) for s in self.sessions], dim=0).to(self.device).contiguous()
-        self.row_elems = self.pool.shape[1]
         self.lat_shape = tuple(self.sessions[0].latents.shape[1:])
+        if max_sessions is not None or pool_rows is not None:
+            for k, s in enumerate(self.sessions):
+                self._check_session(k, s)
+        # every session's cached latents in one pool: a batch is one gather
+        self.pool = self._build_pool(max_sessions, pool_rows)
+        self.row_elems = self.pool.shape[1]
         self.t0 = torch.tensor([0], device=self.device)
+
+    def _check_session(self, k, s):
+        if tuple(s.latents.shape[1:]) != self.lat_shape:
+            raise RuntimeError(f"session {k}: cached latents of shape {tuple(s.latents.shape[1:])}; this batcher's pool holds {self.lat_shape}")
+        if s.avatar_frames is not None and s.avatar_frames.n != s.length:
+            raise RuntimeError(f"session {k}: one cached full frame per cached latent is required (frame_list_cycle / input_latent_list_cycle)")
+
+    @staticmethod
+    def _session_rows(s):
+        return s.latents.reshape(s.length, -1)
 
     @torch.no_grad()
     def prewarm(self, tune=False):
@@ -172,9 +187,23 @@ class EndToEndScheduler(PipelinedScheduler):
     def submit(self, k, pcm_chunks, t_arrival=None):
         """pcm_chunks: the batch's 2B 20 ms chunks -- bare arrays or (chunk, type) pairs (serving.split_batch).  An all-silent batch skips the networks, as
         musereal.py:82-86 does: its B (None, idx, audio_frames) tuples still reach the session's ring so that `process_frames` keeps audio and idle video in step."""
+        self._check_slot(k, "submit")
         chunks, pairs, types = split_batch(pcm_chunks, "EndToEndScheduler.submit")
         win = self.frontends[k].window(chunks)                        # host side of museasr.py:17-29, at arrival time (the window slides for silent batches too)
         super().submit(k, None if all_silent(types) else win, t_arrival, pairs)
+
+    def _check_join(self, k, session, ring, frontend):
+        if not isinstance(frontend, MuseASRFrontend):
+            raise RuntimeError("EndToEndScheduler: add_session takes the joiner's MuseASRFrontend (frontend=), as the constructor takes one per session")
+        super()._check_join(k, session, ring, frontend)
+
+    def _store(self, k, session, ring, frontend):
+        super()._store(k, session, ring, frontend)
+        self.frontends[k] = frontend
+
+    def _drop(self, k):
+        super()._drop(k)
+        self.frontends[k] = None
 
     def _inputs(self, ks, wins, dev):
         """The Whisper stage of one step: wins[k] is the window submit() queued for session k (None: a silent batch, or a context that is still filling)."""

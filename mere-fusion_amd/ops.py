@@ -136,6 +136,41 @@ def melspec_windows(wav, starts, pad_mode, out=None):
     return out
 
 
+def windows_push(buf, rows, new, out=None):
+    """The sliding windows of one step's sessions, pushed by one launch (mf_windows_push, csrc/mf_window_push.hip): buf contiguous fp32 [N, n] on the device (every
+    session's window), rows a host list of m distinct rows of it, new contiguous fp32 [m, n_new] on the device (n_new <= n) -> for every i
+    buf[rows[i]] = concat(buf[rows[i]][n_new:], new[i]), and out fp32 [m, n] (created when None) holds the same m windows.  Rows that `rows` does not name keep
+    their bytes.  The row list travels in the launch arguments: no index tensor.  Refuses before anything is enqueued."""
+    for name, t in (("buf", buf), ("new", new)):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f"windows_push: {name} must be a contiguous fp32 device tensor, got {type(t).__name__}")
+    _require_cuda("windows_push", buf, new)
+    rows = [int(r) for r in rows]
+    m = len(rows)
+    if m == 0:
+        raise RuntimeError("windows_push: no rows (at least one window moves in a push)")
+    if buf.dtype != torch.float32 or buf.dim() != 2 or not buf.is_contiguous():
+        raise RuntimeError(f"windows_push: buf must be contiguous fp32 [N, n], got {buf.dtype} {tuple(buf.shape)}{'' if buf.is_contiguous() else ' (not contiguous)'}")
+    N, n = int(buf.shape[0]), int(buf.shape[1])
+    if new.dtype != torch.float32 or new.dim() != 2 or not new.is_contiguous() or new.shape[0] != m or not 1 <= new.shape[1] <= n or new.device != buf.device:
+        raise RuntimeError(f"windows_push: new must be contiguous fp32 [{m}, n_new] with 1 <= n_new <= {n} on {buf.device}, got {new.dtype} {tuple(new.shape)} on "
+                           f"{new.device}{'' if new.is_contiguous() else ' (not contiguous)'}")
+    bad = [r for r in rows if not 0 <= r < N]
+    if bad:
+        raise RuntimeError(f"windows_push: rows {bad} are out of range: the pool has rows 0 to {N - 1}")
+    if len(set(rows)) != m:
+        raise RuntimeError(f"windows_push: a row appears twice in {rows}")
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=buf.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_cuda and out.device == buf.device and out.is_contiguous() and tuple(out.shape) == (m, n)):
+        what = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise RuntimeError(f"windows_push: out must be a contiguous fp32 tensor {(m, n)} on {buf.device}, got {what}")
+    with torch.cuda.device(buf.device):
+        _lib.check(_lib.lib().mf_windows_push(buf.data_ptr(), N, n, new.data_ptr(), int(new.shape[1]), (C.c_int * m)(*rows), m, out.data_ptr(),
+                                              _stream_ptr(buf.device)), "windows_push")
+    return out
+
+
 FRAME_ORDERS = {"bgr": 0, "rgb": 1}
 
 

@@ -85,17 +85,74 @@ def all_silent(types):
     return all(ty != 0 for ty in types)                              # musereal.py:82-86, lipreal.py:96-105: no type-0 chunk, the networks are skipped
 
 
+class RowPool:
+    """First-fit allocator of contiguous row ranges in a pool of `capacity` rows: where a session's cached frames live in a batcher's pool while sessions come and
+    go.  alloc(n) takes the LOWEST gap that holds n rows; free(offset) returns a range and joins it to the gaps beside it.  Nothing is ever moved: a joiner that
+    fits nowhere is refused, and the caller sizes the pool (`pool_rows`).  Deterministic, no torch."""
+
+    def __init__(self, capacity):
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            refuse("RowPool", f"capacity {capacity} (at least one row)")
+        self.gaps, self.taken = [(0, self.capacity)], {}             # gaps: (offset, length), sorted, never adjacent; taken: {offset: length}
+
+    def alloc(self, n):
+        n = int(n)
+        if n < 1:
+            refuse("RowPool", f"alloc({n}): at least one row")
+        for i, (off, length) in enumerate(self.gaps):
+            if length >= n:
+                self.gaps[i:i + 1] = [(off + n, length - n)] if length > n else []
+                self.taken[off] = n
+                return off
+        refuse("RowPool", f"no gap of {n} rows: the largest free gap has {self.largest_gap()} of {self.capacity} rows ({self.used()} in use)")
+
+    def free(self, offset):
+        if offset not in self.taken:
+            refuse("RowPool", f"free({offset}): no range starts there (ranges start at {sorted(self.taken)})")
+        n = self.taken.pop(offset)
+        gaps = sorted(self.gaps + [(offset, n)])
+        self.gaps = gaps[:1]
+        for off, length in gaps[1:]:
+            last_off, last_len = self.gaps[-1]
+            if last_off + last_len == off:
+                self.gaps[-1] = (last_off, last_len + length)
+            else:
+                self.gaps.append((off, length))
+
+    def used(self):
+        return sum(self.taken.values())
+
+    def largest_gap(self):
+        return max((length for _, length in self.gaps), default=0)
+
+
+def live_sessions(batcher):
+    """the occupied session slots of a batcher (one without `live()` has none vacant)"""
+    live = getattr(batcher, "live", None)
+    return list(live()) if callable(live) else list(range(len(batcher.sessions)))
+
+
 def step_sessions(batcher, inputs, only, skip_none=True):
     """The `only=` handling of a batcher step.  inputs: one entry per session; only: session numbers that take part (None: all).  Returns (picked, active):
     the sessions whose state moves in this step, and those of them that reach the networks (skip_none: a None input is a silent batch and does not).  Refuses a
-    list of another length, a session number out of range and more active sessions than a step holds -- all before anything moves."""
+    list of another length, a session number out of range and more active sessions than a step holds -- all before anything moves.  A vacant slot of a batcher
+    whose sessions come and go is absent: never picked, refused in `only`, and its input must be None."""
     who, n_sessions, capacity = type(batcher).__name__, len(batcher.sessions), batcher.max_sessions_per_step
     if len(inputs) != n_sessions:
         refuse(who, f"{len(inputs)} entries for {n_sessions} sessions")
     take = None if only is None else set(int(k) for k in only)
     if take is not None and (min(take, default=0) < 0 or max(take, default=0) >= n_sessions):
         refuse(who, f"only={sorted(take)}: session numbers run from 0 to {n_sessions - 1}")
-    picked = [k for k in range(n_sessions) if take is None or k in take]
+    live = set(live_sessions(batcher))
+    if len(live) != n_sessions:
+        vacant = [k for k in range(n_sessions) if k not in live]
+        if take is not None and take - live:
+            refuse(who, f"only={sorted(take)}: slots {sorted(take - live)} are vacant (live sessions: {sorted(live)})")
+        full = [k for k in vacant if inputs[k] is not None]
+        if full:
+            refuse(who, f"slots {full} are vacant: their entries must be None (live sessions: {sorted(live)})")
+    picked = [k for k in range(n_sessions) if k in live and (take is None or k in take)]
     active = [k for k in picked if inputs[k] is not None] if skip_none else picked
     if len(active) > capacity:
         refuse(who, f"{len(active)} active sessions in one step; a step holds {capacity} x {batcher.batch_size} frames")
@@ -108,10 +165,81 @@ class PooledBatcher:
 
     frame_order = "bgr"                                                  # channel 0 of the uint8 frames a step returns (Wav2Lip and MuseTalk: cv2's order)
 
-    def frame_hw(self, k):
-        """(H, W) of session k's pasted frames; None where the size is not known before a step (paste=False)"""
-        av = self.sessions[k].avatar_frames if self.paste else None
+    row_pool = None                                                      # the RowPool of a batcher whose sessions come and go (max_sessions= / pool_rows=)
+
+    def session_hw(self, session):
+        """(H, W) of a session's pasted frames; None where the size is not known before a step (paste=False)"""
+        av = session.avatar_frames if self.paste else None
         return None if av is None else (av.H, av.W)
+
+    def frame_hw(self, k):
+        """session_hw of session k"""
+        return self.session_hw(self.sessions[k])
+
+    def live(self):
+        """the occupied slot numbers"""
+        return [k for k, s in enumerate(self.sessions) if s is not None]
+
+    def _build_pool(self, max_sessions, pool_rows):
+        """The pool of the constructor's sessions (each already through `_check_session`).  max_sessions and pool_rows both None: the sessions' rows (`_session_rows`)
+        concatenated, as many rows as they have.  Otherwise ONE allocation of pool_rows rows (default: what the initial sessions need) that lives as long as the
+        batcher -- captured graphs and prewarmed handles may hold its address -- with the sessions laid out by a RowPool (first fit from an empty pool: the
+        offsets of the concatenation), and `sessions` becomes a list of max_sessions slots, None where vacant."""
+        if max_sessions is None and pool_rows is None:
+            self._lay_out_pool()
+            return torch.cat([self._session_rows(s).to(self.device) for s in self.sessions], dim=0).contiguous()
+        who, need = type(self).__name__, sum(s.length for s in self.sessions)
+        max_sessions = len(self.sessions) if max_sessions is None else int(max_sessions)
+        pool_rows = need if pool_rows is None else int(pool_rows)
+        if max_sessions < len(self.sessions):
+            refuse(who, f"max_sessions={max_sessions} for {len(self.sessions)} initial sessions")
+        if pool_rows < need:
+            refuse(who, f"pool_rows={pool_rows}: the {len(self.sessions)} initial sessions have {need} rows")
+        self.row_pool = RowPool(pool_rows)
+        first = self._session_rows(self.sessions[0])
+        pool = torch.zeros((pool_rows,) + tuple(first.shape[1:]), dtype=first.dtype, device=self.device)
+        for s in self.sessions:
+            s.pool_offset = self.row_pool.alloc(s.length)
+            pool[s.pool_offset:s.pool_offset + s.length].copy_(self._session_rows(s))
+        self.sessions = self.sessions + [None] * (max_sessions - len(self.sessions))
+        return pool
+
+    def vacant_slot(self):
+        """the slot the next add_session takes: the lowest vacant one.  Refuses a batcher built for a fixed session list, and a full one."""
+        who = type(self).__name__
+        if self.row_pool is None:
+            refuse(who, f"add_session: this batcher was built for a fixed list of sessions; {who}(..., max_sessions=, pool_rows=) makes room for joiners")
+        for k, s in enumerate(self.sessions):
+            if s is None:
+                return k
+        refuse(who, f"add_session: all {len(self.sessions)} session slots are taken (max_sessions)")
+
+    def add_session(self, session):
+        """A session joins: the lowest vacant slot, `session.length` rows of the pool (RowPool: the lowest gap that fits), its rows copied there on the current
+        stream -- stream-ordered, so a step enqueued after this call reads them and nothing waits.  The same checks as the constructor's, for this one session;
+        refused before anything changes.  No forward, no tune, no capture: the handles are sized by max_sessions_per_step, not by who is here.  Returns the slot."""
+        k = self.vacant_slot()
+        self._check_session(k, session)
+        rows = self._session_rows(session)
+        off = self.row_pool.alloc(session.length)                         # (refuses with the largest free gap; nothing has changed yet)
+        self.pool[off:off + session.length].copy_(rows, non_blocking=True)
+        session.pool_offset = off
+        self.sessions[k] = session
+        return k
+
+    def remove_session(self, k):
+        """Session k leaves: its rows and its slot are free for a joiner.  The caller knows that no step still reads them (a scheduler waits for the session's
+        last batch in flight).  Returns the session object."""
+        who = type(self).__name__
+        if self.row_pool is None:
+            refuse(who, f"remove_session: this batcher was built for a fixed list of sessions; {who}(..., max_sessions=, pool_rows=) lets sessions come and go")
+        k = int(k)
+        if not 0 <= k < len(self.sessions) or self.sessions[k] is None:
+            refuse(who, f"remove_session({k}): no session there (live sessions: {self.live()})")
+        s = self.sessions[k]
+        self.row_pool.free(s.pool_offset)
+        self.sessions[k], s.pool_offset = None, None
+        return s
 
     def idle_source(self, k, i):
         """the device view of session k's cached full frame i, uint8 [H, W, 3] in `frame_order`: what the session shows while it listens"""
@@ -200,19 +328,84 @@ class SessionScheduler:
         self.hold = self.period / 4 if hold_s is None else float(hold_s)
         self.clock = clock
         self.sync = sync if sync is not None else (lambda: torch.cuda.synchronize(batcher.device))
-        self.queues = [deque() for _ in batcher.sessions]
+        live = set(live_sessions(batcher))
+        self.queues = [deque() if k in live else None for k in range(len(batcher.sessions))]       # (None: a vacant slot of a batcher whose sessions come and go)
+        self.leaving = set()                                         # slots whose session has been removed and still has a batch in flight
         self.steps = 0
         self.sessions_served = 0
         self.busy_s = 0.0
 
+    # ---- sessions that come and go (a batcher built with max_sessions= / pool_rows=) -------------------------------------------------------------------
+    def _check_slot(self, k, what):
+        """refuses `what` on a slot that is vacant or whose session is leaving"""
+        if not 0 <= k < len(self.queues) or self.queues[k] is None:
+            refuse(type(self).__name__, f"{what}({k!r}): no session there (live sessions: {[j for j, q in enumerate(self.queues) if q is not None]})")
+        if k in self.leaving:
+            refuse(type(self).__name__, f"{what}({k}): the session is leaving (remove_session was called; its last batches in flight are being delivered)")
+
+    def add_session(self, session, ring=None, frontend=None):
+        """A client connects: the session joins the batcher (PooledBatcher.add_session: the lowest vacant slot, its rows copied into the pool on the current
+        stream; no forward, no capture) and gets a queue; ring / frontend are what the constructor takes per session.  Everything the constructor checks for a
+        session and its ring is checked for this one, before anything is stored.  Returns the slot number k the caller submits to."""
+        k = self.batcher.vacant_slot()
+        self._check_join(k, session, ring, frontend)
+        got = self.batcher.add_session(session)
+        if got != k:
+            refuse(type(self).__name__, f"add_session: the batcher put the session into slot {got}, not {k}")
+        self._store(k, session, ring, frontend)
+        self.queues[k] = deque()
+        return k
+
+    def flush(self, k):
+        """The `pause_talk` of the batched path (lipreal.py:187-189, baseasr.py:30-31): drops session k's queued batches that have not been picked and returns how
+        many.  Batches in flight are delivered; the frame walk and `custom_index` have not moved for a dropped batch and do not move."""
+        self._check_slot(k, "flush")
+        return self._flush(k)
+
+    def _flush(self, k):
+        n = len(self.queues[k])
+        self.queues[k].clear()
+        return n
+
+    def remove_session(self, k):
+        """A client goes: its queued batches are dropped (flush) and the slot is LEAVING -- nothing can be submitted to it, and it is not offered to add_session --
+        until the session's last batch in flight has retired.  Only then are its pool rows, its slot and what the scheduler holds for it released: with steps in
+        flight one of them may still read those rows, and a joiner's rows must not be copied over them."""
+        self._check_slot(k, "remove_session")
+        self._flush(k)
+        self.leaving.add(k)
+        self._release_left()
+
+    def _release_left(self):
+        for k in sorted(self.leaving):
+            if not self._in_flight(k):
+                self.leaving.discard(k)
+                self.queues[k] = None
+                self._drop(k)
+                self.batcher.remove_session(k)
+
+    def _in_flight(self, k):
+        return False                                                 # (run_once waits for its step)
+
+    def _check_join(self, k, session, ring, frontend):
+        if ring is not None or frontend is not None:
+            refuse(type(self).__name__, "add_session: this scheduler delivers no frames through rings and runs no audio stage (ring=None, frontend=None)")
+
+    def _store(self, k, session, ring, frontend):
+        pass
+
+    def _drop(self, k):
+        pass
+
     def submit(self, k, inputs, t_arrival=None):
+        self._check_slot(k, "submit")
         self.queues[k].append((self.clock() if t_arrival is None else t_arrival, inputs))
 
     def pending(self):
         return {k: q[0][0] for k, q in enumerate(self.queues) if q}
 
     def backlog(self):
-        return max((len(q) for q in self.queues), default=0)
+        return max((len(q) for q in self.queues if q is not None), default=0)
 
     def next_due(self):
         p = self.pending()
@@ -267,7 +460,7 @@ class PipelinedScheduler(SessionScheduler):
         if idle_frames:
             self._check_idle_frames(batcher, rings)
         super().__init__(batcher, period_s=period_s, hold_s=hold_s, clock=clock)
-        self.rings = rings
+        self.rings = None if rings is None else list(rings)         # (a list of its own: add_session / remove_session change entries)
         self.frame_format = frame_format
         self.idle_frames = bool(idle_frames)
         self.depth = max(int(depth), 1)                              # steps in flight: the one computing + the one whose frames are being copied
@@ -304,16 +497,22 @@ class PipelinedScheduler(SessionScheduler):
         if len(rings) != len(batcher.sessions):
             refuse(who, f"{len(rings)} rings for {len(batcher.sessions)} sessions")
         frame_hw = getattr(batcher, "frame_hw", None)
-        for k, ring in enumerate(rings):
-            have = tuple(getattr(ring, "frame_shape", ()))
-            hw = frame_hw(k) if frame_hw is not None else None
-            if hw is not None and (hw[0] % 2 or hw[1] % 2):
-                refuse(who, f"frame_format='i420': session {k}'s frames are {hw[0]} x {hw[1]} (H x W); 4:2:0 needs even sizes")
-            if hw is not None and have != i420_shape(*hw):
-                refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}; session {k}'s {hw[0]} x {hw[1]} frames need {i420_shape(*hw)} "
-                            f"(FrameRing(slots, transport.i420_shape(H, W)))")
-            if not is_i420_shape(have):
-                refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}, which is no [H * 3 / 2, W] plane block (FrameRing(slots, transport.i420_shape(H, W)))")
+        for k in live_sessions(batcher):
+            cls._check_session_format(k, rings[k], frame_hw(k) if frame_hw is not None else None)
+
+    @classmethod
+    def _check_session_format(cls, k, ring, hw):
+        """frame_format "i420", one session: ring k carries the planes of session k's frames (hw: their size where it is known before a step).  The constructor
+        runs it for every session, add_session for the joiner."""
+        who = cls.__name__
+        have = tuple(getattr(ring, "frame_shape", ()))
+        if hw is not None and (hw[0] % 2 or hw[1] % 2):
+            refuse(who, f"frame_format='i420': session {k}'s frames are {hw[0]} x {hw[1]} (H x W); 4:2:0 needs even sizes")
+        if hw is not None and have != i420_shape(*hw):
+            refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}; session {k}'s {hw[0]} x {hw[1]} frames need {i420_shape(*hw)} "
+                        f"(FrameRing(slots, transport.i420_shape(H, W)))")
+        if not is_i420_shape(have):
+            refuse(who, f"frame_format='i420': ring {k} has slots of shape {have}, which is no [H * 3 / 2, W] plane block (FrameRing(slots, transport.i420_shape(H, W)))")
 
     @classmethod
     def _check_idle_frames(cls, batcher, rings):
@@ -330,13 +529,45 @@ class PipelinedScheduler(SessionScheduler):
             refuse(who, f"idle_frames=True: {name} does not state its frames' channel order (frame_order = 'bgr' or 'rgb')")
         if not getattr(batcher, "paste", False):
             refuse(who, f"idle_frames=True: {name} was built with paste=False; the frames of a batch that runs no network have the pasted frames' size")
-        for k, s in enumerate(batcher.sessions):
-            hw = batcher.frame_hw(k) if callable(getattr(batcher, "frame_hw", None)) else None
-            if hw is None:
-                refuse(who, f"idle_frames=True: session {k} has no AvatarFrames (its frame size is not known before a step)")
-            cv = getattr(s, "custom_videos", None)
-            if cv is not None:
-                cv.check_size(hw[0], hw[1], f"{who}: session {k}")
+        for k in live_sessions(batcher):
+            cls._check_session_idle(k, batcher.sessions[k], batcher.frame_hw(k) if callable(getattr(batcher, "frame_hw", None)) else None)
+
+    @classmethod
+    def _check_session_idle(cls, k, session, hw):
+        """idle_frames=True, one session: its frame size is known before a step and its custom videos have that size (constructor and add_session)"""
+        who = cls.__name__
+        if hw is None:
+            refuse(who, f"idle_frames=True: session {k} has no AvatarFrames (its frame size is not known before a step)")
+        cv = getattr(session, "custom_videos", None)
+        if cv is not None:
+            cv.check_size(hw[0], hw[1], f"{who}: session {k}")
+
+    def _check_join(self, k, session, ring, frontend):
+        """what the constructor checks for a session and its ring, for the joiner (slot k): before anything is stored"""
+        who, bat = type(self).__name__, self.batcher
+        if (ring is None) != (self.rings is None):
+            refuse(who, "add_session: a ring per session, as the scheduler was built (rings=None: none)")
+        hw = bat.session_hw(session) if callable(getattr(bat, "session_hw", None)) else None
+        if self.frame_format == "i420":
+            self._check_session_format(k, ring, hw)
+        if self.idle_frames:
+            self._check_session_idle(k, session, hw)
+
+    def _store(self, k, session, ring, frontend):
+        if self.rings is not None:
+            self.rings[k] = ring
+
+    def _drop(self, k):
+        if self.rings is not None:
+            self.rings[k] = None
+        self._deferred.pop(k, None)
+
+    def _flush(self, k):
+        self._deferred.pop(k, None)                                  # (an empty queue has no deferred batch)
+        return super()._flush(k)
+
+    def _in_flight(self, k):
+        return any(k in item["ks"] for item in self.inflight)
 
     def _finish_frames(self, ks, out, audio):
         """idle_frames: every picked session's block of B finished frames in the ring's format, on the step's stream (one gather per session that has a non-speech
@@ -426,6 +657,7 @@ class PipelinedScheduler(SessionScheduler):
         if self.idle_frames and len(pairs) != 2 * self.batcher.batch_size:
             refuse(type(self).__name__ + ".submit", f"idle_frames=True chooses every frame from its two (pcm, type) pairs: {len(pairs)} pairs for "
                                                     f"{self.batcher.batch_size} frames")
+        self._check_slot(k, "submit")
         self.queues[k].append((self.clock() if t_arrival is None else t_arrival, (payload, list(pairs))))
 
     def _retire(self, block=False):
@@ -450,6 +682,8 @@ class PipelinedScheduler(SessionScheduler):
                 done.append((k, fr, idx, t1 - item["arrival"][k]))
             self.busy_s += max(t1 - max(item["t0"], self._busy_until), 0.0)      # union of the steps' [launch, done] intervals
             self._busy_until = max(self._busy_until, t1)
+        if self.leaving:                                                 # a removed session's last batch has retired: its rows, slot and ring go now
+            self._release_left()
         return done
 
     def pending(self):
