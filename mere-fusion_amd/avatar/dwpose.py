@@ -214,9 +214,6 @@ class DWPose:
         return g
 
     # ---- execution -------------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def logits(self, frames_u8, flip=True):
         """uint8 BGR device frames [n, H, W, 3] -> (simcc_x [n, K, 2w], simcc_y [n, K, 2h], the two of the mirrored pass or None, None), fp32 on the device"""
         if self._sd is None:
@@ -237,9 +234,9 @@ class DWPose:
         ly = torch.empty((B, g["K"], g["by"]), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mf_warp_affine_u8(net._h, g["inp"], C.c_void_p(fr.data_ptr()), n, H, W, C.c_void_p(minv.data_ptr()), (C.c_float * 3)(*MEAN),
-                                                    (C.c_float * 3)(*STD), 1, int(bool(flip)), self._stream()), "warp_affine_u8")
+                                                    (C.c_float * 3)(*STD), 1, int(bool(flip)), _lib.stream_ptr(self.device)), "warp_affine_u8")
             net.run(B)
-            _lib.check(_lib.lib().mf_rtmcc_head_forward(self._head, net._h, g["maps"], 0, B, C.c_void_p(lx.data_ptr()), C.c_void_p(ly.data_ptr()), self._stream()),
+            _lib.check(_lib.lib().mf_rtmcc_head_forward(self._head, net._h, g["maps"], 0, B, C.c_void_p(lx.data_ptr()), C.c_void_p(ly.data_ptr()), _lib.stream_ptr(self.device)),
                        "rtmcc_head_forward")
         return (lx[:n], ly[:n], lx[n:], ly[n:]) if flip else (lx, ly, None, None)
 
@@ -268,5 +265,5 @@ def simcc_decode(lx, ly, fx, fy, pairs, input_size, center, scale):
         _lib.check(_lib.lib().mf_simcc_decode(p(lx), p(ly), p(fx), p(fy), (C.c_int * K)(*[int(v) for v in pairs]) if pairs is not None else None, n, K, int(lx.shape[2]),
                                               int(ly.shape[2]), int(input_size[0]), int(input_size[1]), (C.c_float * 2)(*[float(v) for v in center]),
                                               (C.c_float * 2)(*[float(v) for v in scale]), p(kpts), p(scores),
-                                              C.c_void_p(torch.cuda.current_stream(lx.device).cuda_stream)), "simcc_decode")
+                                              _lib.stream_ptr(lx.device)), "simcc_decode")
     return kpts, scores

@@ -51,7 +51,7 @@ def finish_masks(masks, jobs, blur=True, want_pre_blur=False):
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mf_face_mask_finish(masks.data_ptr(), masks.shape[1], masks.shape[2], _ints(jobs), len(jobs), int(bool(blur)), ws.data_ptr(), ws.numel(),
                                                   None if pre is None else pre.data_ptr(), None if out is None else out.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "face_mask_finish")
+                                                  _lib.stream_ptr(dev)), "face_mask_finish")
 
     def split(flat):
         res, o = [], 0
@@ -106,7 +106,7 @@ class FaceParsing:
             with torch.cuda.device(dev):
                 _lib.check(_lib.lib().mf_face_mask_parse(n._h, g["inp"], g["out"], self.net.n_classes, frames_u8.data_ptr(), frames_u8.shape[0], frames_u8.shape[1],
                                                          frames_u8.shape[2], int(bool(reverse_channels)), _ints(jobs), len(jobs), mean, std, ws.data_ptr(), ws.numel(),
-                                                         out[i:i + len(jobs)].data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "face_mask_parse")
+                                                         out[i:i + len(jobs)].data_ptr(), _lib.stream_ptr(dev)), "face_mask_parse")
         return out
 
     @staticmethod

@@ -35,7 +35,7 @@ class Net:
             pass
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     def buffer(self, Cn, H, W, halo=1):
         with torch.cuda.device(self.device):

@@ -57,7 +57,7 @@ def lip_boxes(boxes, counts, H, W, pads=(0, 10, 0, 0), nosmooth=False, T=SMOOTH_
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mf_avatar_lip_boxes(boxes.data_ptr(), counts.data_ptr(), n, int(boxes.shape[1]), int(H), int(W), (C.c_int * 4)(*[int(p) for p in pads]),
                                                   0 if nosmooth else int(T), coords.data_ptr(), jobs.data_ptr(), no_face.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "avatar_lip_boxes")
+                                                  _lib.stream_ptr(dev)), "avatar_lip_boxes")
     return coords, jobs, no_face
 
 
@@ -109,7 +109,7 @@ def landmark_boxes_device(kpts, boxes, counts, H, W, bbox_shift=0):
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mf_muse_landmark_boxes(kpts.data_ptr(), int(kpts.shape[1]), boxes.data_ptr(), counts.data_ptr(), n, int(boxes.shape[1]), int(H), int(W),
                                                      int(bbox_shift), coords.data_ptr(), flags.data_ptr(), sums.data_ptr(),
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "muse_landmark_boxes")
+                                                     _lib.stream_ptr(dev)), "muse_landmark_boxes")
     return coords, flags, sums
 
 

@@ -113,7 +113,7 @@ class s3fd:
             if i == 0:                                                   # max-out background label (net_s3fd.py:123-126)
                 c2 = torch.empty((B, 2) + tuple(cls.shape[2:]), dtype=torch.float32, device=cls.device)
                 _lib.check(_lib.lib().mf_s3fd_maxout_bg(C.c_void_p(cls.data_ptr()), C.c_void_p(c2.data_ptr()), B, cls.shape[2] * cls.shape[3],
-                                                        C.c_void_p(torch.cuda.current_stream(cls.device).cuda_stream)), "s3fd_maxout_bg")
+                                                        _lib.stream_ptr(cls.device)), "s3fd_maxout_bg")
                 cls = c2
             outs += [cls, n.output(ob, 4, B, coff=4)]
         return outs
@@ -177,7 +177,7 @@ def detect_from_heads(olist, cand_thresh=CAND_THRESH, nms_thresh=NMS_THRESH, fin
     with torch.cuda.device(dev):
         _lib.check(lib.mf_s3fd_detect_tensors(heads, (C.c_int * 12)(*hw), B, cand_thresh, nms_thresh, final_thresh, int(max_candidates), int(max_det),
                                               C.c_void_p(ws.data_ptr()), C.c_void_p(boxes.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(ncand.data_ptr()),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s3fd_detect_tensors")
+                                              _lib.stream_ptr(dev)), "s3fd_detect_tensors")
     return boxes, counts, ncand
 
 

@@ -107,7 +107,7 @@ class HipWav2Vec2ForCTC:
         out = torch.empty((S, self.n_frames, self.width), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mf_wav2vec2_forward(h, x.data_ptr(), n, S, out.data_ptr(),
-                                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "wav2vec2_forward")
+                                                      _lib.stream_ptr(self.device)), "wav2vec2_forward")
         return SimpleNamespace(last_hidden_state=out) if self.out_hidden else SimpleNamespace(logits=out)
 
 

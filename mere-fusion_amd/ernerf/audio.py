@@ -53,7 +53,7 @@ class HipAudioEncoder:
                 raise RuntimeError("HipAudioEncoder.encode_audio_smooth: prev must be the previous [1, 32] CUDA feature vector")
         _lib.check(self._lib.mf_audio_encoder_forward_smooth(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0]),
                                                              C.c_void_p(pv.data_ptr()) if pv is not None else None, C.c_void_p(out.data_ptr()),
-                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_audio_encoder_forward_smooth")
+                                                             _lib.stream_ptr()), "mf_audio_encoder_forward_smooth")
         return out
 
     def encode_audio(self, a):
@@ -63,5 +63,5 @@ class HipAudioEncoder:
         a = self._windows(a, "encode_audio")
         out = torch.empty(1, 32, device=a.device)
         _lib.check(self._lib.mf_audio_encoder_forward(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0]), C.c_void_p(out.data_ptr()),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_audio_encoder_forward")
+                                                      _lib.stream_ptr()), "mf_audio_encoder_forward")
         return out

@@ -34,7 +34,7 @@ def u8(t, name):
 
 
 def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return _lib.stream_ptr()
 
 
 def call(fn_name, *args):

@@ -72,7 +72,7 @@ class HipNeRFField:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         eye = float(e.reshape(-1)[0]) if e is not None else 0.0
         _lib.check(self._lib.mf_nerf_field_forward(self._h, p(x), p(d), p(ea), p(cc), eye, M, p(sig), p(rgb), p(aa), p(ae), p(un),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_field_forward")
+                                                   _lib.stream_ptr()), "mf_nerf_field_forward")
         return sig, rgb, aa, ae, un
 
     __call__ = forward

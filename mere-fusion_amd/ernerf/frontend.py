@@ -82,7 +82,7 @@ class TrainerMixin:
             out_i = torch.empty(H, W, 3, device=img.device)
             out_d = torch.empty(H, W, device=img.device)
             _lib.check(_lib.lib().mf_nerf_resize_frame(C.c_void_p(img.data_ptr()), C.c_void_p(dep.data_ptr()), h, w, int(H), int(W), C.c_void_p(out_i.data_ptr()),
-                                                       C.c_void_p(out_d.data_ptr()), None, C.c_void_p(torch.cuda.current_stream(img.device).cuda_stream)),
+                                                       C.c_void_p(out_d.data_ptr()), None, _lib.stream_ptr(img.device)),
                        "mf_nerf_resize_frame")
             img, dep = out_i, out_d
         pin_i, pin_d = self._mf_pinned(int(H), int(W))

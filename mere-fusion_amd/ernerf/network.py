@@ -43,7 +43,7 @@ class _Results(dict):
         dev = self["image"].device
         aa, ae, un = (torch.empty(self._n, device=dev) for _ in range(3))
         import ctypes as C
-        ptrs = (C.c_void_p(aa.data_ptr()), C.c_void_p(ae.data_ptr()), C.c_void_p(un.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        ptrs = (C.c_void_p(aa.data_ptr()), C.c_void_p(ae.data_ptr()), C.c_void_p(un.data_ptr()), _lib.stream_ptr(dev))
         if self._slot is None:
             _lib.check(_lib.lib().mf_nerf_head_sums(o._mf["renderer"]._head, self._n, *ptrs), "mf_nerf_head_sums")
         else:

@@ -75,7 +75,7 @@ class HipHeadRenderer:
                "frame_u8": torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if want_u8 else None}
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self._lib.mf_nerf_resize_frame(p(img), p(dep), h, w, H, W, p(res["image"]), p(res["depth"]), p(res["frame_u8"]),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_resize_frame")
+                                                  _lib.stream_ptr()), "mf_nerf_resize_frame")
         return res
 
     def finish_device(self, out, bg_color):
@@ -86,7 +86,7 @@ class HipHeadRenderer:
         per_ray = bg is not None and bg.numel() == 3 * N
         bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
         _lib.check(self._lib.mf_nerf_head_finish(self._head, N, p(bg), int(per_ray), bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]),
-                                                 p(out["frame_u8"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_finish")
+                                                 p(out["frame_u8"]), _lib.stream_ptr()), "mf_nerf_head_finish")
         return out
 
     def __del__(self):
@@ -134,7 +134,7 @@ class HipHeadRenderer:
             _lib.check(self._lib.mf_nerf_head_render(self._head, p(rays_o), p(rays_d), N, p(self.bitfield), self.cascade, self.grid_size, self.min_near,
                                                      float(dt_gamma), int(max_steps), float(T_thresh), self.density_scale, p(ea), p(ic), ev, p(bg), int(per_ray) if finish else -1,
                                                      bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]), p(out["frame_u8"]),
-                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_render")
+                                                     _lib.stream_ptr()), "mf_nerf_head_render")
 
         def fresh():
             return {"image": torch.empty(N, 3, device=dev), "depth": torch.empty(N, device=dev), "weights_sum": torch.empty(N, device=dev),
@@ -237,7 +237,7 @@ class HipHeadRenderer:
         _lib.check(self._lib.mf_nerf_head_batch_render(h, descs, F, N, C.c_void_p(self.bitfield.data_ptr()), self.cascade, self.grid_size, self.min_near,
                                                        float(dt_gamma), int(max_steps), float(T_thresh), self.density_scale,
                                                        C.c_void_p(aabb.data_ptr()) if aabb is not None else None,
-                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_batch_render")
+                                                       _lib.stream_ptr()), "mf_nerf_head_batch_render")
         del keep
         return outs
 
@@ -250,7 +250,7 @@ class HipHeadRenderer:
             per_ray = bg is not None and bg.numel() == 3 * N
             bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
             _lib.check(self._lib.mf_nerf_head_batch_finish(self._batch, i, N, p(bg), int(per_ray), bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]),
-                                                           p(out["frame_u8"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_head_batch_finish")
+                                                           p(out["frame_u8"]), _lib.stream_ptr()), "mf_nerf_head_batch_finish")
         return outs
 
     FRAME_BATCH = True                  # render_frames takes torso_batch (nerf_serving.NerfBatcher asks before it passes it)
@@ -333,7 +333,7 @@ class HipHeadRenderer:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self._lib.mf_nerf_density_grid_update(self.field._h, p(density_grid), p(self.bitfield), cascades, H, self.bound, p(ea), ev, int(use_eye),
                                                          self.density_scale, float(decay), float(density_thresh), p(noise), p(tmp_grid), p(xyzs_out), p(mean),
-                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_density_grid_update")
+                                                         _lib.stream_ptr()), "mf_nerf_density_grid_update")
         return mean
 
     @torch.no_grad()
@@ -357,7 +357,7 @@ class HipHeadRenderer:
         poses = poses.contiguous()
         fx, fy, cx, cy = (float(v) for v in intrinsic)
         _lib.check(self._lib.mf_nerf_mark_untrained(C.c_void_p(poses.data_ptr()), int(poses.shape[0]), fx, fy, cx, cy, self.bound, cascades, H,
-                                                    C.c_void_p(density_grid.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                    C.c_void_p(density_grid.data_ptr()), _lib.stream_ptr()),
                    "mf_nerf_mark_untrained")
 
     @torch.no_grad()
@@ -401,6 +401,6 @@ class HipHeadRenderer:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self._lib.mf_nerf_finish(p(image), p(depth), p(weights_sum), p(nears), p(fars), p(bg), int(per_ray),
                                             float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color)), N, p(frame),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_finish")
+                                            _lib.stream_ptr()), "mf_nerf_finish")
         return {"image": image, "depth": depth, "ambient_aud": amb_aud_sum, "ambient_eye": amb_eye_sum, "uncertainty": unc_sum,
                 "weights_sum": weights_sum, "frame_u8": frame, "trace": trace}

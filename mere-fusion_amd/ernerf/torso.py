@@ -105,7 +105,7 @@ class HipTorso:
         grid = self._grid(self.density_grid if density_grid is None else density_grid, "run_torso")
         _lib.check(self._lib.mf_nerf_torso_set_grid(self._h, p(grid)), "mf_nerf_torso_set_grid")
         _lib.check(self._lib.mf_nerf_torso_forward(self._h, p(xy), cbuf, p(bg), int(per_ray), float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color)),
-                                                   self.thresh, N, p(out), p(alpha), p(deform), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                   self.thresh, N, p(out), p(alpha), p(deform), _lib.stream_ptr()),
                    "mf_nerf_torso_forward")
         return {"bg_color": out, "torso_alpha": alpha.view(N, 1), "deform": deform}
 
@@ -150,7 +150,7 @@ class HipTorso:
             self._fb, self._fb_pixels = fb, N
         grid = self._grid(self.density_grid if density_grid is None else density_grid, "run_torso_batch")
         _lib.check(self._lib.mf_nerf_torso_set_grid(self._h, C.c_void_p(grid.data_ptr())), "mf_nerf_torso_set_grid")
-        _lib.check(self._lib.mf_nerf_torso_forward_batch(self._h, fb, descs, F, N, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+        _lib.check(self._lib.mf_nerf_torso_forward_batch(self._h, fb, descs, F, N, _lib.stream_ptr()),
                    "mf_nerf_torso_forward_batch")
         del keep
         return outs
@@ -187,6 +187,6 @@ class HipTorso:
         mean = torch.empty((), dtype=torch.float32, device=grid.device)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self._lib.mf_nerf_torso_grid_update(self._h, cbuf, p(noise), float(decay), p(grid), p(raw), p(xys_out), p(mean),
-                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mf_nerf_torso_grid_update")
+                                                       _lib.stream_ptr()), "mf_nerf_torso_grid_update")
         self.density_grid = grid
         return mean

@@ -42,7 +42,7 @@ def feature_chunks_device(feat, left_rows, rows_per_chunk=10, out=None):
     rows = (C.c_int * B)(*[int(r) for r in left_rows])
     with torch.cuda.device(feat.device):
         _lib.check(_lib.lib().mf_whisper_feature_chunks(feat.data_ptr(), T, L1 * Cc, rows, rows_per_chunk, B, out.data_ptr(),
-                                                        C.c_void_p(torch.cuda.current_stream(feat.device).cuda_stream)), "whisper_feature_chunks")
+                                                        _lib.stream_ptr(feat.device)), "whisper_feature_chunks")
     return out
 
 
@@ -157,7 +157,7 @@ class MuseBatcher(PooledBatcher):
         crows = (C.c_int * n)(*rows)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mf_gather_rows_f32(self.pool.data_ptr(), self.pool.shape[0], self.row_elems, crows, n, lat.data_ptr(),
-                                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "gather_rows_f32")
+                                                     _lib.stream_ptr(self.device)), "gather_rows_f32")
         pred = self.unet.model(lat, self.t0, encoder_hidden_states=self.unet.pe(self.cat_inputs(chunks))).sample    # musereal.py:102-107
         return self.vae.decode_latents_device(pred)                                                     # musereal.py:108, frames stay in HBM
 

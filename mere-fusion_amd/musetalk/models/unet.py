@@ -96,7 +96,7 @@ class HipUNetModel:
         forward at that size and keeps the fastest; a server calls it at start-up for every batch size its loop emits, or ships MF_TUNE_CACHE.
         A forward itself never measures."""
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mf_unet_tune(self._h, int(batch), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "unet_tune")
+            _lib.check(_lib.lib().mf_unet_tune(self._h, int(batch), _lib.stream_ptr(self.device)), "unet_tune")
 
     def half(self):   # musereal.py:62; arithmetic mode is fixed at create time, dtype only labels the I/O tensors
         self.dtype = torch.float16

@@ -146,7 +146,7 @@ class VAE:
         mom = torch.empty((B, 2 * self._cfg.latent_channels, size // 8, size // 8), dtype=torch.float32, device=src.device)
         with torch.cuda.device(src.device):
             _lib.check(_lib.lib().mf_vae_encode(h, src.data_ptr() if image is not None else None, src.data_ptr() if image is None else None,
-                                                int(bool(half_mask)), mom.data_ptr(), B, C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)),
+                                                int(bool(half_mask)), mom.data_ptr(), B, _lib.stream_ptr(src.device)),
                        "vae_encode")
         return mom
 
@@ -210,7 +210,7 @@ class VAE:
         with torch.cuda.device(lat.device):
             _lib.check(_lib.lib().mf_vae_decode_latents(self._h, lat.data_ptr(), frames.data_ptr(),
                                                         image.data_ptr() if want_image else None, B,
-                                                        C.c_void_p(torch.cuda.current_stream(lat.device).cuda_stream)),
+                                                        _lib.stream_ptr(lat.device)),
                        "vae_decode_latents")
         return (frames, image) if want_image else frames
 
@@ -219,4 +219,4 @@ class VAE:
 
     def tune(self, batch):
         """Explicit launch-configuration warm-up of the decoder at this batch size (mf_vae_tune; see HipUNetModel.tune)."""
-        _lib.check(_lib.lib().mf_vae_tune(self._h, int(batch), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "vae_tune")
+        _lib.check(_lib.lib().mf_vae_tune(self._h, int(batch), _lib.stream_ptr(self.device)), "vae_tune")

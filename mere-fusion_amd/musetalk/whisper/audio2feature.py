@@ -54,9 +54,6 @@ class Audio2Feature:
         except Exception:
             pass
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _wav(self, audio):
         """float32 waveform on the device: ndarray (museasr.py:25), list, or an already resident tensor."""
         if torch.is_tensor(audio):
@@ -69,7 +66,7 @@ class Audio2Feature:
         n = wav.numel()
         out = torch.empty((80, n // 160), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mf_whisper_log_mel(self._h, wav.data_ptr(), n, out.data_ptr(), self._stream()), "whisper_log_mel")
+            _lib.check(_lib.lib().mf_whisper_log_mel(self._h, wav.data_ptr(), n, out.data_ptr(), _lib.stream_ptr(self.device)), "whisper_log_mel")
         return out
 
     # ---- the encoder call -----------------------------------------------------------------------------------
@@ -114,7 +111,7 @@ class Audio2Feature:
         n = wav.numel()
         emb = torch.empty((self.n_layer + 1, self.n_ctx, self.n_state), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mf_whisper_encode_audio(self._h, wav.data_ptr(), n, emb.data_ptr(), self._stream()), "whisper_encode_audio")
+            _lib.check(_lib.lib().mf_whisper_encode_audio(self._h, wav.data_ptr(), n, emb.data_ptr(), _lib.stream_ptr(self.device)), "whisper_encode_audio")
         return emb[:, : int((n // 160) / 2)].permute(1, 0, 2).contiguous()     # audio2feature.py:104-110
 
     def audio2feat_device(self, audio):

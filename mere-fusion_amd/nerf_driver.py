@@ -65,7 +65,7 @@ class NerfFrameBatch:
             d = descs[i]
             d.torso_rgba, d.bg_image = s.torso_imgs[mi].data_ptr(), (s.bg_image.data_ptr() if s.bg_image is not None else None)
             d.bg_const, d.half_mode, d.bg_color = s.bg_const, int(s.half), out[i].data_ptr()
-        _lib.check(self._lib.mf_nerf_frame_batch_background(self._h, descs, F, s0.H, s0.W, s0._stream()), "mf_nerf_frame_batch_background")
+        _lib.check(self._lib.mf_nerf_frame_batch_background(self._h, descs, F, s0.H, s0.W, _lib.stream_ptr(s0.poses.device)), "mf_nerf_frame_batch_background")
         return out
 
     def frame_out(self, sessions, images, bodies, out):
@@ -92,7 +92,7 @@ class NerfFrameBatch:
             d.render, d.body_bgr = (image.data_ptr() if image is not None else None), (body.data_ptr() if body is not None else None)
             d.x0, d.y0 = (s.x0, s.y0) if (image is not None and body is not None) else (0, 0)
         _lib.check(self._lib.mf_nerf_frame_batch_out(self._h, descs, F, s0.H, s0.W, s0.GH, s0.GW, FH, FW, int(s0.linear_to_srgb), C.c_void_p(out.data_ptr()),
-                                                     s0._stream()), "mf_nerf_frame_batch_out")
+                                                     _lib.stream_ptr(s0.poses.device)), "mf_nerf_frame_batch_out")
         del keep
         return out
 
@@ -189,16 +189,13 @@ class NerfSession:
         self._lib = _lib.lib()
 
     # ---- the two launches around the render ------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.poses.device).cuda_stream)
-
     def background(self, mi):
         """bg_color [H * W, 3] fp32 of the frame (provider.py:316-330)"""
         if self.torso_imgs is None:
             return self.bg_color
         out = torch.empty(self.H * self.W, 3, dtype=torch.float32, device=self.poses.device)
         _lib.check(self._lib.mf_nerf_frame_background(C.c_void_p(self.torso_imgs[mi].data_ptr()), C.c_void_p(self.bg_image.data_ptr()) if self.bg_image is not None else None,
-                                                      self.bg_const, self.H, self.W, int(self.half), C.c_void_p(out.data_ptr()), self._stream()),
+                                                      self.bg_const, self.H, self.W, int(self.half), C.c_void_p(out.data_ptr()), _lib.stream_ptr(self.poses.device)),
                    "mf_nerf_frame_background")
         return out
 
@@ -226,7 +223,7 @@ class NerfSession:
         x0, y0 = (self.x0, self.y0) if (image is not None and body is not None) else (0, 0)
         _lib.check(self._lib.mf_nerf_frame_out(C.c_void_p(image.data_ptr()) if image is not None else None, self.H, self.W, self.GH, self.GW,
                                                C.c_void_p(body.data_ptr()) if body is not None else None, FH, FW, x0, y0, int(self.linear_to_srgb),
-                                               C.c_void_p(out.data_ptr()), self._stream()), "mf_nerf_frame_out")
+                                               C.c_void_p(out.data_ptr()), _lib.stream_ptr(self.poses.device)), "mf_nerf_frame_out")
         return out
 
     def next_custom(self, audiotype):

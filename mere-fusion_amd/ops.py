@@ -11,10 +11,6 @@ import torch
 from . import _lib
 
 
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _require_cuda(name, *tensors):
     for t in tensors:
         if not t.is_cuda:
@@ -39,7 +35,7 @@ def wav2lip_forward(handle: int, mel: torch.Tensor, face: torch.Tensor) -> torch
         return out
     with torch.cuda.device(mel.device):
         _lib.check(_lib.lib().mf_wav2lip_forward(handle, mel.data_ptr(), face.data_ptr(), out.data_ptr(), B,
-                                                 _stream_ptr(mel.device)), "wav2lip_forward")
+                                                 _lib.stream_ptr(mel.device)), "wav2lip_forward")
     return out
 
 
@@ -64,7 +60,7 @@ def wav2lip_forward_u8(handle: int, mel: torch.Tensor, faces_u8: torch.Tensor) -
         return out
     with torch.cuda.device(mel.device):
         _lib.check(_lib.lib().mf_wav2lip_forward_u8(handle, mel.data_ptr(), faces_u8.data_ptr(), out.data_ptr(), B,
-                                                    _stream_ptr(mel.device)), "wav2lip_forward_u8")
+                                                    _lib.stream_ptr(mel.device)), "wav2lip_forward_u8")
     return out
 
 
@@ -84,7 +80,7 @@ def melspec(wav: torch.Tensor, pad_mode: int) -> torch.Tensor:
     T = _lib.lib().mf_melspec_frames(n)
     out = torch.empty((80, T), dtype=torch.float32, device=wav.device)
     with torch.cuda.device(wav.device):
-        _lib.check(_lib.lib().mf_melspec(wav.data_ptr(), n, out.data_ptr(), int(pad_mode), _stream_ptr(wav.device)),
+        _lib.check(_lib.lib().mf_melspec(wav.data_ptr(), n, out.data_ptr(), int(pad_mode), _lib.stream_ptr(wav.device)),
                    "melspec")
     return out
 
@@ -112,7 +108,7 @@ def wav2lip_forward_u8_rows(handle, mel, face_pool, rows):
         return out
     with torch.cuda.device(mel.device):
         _lib.check(_lib.lib().mf_wav2lip_forward_u8_rows(handle, mel.data_ptr(), face_pool.data_ptr(), face_pool.shape[0], (C.c_int * B)(*rows),
-                                                         out.data_ptr(), B, _stream_ptr(mel.device)), "wav2lip_forward_u8_rows")
+                                                         out.data_ptr(), B, _lib.stream_ptr(mel.device)), "wav2lip_forward_u8_rows")
     return out
 
 
@@ -132,7 +128,7 @@ def melspec_windows(wav, starts, pad_mode, out=None):
         raise RuntimeError(f"melspec_windows: out must be a contiguous fp32 device tensor {shape}, got {out.dtype} {tuple(out.shape)}")
     with torch.cuda.device(wav.device):
         _lib.check(_lib.lib().mf_melspec_windows(wav.data_ptr(), n, nw, (C.c_int * len(starts))(*starts), len(starts), out.data_ptr(), int(pad_mode),
-                                                 _stream_ptr(wav.device)), "melspec_windows")
+                                                 _lib.stream_ptr(wav.device)), "melspec_windows")
     return out
 
 
@@ -167,7 +163,7 @@ def windows_push(buf, rows, new, out=None):
         raise RuntimeError(f"windows_push: out must be a contiguous fp32 tensor {(m, n)} on {buf.device}, got {what}")
     with torch.cuda.device(buf.device):
         _lib.check(_lib.lib().mf_windows_push(buf.data_ptr(), N, n, new.data_ptr(), int(new.shape[1]), (C.c_int * m)(*rows), m, out.data_ptr(),
-                                              _stream_ptr(buf.device)), "windows_push")
+                                              _lib.stream_ptr(buf.device)), "windows_push")
     return out
 
 
@@ -199,7 +195,7 @@ def frames_to_i420(frames, order="bgr", out=None):
         what = f"{out.dtype} {tuple(out.shape)} on {out.device}" if torch.is_tensor(out) else type(out).__name__
         raise RuntimeError(f"frames_to_i420: out must be a contiguous uint8 tensor {shape} on {frames.device}, got {what}")
     with torch.cuda.device(frames.device):
-        _lib.check(_lib.lib().mf_frames_to_i420(frames.data_ptr(), B, H, W, FRAME_ORDERS[order], out.data_ptr(), _stream_ptr(frames.device)), "frames_to_i420")
+        _lib.check(_lib.lib().mf_frames_to_i420(frames.data_ptr(), B, H, W, FRAME_ORDERS[order], out.data_ptr(), _lib.stream_ptr(frames.device)), "frames_to_i420")
     return out
 
 
@@ -243,7 +239,7 @@ def gather_frames(sources, dst, out, fmt="packed", order="bgr"):
     for s, t, d in zip(srcs, sources, dst):
         s.frame, s.dst = t.data_ptr(), d
     with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().mf_frames_gather(srcs, len(sources), H, W, FRAME_FORMATS[fmt], FRAME_ORDERS[order], out.data_ptr(), N, _stream_ptr(out.device)),
+        _lib.check(_lib.lib().mf_frames_gather(srcs, len(sources), H, W, FRAME_FORMATS[fmt], FRAME_ORDERS[order], out.data_ptr(), N, _lib.stream_ptr(out.device)),
                    "frames_gather")
     return out
 
@@ -338,7 +334,7 @@ def crop_resize_u8(frames, boxes, size, mode="linear", frame_indices=None, out=N
         raise RuntimeError(f"crop_resize_u8: out must be a contiguous uint8 tensor {shape} on {dev}, got {what}")
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mf_crop_resize_u8(frames.data_ptr(), n, H, W, jobs_dev.data_ptr(), jobs_host, n_jobs, out.data_ptr(), dh, dw, _lib.CROP_MODES[mode],
-                                                *[None if t is None else t.data_ptr() for t in tables], _stream_ptr(dev)), "crop_resize_u8")
+                                                *[None if t is None else t.data_ptr() for t in tables], _lib.stream_ptr(dev)), "crop_resize_u8")
     return out
 
 
@@ -366,7 +362,7 @@ def nerf_feat_scatter(feats, left, right, rings, rows, starts):
         raise RuntimeError(f"nerf_feat_scatter: {S} rows and {n} starts for {feats.shape[0]} slices of the net output")
     with torch.cuda.device(rings.device):
         _lib.check(_lib.lib().mf_nerf_feat_scatter(feats.data_ptr(), S, feats.shape[1], feats.shape[2], int(left), int(right), rings.data_ptr(), rings.shape[0],
-                                                   rings.shape[1], crows, cstarts, _stream_ptr(rings.device)), "nerf_feat_scatter")
+                                                   rings.shape[1], crows, cstarts, _lib.stream_ptr(rings.device)), "nerf_feat_scatter")
 
 
 def nerf_feat_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
@@ -399,7 +395,7 @@ def nerf_feat_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
         raise RuntimeError(f"nerf_feat_windows: out must be a contiguous fp32 device tensor {shape}, got {out.dtype} {tuple(out.shape)}")
     with torch.cuda.device(rings.device):
         _lib.check(_lib.lib().mf_nerf_feat_windows(rings.data_ptr(), hist.data_ptr() if att else None, N, R, dim, S, crows, lists[0][0], lists[1][0], lists[2][0],
-                                                   int(bool(att)), out.data_ptr(), _stream_ptr(rings.device)), "nerf_feat_windows")
+                                                   int(bool(att)), out.data_ptr(), _lib.stream_ptr(rings.device)), "nerf_feat_windows")
     return out
 
 
@@ -417,7 +413,7 @@ def unet_forward(handle: int, latents: torch.Tensor, audio: torch.Tensor, add_pe
     if B == 0:
         return out
     with torch.cuda.device(lat.device):
-        _lib.check(_lib.lib().mf_unet_forward(handle, lat.data_ptr(), aud.data_ptr(), int(add_pe), out.data_ptr(), B, _stream_ptr(lat.device)),
+        _lib.check(_lib.lib().mf_unet_forward(handle, lat.data_ptr(), aud.data_ptr(), int(add_pe), out.data_ptr(), B, _lib.stream_ptr(lat.device)),
                    "unet_forward")
     return out
 
@@ -439,7 +435,7 @@ def vae_decode_latents(handle: int, latents: torch.Tensor) -> torch.Tensor:
     if B == 0:
         return frames
     with torch.cuda.device(lat.device):
-        _lib.check(_lib.lib().mf_vae_decode_latents(handle, lat.data_ptr(), frames.data_ptr(), None, B, _stream_ptr(lat.device)), "vae_decode_latents")
+        _lib.check(_lib.lib().mf_vae_decode_latents(handle, lat.data_ptr(), frames.data_ptr(), None, B, _lib.stream_ptr(lat.device)), "vae_decode_latents")
     return frames
 
 
@@ -459,7 +455,7 @@ def whisper_encode_windows(handle: int, wavs: torch.Tensor, ctx_tokens: int, n_l
     S, n = w.shape
     feat = torch.empty((S, n // 320, n_layers1, n_state), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _lib.check(_lib.lib().mf_whisper_encode_windows(handle, w.data_ptr(), n, S, int(ctx_tokens), feat.data_ptr(), _stream_ptr(w.device)),
+        _lib.check(_lib.lib().mf_whisper_encode_windows(handle, w.data_ptr(), n, S, int(ctx_tokens), feat.data_ptr(), _lib.stream_ptr(w.device)),
                    "whisper_encode_windows")
     return feat
 

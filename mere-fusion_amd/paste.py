@@ -4,8 +4,6 @@ The reference does this per frame on the host after a D2H of every generated fac
 musetalk/utils/blending.py:103-125).  Here the avatar's full frames, bboxes and masks are cached on the device once and a batch of
 generated faces is composed into a batch of uint8 BGR frames in one launch; results are bit-exact with OpenCV's 8-bit arithmetic
 (csrc/mf_blend.hip).  There is no CPU path."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -86,7 +84,7 @@ class AvatarFrames:
         with torch.cuda.device(res.device):
             _lib.check(_lib.lib().mf_paste_frames(res.data_ptr(), int(res.dtype == torch.float32), res.shape[1], res.shape[2], self.frames.data_ptr(),
                                                   self.n, self.H, self.W, jobs, B, out.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream(res.device).cuda_stream)), "paste_frames")
+                                                  _lib.stream_ptr(res.device)), "paste_frames")
         return out
 
     def paste_i420(self, res, indices, out=None):
@@ -141,5 +139,5 @@ def resize_linear_u8(src, dw, dh):
     dst = torch.empty((dh, dw, 3), dtype=torch.uint8, device=src.device)
     with torch.cuda.device(src.device):
         _lib.check(_lib.lib().mf_resize_linear_u8(src.data_ptr(), src.shape[0], src.shape[1], dst.data_ptr(), int(dh), int(dw),
-                                                  C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)), "resize_linear_u8")
+                                                  _lib.stream_ptr(src.device)), "resize_linear_u8")
     return dst

@@ -7,7 +7,6 @@ scores them on demand.  Neither is wired into the schedulers: a deployment calls
 [upstream-knowledge] The windowing rule and the score are upstream Wav2Lip's (color_syncnet_train.py, hparams.py: window i starts at frame i, its mel window at
 column int(80 * i / fps), syncnet_mel_step_size = 16 columns of the hop-200 mel at 16 kHz); that file is not part of the reference tree, which ships the module
 alone.  The network is pinned to the reference's module; no real checkpoint has been loaded here, and scores on seeded weights say nothing about sync."""
-import ctypes as C
 from types import SimpleNamespace
 
 import torch
@@ -61,7 +60,7 @@ def sync_score(face_emb, audio_emb, max_shift, out=None):
     _lib.init_device(f.device.index if f.device.index is not None else torch.cuda.current_device())
     with torch.cuda.device(f.device):
         _lib.check(_lib.lib().mf_sync_score(f.data_ptr(), a.data_ptr(), W, dim, int(max_shift), sim.data_ptr(), curve.data_ptr(), counts.data_ptr(),
-                                            C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)), "sync_score")
+                                            _lib.stream_ptr(f.device)), "sync_score")
     return sim, curve, counts
 
 

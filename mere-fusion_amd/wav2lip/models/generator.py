@@ -161,7 +161,7 @@ class Wav2Lip(nn.Module):
             raise RuntimeError("Wav2Lip.tune: run one forward first")
         dev = self._handle_device
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mf_wav2lip_tune(self._handle, int(batch), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wav2lip_tune")
+            _lib.check(_lib.lib().mf_wav2lip_tune(self._handle, int(batch), _lib.stream_ptr(dev)), "wav2lip_tune")
 
     def read_tap(self, name, batch):
         """Intermediate activation of the last forward as fp32 NCHW (parity tests)."""
@@ -176,6 +176,6 @@ class Wav2Lip(nn.Module):
         out = torch.empty((batch,) + shapes[name], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().mf_wav2lip_read_tap(self._handle, name.encode(), out.data_ptr(), batch,
-                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                                      _lib.stream_ptr(dev)),
                        "wav2lip_read_tap")
         return out

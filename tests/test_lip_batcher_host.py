@@ -2,14 +2,11 @@
 CPU tensors -- pool offsets, the ping-pong walk, silence, `only=`, validation before any index moves, scheduling on an injected clock, ring deferral -- and the
 C ABI of the two entry points underneath (header, exports, ctypes table, argument checks that need no device)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from mere_fusion_amd import lip_driver as D
 from serving_fakes import FakeBatcher, FakeRing, fake_cuda_events
 
@@ -270,15 +267,10 @@ def test_a_failed_step_does_not_slide_the_window_twice(monkeypatch):
 NEW_SYMBOLS = ("mf_melspec_windows", "mf_wav2lip_forward_u8_rows")
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "merefusion.h")).read()
-    bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return text, sorted(set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", bare)))
-
-
 def test_header_exports_and_ctypes_table_agree_for_the_new_symbols(lib_built):
     from mere_fusion_amd import _lib
-    text, names = _declared()
+    declared = _lib.HEADER.functions
+    names = sorted(declared)
     lib = C.CDLL(lib_built)
     for n in NEW_SYMBOLS:
         assert n in names, f"{n} is not declared in merefusion.h"
@@ -286,10 +278,9 @@ def test_header_exports_and_ctypes_table_agree_for_the_new_symbols(lib_built):
         assert n in _lib.SIGNATURES, f"{n} has no ctypes signature"
     assert sorted(_lib.SIGNATURES) == names
     # argument counts of the ctypes rows against the declarations
-    bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for n in NEW_SYMBOLS:
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % n, bare).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[n][1]) == 8, n
+        assert len(declared[n][1]) == len(_lib.SIGNATURES[n][1]) == 8, n
+    text = open(_lib.HEADER_PATH).read()
     assert "lipasr.py:24-35" in text[text.index("mf_melspec_frames(int n);"):text.index("mf_melspec_windows(")]
     assert _lib.lib().mf_abi_version() == 4
 

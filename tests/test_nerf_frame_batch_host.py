@@ -3,13 +3,10 @@ and ctypes table, every argument refusal by name before anything touches a devic
 exists on a box without a GPU), and `NerfBatcher`'s grouping: frames of unequal size never share a call, and a size's frames fill neighbouring slots of one
 block.  The bits are tests/test_nerf_frame_batch.py's business."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
 import nerf_serving_util as U  # noqa: F401  (the serving tests' shared helpers live on the same path)
 
 NEW_SYMBOLS = ("mf_nerf_frame_batch_create", "mf_nerf_frame_batch_destroy", "mf_nerf_frame_batch_background", "mf_nerf_torso_forward_batch",
@@ -19,18 +16,16 @@ B = 2
 
 def test_new_symbols_in_header_exports_and_ctypes_table(lib_built):
     from mere_fusion_amd import _lib
-    text = open(os.path.join(ROOT, "include", "merefusion.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = _lib.HEADER.functions
     lib = C.CDLL(lib_built)
     for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, text), f"{name} is not declared in merefusion.h"
+        assert name in declared, f"{name} is not declared in merefusion.h"
         assert hasattr(lib, name), f"{name} is not exported"
         assert name in _lib.SIGNATURES, f"{name} is not in the ctypes table"
     # the declared argument lists, against the ctypes table: as many arguments, and the descriptor tables typed
     for name, n_args in (("mf_nerf_frame_batch_create", 3), ("mf_nerf_frame_batch_destroy", 1), ("mf_nerf_frame_batch_background", 6),
                          ("mf_nerf_torso_forward_batch", 6), ("mf_nerf_frame_batch_out", 12)):
-        decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1)
-        assert len(decl.split(",")) == n_args == len(_lib.SIGNATURES[name][1]), (name, decl)
+        assert len(declared[name][1]) == n_args == len(_lib.SIGNATURES[name][1]), (name, declared[name])
     assert _lib.SIGNATURES["mf_nerf_frame_batch_background"][1][1] is C.POINTER(_lib.MfNerfBgDesc)
     assert _lib.SIGNATURES["mf_nerf_torso_forward_batch"][1][2] is C.POINTER(_lib.MfNerfTorsoDesc)
     assert _lib.SIGNATURES["mf_nerf_frame_batch_out"][1][1] is C.POINTER(_lib.MfNerfOutDesc)

@@ -3,15 +3,12 @@ with the two launches replaced by a restatement of what include/merefusion.h say
 bit for bit without a device; `NerfBatcher` and scheduler bookkeeping and refusals with stand-in sessions; and the C ABI of the two entries (header, exports,
 ctypes table, argument checks that never launch)."""
 import ctypes as C
-import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 import nerf_serving_util as U
 from serving_fakes import FakeRing, fake_cuda_events
 
@@ -348,14 +345,12 @@ NEW_SYMBOLS = {"mf_nerf_feat_scatter": 12, "mf_nerf_feat_windows": 13}
 
 def test_header_exports_and_ctypes_table_agree_for_the_new_symbols(lib_built):
     from mere_fusion_amd import _lib
-    text = open(os.path.join(ROOT, "include", "merefusion.h")).read()
-    bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", bare)))
+    declared = _lib.HEADER.functions
+    names = sorted(declared)
     lib = C.CDLL(lib_built)
     for n, n_args in NEW_SYMBOLS.items():
         assert n in names and hasattr(lib, n) and n in _lib.SIGNATURES, n
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % n, bare).group(1)
-        assert len(args.split(",")) == len(_lib.SIGNATURES[n][1]) == n_args, n
+        assert len(declared[n][1]) == len(_lib.SIGNATURES[n][1]) == n_args, n
     assert sorted(_lib.SIGNATURES) == names
     assert _lib.lib().mf_abi_version() == 4
 
