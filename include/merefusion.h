@@ -563,7 +563,7 @@ int mf_nerf_frame_batch_out(mf_nerf_frame_batch* h, const mf_nerf_out_desc* desc
 
 /* ---- the audio features of many ER-NeRF sessions (mf_nerf_featpool.hip; nerf_serving.NerfFeaturePool) ---- */
 /* What `NerfASR` keeps per session in torch tensors, for N sessions in two caller-owned device buffers: rings fp32 [N][R][dim] (`feat_queue`,
- * nerfasr.py:48-50; R = feat_buffer_size * m = 32) and hist fp32 [N][8][dim][16] (`att_feats`, nerfasr.py:55, as a circular buffer).  Both entries are
+ * nerfasr.py:48-50; R = feat_buffer_size * m = 32) and hist fp32 [N][8][dim][16] (`att_feats`, nerfasr.py:55, as a circular buffer).  All entries are
  * stateless, take HOST int arrays of one value per picked session (read during the call only; they travel as launch arguments), check every argument
  * before anything is enqueued and never wait for the host: one launch per 64 picked sessions.  dim 1..1024, R >= 16, rows distinct and inside N, else
  * MF_ERR_INVALID.  They move fp32 values only.
@@ -583,6 +583,14 @@ int mf_nerf_feat_scatter(const float* feats, int n_sessions, int T, int dim, int
  * out is [n_sessions][1][dim][16]. */
 int mf_nerf_feat_windows(const float* rings, float* hist, int N, int R, int dim, int n_sessions, const int* rows, const int* fronts,
                          const int* heads, const int* n_new, int att, float* out, void* stream);
+/* mf_nerf_feat_rows_load: a session joins, starts again or is reset.  For each of the n_rows named rows (HOST int array, as above) the ring row [R][dim]
+ * is written from src_ring (device fp32 [R][dim]; NULL: zeros) and, when hist is not NULL, the history row [8][dim][16] from src_hist (NULL: zeros): the
+ * state a warmed-up `NerfASR` holds, taken once, reaches any number of rows without running the net.  One launch per 64 rows, 16-byte accesses: R must be
+ * a multiple of 4 (it is 4 * m) and every buffer 16-byte aligned.  A source may lie in the same allocation as the pool (a row that is never named) but
+ * must not overlap a named row.  Refused with MF_ERR_INVALID before any launch: rings or rows NULL, src_hist without hist, dim / R / N outside the
+ * ranges above, a row out of range or named twice, a misaligned buffer, an overlapping source. */
+int mf_nerf_feat_rows_load(float* rings, float* hist, int N, int R, int dim, int n_rows, const int* rows, const float* src_ring,
+                           const float* src_hist, void* stream);
 
 /* ---- ER-NeRF head frame without host round trips ----------------------------------------------- */
 typedef struct mf_nerf_head mf_nerf_head;

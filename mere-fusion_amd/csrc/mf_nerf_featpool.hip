@@ -1,17 +1,18 @@
 // The audio-feature pool of many ER-NeRF sessions (nerf_serving.NerfFeaturePool): what `NerfASR` keeps per session as torch tensors -- the feature ring
 // `feat_queue` [R, dim] (nerfasr.py:48-50) and the attention windows `att_feats` (nerfasr.py:55, 75-103) -- for N sessions in two caller-owned buffers,
-// served by two stateless launches whatever the number of sessions:
+// served by stateless launches whatever the number of sessions:
 //
 //   k_nerf_feat_scatter   nerfasr.py:119-124 + :140-142: rows [left, right) of each picked session's slice of the net output into its ring
 //   k_nerf_feat_windows   nerfasr.py:75-103: each picked session's new [dim, 16] windows out of its ring (transposed through LDS), into its circular
 //                         history of eight, and the eight, oldest first, to the frame's `auds`
+//   k_nerf_feat_rows_load a session joins, starts again or is reset: whole pool rows (ring and history) written from one snapshot row, or zeroed
 //
 // What the eight windows of a frame hold is what `torch.stack(self.att_feats)` reads at that moment.  A window whose rows wrap round the ring's end was built by
 // `torch.cat` (nerfasr.py:81): a copy, which keeps its values -- the history.  A window that does not wrap is `feat_queue[front:tail].permute(1, 0)`
 // (:79, 86): a VIEW of the ring, which shows whatever run_step has written under it since -- such a window is read from the ring again every frame.  The four
 // zero windows of :55 are tensors of their own: history slots the caller has zeroed.
 //
-// Both only move fp32 values: the results are the reference's bits.  Session rows and positions travel as launch arguments (one struct of at most
+// All three only move fp32 values: the results are the reference's bits.  Session rows and positions travel as launch arguments (one struct of at most
 // CHUNK sessions per launch); nothing is read back and nothing waits for the host.
 #include "mf_common.h"
 #include <vector>
@@ -38,6 +39,10 @@ struct WindowArgs {
     int front[CHUNK][HIST];            // per window of `out`, oldest first: the ring row it starts at; -1: a zero window of nerfasr.py:55
     int head[CHUNK];                   // history slot the first new window goes to
     int n_new[CHUNK];                  // new windows of this call (the last n_new of `out`): 1, or 4 on a session's first call
+};
+
+struct LoadArgs {
+    int row[CHUNK];
 };
 
 // grid (right - left, sessions of this launch).  One block copies one feature row.
@@ -84,6 +89,26 @@ __global__ __launch_bounds__(NT) void k_nerf_feat_windows(const float* __restric
             if (h) h[e] = v;
         }
     }
+}
+
+// grid (blocks per row, rows of this launch).  A copy: every lane moves 16 bytes per access, a wave one 1 KiB run; the blocks of a row stride over the row's
+// ring part and then over its history part.  R is a multiple of 4 and a history row is 128 * dim floats, so both parts are whole 16-byte groups and every row
+// starts on one.  src == nullptr: zeros.  The host has checked that no source overlaps a named row, so nothing is read that this launch writes.
+typedef float f4v __attribute__((ext_vector_type(4)));                // (the compiler's own vector: float4's union put the zero value on the stack)
+
+__device__ __forceinline__ void load_part(f4v* __restrict__ dst, const f4v* __restrict__ src, int n4, int first, int step) {
+    if (src) {
+        for (int e = first; e < n4; e += step) dst[e] = src[e];
+    } else {
+        for (int e = first; e < n4; e += step) dst[e] = (f4v)(0.f);
+    }
+}
+
+__global__ __launch_bounds__(NT) void k_nerf_feat_rows_load(f4v* __restrict__ rings, f4v* __restrict__ hist, int n4_ring, int n4_hist,
+                                                            const f4v* __restrict__ src_ring, const f4v* __restrict__ src_hist, LoadArgs a) {
+    const int row = a.row[blockIdx.y], first = blockIdx.x * NT + threadIdx.x, step = gridDim.x * NT;
+    load_part(rings + (size_t)row * n4_ring, src_ring, n4_ring, first, step);
+    if (hist) load_part(hist + (size_t)row * n4_hist, src_hist, n4_hist, first, step);
 }
 
 // every picked session once, inside the pool
@@ -153,6 +178,40 @@ extern "C" int mf_nerf_feat_windows(const float* rings, float* hist, int N, int 
         }
         hipLaunchKernelGGL(k_nerf_feat_windows, dim3((dim + TD - 1) / TD, n_out, ns), dim3(NT), 0, (hipStream_t)stream, rings, att ? hist : nullptr, R, dim,
                            n_out, a, out + (size_t)s0 * n_out * dim * WIN);
+        MF_HIP(hipGetLastError());
+    }
+    return MF_OK;
+}
+
+extern "C" int mf_nerf_feat_rows_load(float* rings, float* hist, int N, int R, int dim, int n_rows, const int* rows, const float* src_ring,
+                                      const float* src_hist, void* stream) {
+    MF_REQUIRE(rings && rows, "nerf_feat_rows_load: null argument");
+    MF_REQUIRE(hist || !src_hist, "nerf_feat_rows_load: null history with a history source (att == 0 keeps no history)");
+    MF_REQUIRE(dim >= 1 && dim <= 1024, "nerf_feat_rows_load: dim %d (1..1024)", dim);
+    MF_REQUIRE(R >= WIN && R <= (1 << 16) && R % 4 == 0, "nerf_feat_rows_load: a ring of %d rows (16..65536 and 4 * m: a row moves in 16-byte groups)", R);
+    MF_REQUIRE(N >= 1 && N <= (1 << 16), "nerf_feat_rows_load: a pool of %d sessions (1..65536)", N);
+    MF_REQUIRE(n_rows >= 1 && n_rows <= N, "nerf_feat_rows_load: %d picked sessions of %d", n_rows, N);
+    for (const void* p : {(const void*)rings, (const void*)hist, (const void*)src_ring, (const void*)src_hist})
+        MF_REQUIRE((uintptr_t)p % 16 == 0, "nerf_feat_rows_load: a buffer at %p is not 16-byte aligned", p);
+    if (const int rc = check_rows("nerf_feat_rows_load", rows, n_rows, N)) return rc;
+    const size_t ring_bytes = (size_t)R * dim * sizeof(float), hist_bytes = (size_t)HIST * dim * WIN * sizeof(float);
+    for (int s = 0; s < n_rows; ++s) {                                 // a source may lie in the pool's own allocation (a scratch row), but not under a named row
+        const uintptr_t r0 = (uintptr_t)rings + rows[s] * ring_bytes, h0 = (uintptr_t)hist + rows[s] * hist_bytes;
+        MF_REQUIRE(!src_ring || (uintptr_t)src_ring + ring_bytes <= r0 || r0 + ring_bytes <= (uintptr_t)src_ring,
+                   "nerf_feat_rows_load: the ring source overlaps session row %d", rows[s]);
+        MF_REQUIRE(!src_hist || (uintptr_t)src_hist + hist_bytes <= h0 || h0 + hist_bytes <= (uintptr_t)src_hist,
+                   "nerf_feat_rows_load: the history source overlaps session row %d", rows[s]);
+    }
+    const int n4_ring = (int)(ring_bytes / 16), n4_hist = hist ? (int)(hist_bytes / 16) : 0;
+    const int most = n4_ring > n4_hist ? n4_ring : n4_hist;
+    int blocks = (most + 4 * NT - 1) / (4 * NT);                       // four 16-byte groups per lane and part, up to 64 blocks a row
+    blocks = blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
+    for (int s0 = 0; s0 < n_rows; s0 += CHUNK) {
+        const int ns = n_rows - s0 < CHUNK ? n_rows - s0 : CHUNK;
+        LoadArgs a{};
+        for (int s = 0; s < ns; ++s) a.row[s] = rows[s0 + s];
+        hipLaunchKernelGGL(k_nerf_feat_rows_load, dim3(blocks, ns), dim3(NT), 0, (hipStream_t)stream, (f4v*)rings, (f4v*)hist, n4_ring, n4_hist,
+                           (const f4v*)src_ring, (const f4v*)src_hist, a);
         MF_HIP(hipGetLastError());
     }
     return MF_OK;

@@ -19,22 +19,38 @@ import numpy as np
 import torch
 
 from . import ops
-from .serving import PipelinedScheduler, SessionScheduler, refuse as _refuse, split_batch, step_sessions
+from .serving import PipelinedScheduler, SessionScheduler, live_sessions, refuse as _refuse, split_batch, step_sessions
+
+
+def host_rows_load(rings, hist, rows, src_ring=None, src_hist=None):
+    """what ops.nerf_feat_rows_load does, for a pool whose buffers are host tensors (device="cpu": the pools the CPU tests step; nothing is served from one)"""
+    for t, src in ((rings, src_ring), (hist, src_hist)):
+        if t is not None:
+            t[list(rows)] = 0.0 if src is None else src.clone()
 
 
 class NerfFeaturePool:
     """model: `HipWav2Vec2ForCTC(max_windows >= n_sessions)` or any callable that takes the raw samples [S, (m + l + r) * chunk] as a device tensor and returns an
     object with `.logits` or `.last_hidden_state` [S, T, audio_dim] on the device (normalisation is the callable's business, as with `RawProcessor`).
-    A fresh pool is in the state `NerfASR.__init__` leaves; `warm_up` adds `NerfASR.warm_up()` (nerfreal.py always warms up)."""
+    A fresh pool is in the state `NerfASR.__init__` leaves; `warm_up` adds `NerfASR.warm_up()` (nerfreal.py always warms up).
+    max_sessions=: rows are taken and given back while the others go on (`join`, `leave`, `warm_state`)."""
 
     HIST = 8                                                          # windows of one `auds` with att > 0 (nerfasr.py:77)
 
-    def __init__(self, n_sessions, model, audio_dim, att=2, m=8, l=10, r=10, fps=50, device="cuda"):
+    def __init__(self, n_sessions, model, audio_dim, att=2, m=8, l=10, r=10, fps=50, device="cuda", max_sessions=None):
         who = "NerfFeaturePool"
-        self.n_sessions, self.model, self.audio_dim, self.att = int(n_sessions), model, int(audio_dim), int(att)
+        self.model, self.audio_dim, self.att = model, int(audio_dim), int(att)
         self.m, self.l, self.r, self.chunk = int(m), int(l), int(r), 16000 // fps
-        if self.n_sessions < 1:
+        if int(n_sessions) < 1:
             _refuse(who, "at least one session is required")
+        # max_sessions: sessions come and go.  The buffers hold max_sessions rows, of which the first n_sessions are live, and one scratch row behind them that
+        # is never handed out: `warm_state` warms it up once and `join` copies it.  `n_sessions` is the number of session rows either way.
+        self.max_sessions = None if max_sessions is None else int(max_sessions)
+        if self.max_sessions is not None and self.max_sessions < int(n_sessions):
+            _refuse(who, f"max_sessions={max_sessions} for {n_sessions} initial sessions")
+        self.n_sessions = int(n_sessions) if self.max_sessions is None else self.max_sessions
+        self.vacant = set(range(int(n_sessions), self.n_sessions))
+        self.scratch = None if self.max_sessions is None else self.n_sessions
         if not 1 <= self.audio_dim <= 1024:
             _refuse(who, f"audio_dim {audio_dim} (1..1024)")
         if self.m < 2 or self.l < 0 or self.r < 0 or self.l + self.r < 1:
@@ -46,15 +62,16 @@ class NerfFeaturePool:
             _refuse(who, f"a ring of {self.R} rows cannot hold a 16-row window")
         self.total = self.m + self.l + self.r                          # chunks of one net window; also NerfASR.warm_up_steps (nerfasr.py:58)
         self.warm_up_steps = self.total
-        self.rings = torch.zeros((self.n_sessions, self.R, self.audio_dim), dtype=torch.float32, device=self.device)
-        self.hist = torch.zeros((self.n_sessions, self.HIST, self.audio_dim, 16), dtype=torch.float32, device=self.device) if self.att > 0 else None
-        self.pcm = np.zeros((self.n_sessions, self.total, self.chunk), np.float32)
-        N = self.n_sessions
+        N = self.n_sessions + (self.scratch is not None)
+        self.rings = torch.zeros((N, self.R, self.audio_dim), dtype=torch.float32, device=self.device)
+        self.hist = torch.zeros((N, self.HIST, self.audio_dim, 16), dtype=torch.float32, device=self.device) if self.att > 0 else None
+        self.pcm = np.zeros((N, self.total, self.chunk), np.float32)
         self.frames, self.feat_buffer_idx, self.front, self.tail, self.head, self.first = [0] * N, [0] * N, [0] * N, [0] * N, [0] * N, [True] * N
         self.win_fronts = [[] for _ in range(N)]                        # ring rows the windows `att_feats` holds start at, oldest first; -1: a zero window
         for k in range(N):
             self._reset_counters(k)
-        self.launches = self.net_calls = 0                              # kernel launches of this module's two entries / calls of the net, since creation
+        self.launches = self.net_calls = 0                              # kernel launches of this module's entries / calls of the net, since creation
+        self._warm = None                                               # warm_state(): the scratch row's host state once it has been warmed up
 
     # ---- host state ----------------------------------------------------------------------------------------------------------------------
     def _reset_counters(self, k):
@@ -73,7 +90,13 @@ class NerfFeaturePool:
             _refuse(who, f"a session appears twice in {ks}")
         if min(ks) < 0 or max(ks) >= self.n_sessions:
             _refuse(who, f"sessions {ks}: rows run from 0 to {self.n_sessions - 1}")
+        if self.vacant.intersection(ks):
+            _refuse(who, f"sessions {ks}: rows {sorted(self.vacant.intersection(ks))} are vacant (live rows: {self.live()})")
         return ks
+
+    def live(self):
+        """the rows that hold a session"""
+        return [k for k in range(self.n_sessions) if k not in self.vacant]
 
     def host_block(self, chunks, n_frames):
         """the 2 * n_frames new 20 ms chunks of one session as one fp32 [2 * n_frames, chunk] array; refuses anything else (before any state moves)"""
@@ -126,6 +149,9 @@ class NerfFeaturePool:
         blocks = [self._chunk(c) for c in chunks]
         if len(blocks) != len(ks):
             _refuse("NerfFeaturePool.run_step", f"{len(blocks)} chunks for {len(ks)} sessions")
+        self._run_step(ks, blocks)
+
+    def _run_step(self, ks, blocks):
         self._fire([(k, w) for k, w in ((k, self._advance(k, c)) for k, c in zip(ks, blocks)) if w is not None])
 
     def next_feat(self, ks, out=None):
@@ -163,23 +189,85 @@ class NerfFeaturePool:
             self.next_feat(ks, out=buf[b])
         return buf.transpose(0, 1)
 
-    def reset(self, ks=None):
-        """sessions ks (default: all) back to the state `NerfASR.__init__` leaves"""
-        ks = list(range(self.n_sessions)) if ks is None else self._rows([ks] if isinstance(ks, int) else ks, "NerfFeaturePool.reset")
+    def _load_rows(self, ks, ring=None, hist=None):
+        """rows ks of both buffers from one source row (None: zeros) in ONE launch (mf_nerf_feat_rows_load); nothing waits and nothing is allocated.  A pool
+        on the host -- the stand-in the CPU tests step -- has no device to launch on: `host_rows_load` states the same assignment."""
+        if not ks:                                                       # (reset() / warm_up() of a pool everyone has left)
+            return
+        (ops.nerf_feat_rows_load if self.rings.is_cuda else host_rows_load)(self.rings, self.hist, ks, ring, hist)
+        self.launches += 1
+
+    def _reset_rows(self, ks):
         for k in ks:
             self._reset_counters(k)
-            self.rings[k].zero_()
-            if self.hist is not None:
-                self.hist[k].zero_()
+        self._load_rows(ks)
+
+    def _warm_up_rows(self, ks):
+        self._reset_rows(ks)
+        silence = np.zeros(self.chunk, np.float32)
+        for _ in range(self.warm_up_steps):
+            self._run_step(ks, [silence] * len(ks))
+
+    def reset(self, ks=None):
+        """sessions ks (default: all live ones) back to the state `NerfASR.__init__` leaves"""
+        ks = self.live() if ks is None else self._rows([ks] if isinstance(ks, int) else ks, "NerfFeaturePool.reset")
+        self._reset_rows(ks)
         return ks
 
     def warm_up(self, ks=None):
-        """sessions ks (one number, a list; default: all) to the state `NerfASR.__init__` plus `warm_up()` leave (nerfasr.py:146-152: m + l + r run_steps on
-        silence), so that a session can join or start again while the others go on"""
-        ks = self.reset(ks)
-        silence = np.zeros(self.chunk, np.float32)
-        for _ in range(self.warm_up_steps):
-            self.run_step(ks, [silence] * len(ks))
+        """sessions ks (one number, a list; default: all live ones) to the state `NerfASR.__init__` plus `warm_up()` leave (nerfasr.py:146-152: m + l + r
+        run_steps on silence), so that a session can start again while the others go on.  (A session that JOINS takes that state from `join`, without the net.)"""
+        ks = self.live() if ks is None else self._rows([ks] if isinstance(ks, int) else ks, "NerfFeaturePool.warm_up")
+        self._warm_up_rows(ks)
+
+    # ---- rows that are taken and given back (max_sessions=) ---------------------------------------------------------------------------------
+    def _dynamic(self, what):
+        if self.scratch is None:
+            _refuse("NerfFeaturePool", f"{what}: this pool was built for a fixed list of sessions; NerfFeaturePool(..., max_sessions=) lets sessions come and go")
+
+    def warm_state(self):
+        """What `warm_up([k])` leaves in a row, computed ONCE (here, or from NerfBatcher.prewarm, before the serving loop): the scratch row runs exactly what
+        warm_up runs -- S = 1 net calls on silence -- and stays as the device snapshot; the host state stands beside it.  Silence gives every joiner the same
+        features, so installing this IS warm_up([k]): bit for bit where the net gives the same bits run to run."""
+        self._dynamic("warm_state")
+        if self._warm is None:
+            s = self.scratch
+            self._warm_up_rows([s])
+            self._warm = dict(pcm=self.pcm[s].copy(), frames=self.frames[s], feat_buffer_idx=self.feat_buffer_idx[s], front=self.front[s], tail=self.tail[s],
+                              head=self.head[s], first=self.first[s], win_fronts=list(self.win_fronts[s]))
+        return self._warm
+
+    def join(self, ks, warm=True):
+        """Vacant rows ks are taken: each gets the state `warm_up` leaves (warm=False: the state `NerfASR.__init__` leaves) through ONE launch on the current
+        stream -- no net call, no synchronisation, no allocation (the first join of a pool whose warm_state nobody has asked for computes it).  The caller
+        knows that no step in flight still reads these rows (NerfEndToEndScheduler releases a leaver's row only when its last batch has retired)."""
+        who = "NerfFeaturePool.join"
+        self._dynamic("join")
+        ks = [int(k) for k in ([ks] if isinstance(ks, int) else ks)]
+        if not ks or len(set(ks)) != len(ks) or min(ks) < 0 or max(ks) >= self.n_sessions:
+            _refuse(who, f"rows {ks}: distinct rows from 0 to {self.n_sessions - 1}")
+        if set(ks) - self.vacant:
+            _refuse(who, f"rows {sorted(set(ks) - self.vacant)} hold a session (vacant rows: {sorted(self.vacant)})")
+        w = self.warm_state() if warm else None
+        s = self.scratch
+        self._load_rows(ks, self.rings[s] if warm else None, self.hist[s] if warm and self.hist is not None else None)
+        for k in ks:
+            if warm:
+                self.pcm[k] = w["pcm"]
+                self.frames[k], self.feat_buffer_idx[k], self.front[k], self.tail[k] = w["frames"], w["feat_buffer_idx"], w["front"], w["tail"]
+                self.head[k], self.first[k], self.win_fronts[k] = w["head"], w["first"], list(w["win_fronts"])
+            else:
+                self._reset_counters(k)
+            self.vacant.discard(k)
+        return ks
+
+    def leave(self, k):
+        """row k is vacant again: refused by step / next_feat / run_step until a joiner takes it"""
+        self._dynamic("leave")
+        k = int(k)
+        if not 0 <= k < self.n_sessions or k in self.vacant:
+            _refuse("NerfFeaturePool.leave", f"row {k}: no session there (live rows: {self.live()})")
+        self.vacant.add(k)
 
 
 class NerfASRDeviceFrontend:
@@ -229,7 +317,16 @@ class NerfBatcher:
         """(H, W) of session k's frames"""
         return self.out_shape[k][:2]
 
-    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32, frame_batch=True, torso_batch=False):
+    @staticmethod
+    def session_hw(s):
+        """(H, W) of a session's frames, in the batcher or about to join"""
+        return (int(s.fullbody_frames.shape[1]), int(s.fullbody_frames.shape[2])) if s.fullbody_frames is not None else (s.GH, s.GW)
+
+    def __init__(self, sessions, batch_size=4, pool=None, device="cuda", max_sessions_per_step=None, frames_per_render=32, frame_batch=True, torso_batch=False,
+                 max_sessions=None, max_pixels=None):
+        """max_sessions= (and max_pixels=): sessions come and go (add_session / remove_session).  `sessions`, `enc_a` and `out_shape` are then
+        lists of max_sessions slots, None where vacant, and everything a running step uses is sized by the limits, not by who is here: a head call's frame slots
+        (`_most_frames`), the frame batch (max_pixels rendered pixels per frame; default: the largest initial session) and the feature pool's rows."""
         who = "NerfBatcher"
         self.sessions, self.batch_size, self.pool, self.device = list(sessions), int(batch_size), pool, torch.device(device)
         if not self.sessions:
@@ -239,20 +336,80 @@ class NerfBatcher:
         if int(frames_per_render) < 1:
             _refuse(who, f"frames_per_render {frames_per_render}")
         self.frames_per_render = min(int(frames_per_render), self.MAX_FRAMES_PER_RENDER)
-        self.max_sessions_per_step = len(self.sessions) if max_sessions_per_step is None else int(max_sessions_per_step)
-        if pool is not None and pool.n_sessions != len(self.sessions):
-            _refuse(who, f"a feature pool of {pool.n_sessions} rows for {len(self.sessions)} sessions")
-        self.out_shape = []
-        for k, s in enumerate(self.sessions):
-            hw = (int(s.fullbody_frames.shape[1]), int(s.fullbody_frames.shape[2])) if s.fullbody_frames is not None else (s.GH, s.GW)
-            for t, cycle in s.custom_img_cycle.items():
-                for f in cycle:
-                    if tuple(f.shape[:2]) != hw:
-                        _refuse(who, f"session {k}: custom_img_cycle[{t}] holds a {f.shape[1]} x {f.shape[0]} frame, the session's frames are {hw[1]} x {hw[0]} "
-                                     f"(a step's {self.batch_size} frames leave as one block)")
-            self.out_shape.append(hw + (3,))
-        self.enc_a = [None] * len(self.sessions)
+        self.dynamic = max_sessions is not None or max_pixels is not None
+        n_slots = len(self.sessions) if max_sessions is None else int(max_sessions)
+        if n_slots < len(self.sessions):
+            _refuse(who, f"max_sessions={max_sessions} for {len(self.sessions)} initial sessions")
+        self.max_sessions_per_step = n_slots if max_sessions_per_step is None else int(max_sessions_per_step)
+        if pool is not None and pool.n_sessions != n_slots:
+            _refuse(who, f"a feature pool of {pool.n_sessions} rows for {n_slots} sessions")
         self.frame_batch, self.torso_batch, self._fb = bool(frame_batch), bool(torso_batch), None
+        self.max_pixels = None
+        self.out_shape = [self._check_session(k, s) for k, s in enumerate(self.sessions)]
+        if self.dynamic:
+            most = max((s.H * s.W for s in self.sessions if self._can_frame_batch(s)), default=0)
+            self.max_pixels = most if max_pixels is None else int(max_pixels)
+            if self.max_pixels < most:
+                _refuse(who, f"max_pixels={max_pixels}: an initial session renders {most} pixels per frame")
+        self.sessions += [None] * (n_slots - len(self.sessions))
+        self.out_shape += [None] * (n_slots - len(self.out_shape))
+        self.enc_a = [None] * n_slots
+
+    def _check_session(self, k, s):
+        """what the constructor checks for one session, and add_session for the joiner (slot k), before anything is stored: the custom-video frames have the
+        size of the session's frames, the session can be stepped (the two halves with a model that renders batches, or `step`), and -- where sessions come and
+        go -- its rendered frames fit the frame batch.  Returns the session's output shape."""
+        who = "NerfBatcher"
+        hw = (int(s.fullbody_frames.shape[1]), int(s.fullbody_frames.shape[2])) if s.fullbody_frames is not None else (s.GH, s.GW)
+        for t, cycle in s.custom_img_cycle.items():
+            for f in cycle:
+                if tuple(f.shape[:2]) != hw:
+                    _refuse(who, f"session {k}: custom_img_cycle[{t}] holds a {f.shape[1]} x {f.shape[0]} frame, the session's frames are {hw[1]} x {hw[0]} "
+                                 f"(a step's {self.batch_size} frames leave as one block)")
+        if not self._can_batch(s) and not callable(getattr(s, "step", None)):
+            _refuse(who, f"session {k}: neither begin / end / bind_aabb over a model with render_frames nor step")
+        if self.max_pixels is not None and self.frame_batch and self._can_frame_batch(s) and s.H * s.W > self.max_pixels:
+            _refuse(who, f"session {k}: its frames are rendered at {s.W} x {s.H} = {s.H * s.W} pixels; the frame batch was sized for {self.max_pixels} "
+                         f"(NerfBatcher(..., max_pixels=))")
+        return hw + (3,)
+
+    # ---- sessions that come and go (max_sessions=) ------------------------------------------------------------------------------------------
+    def live(self):
+        """the occupied slot numbers"""
+        return [k for k, s in enumerate(self.sessions) if s is not None]
+
+    def vacant_slot(self):
+        """the slot the next add_session takes: the lowest vacant one.  Refuses a batcher built for a fixed session list, and a full one."""
+        self._check_dynamic("add_session", "makes room for joiners")
+        for k, s in enumerate(self.sessions):
+            if s is None:
+                return k
+        _refuse("NerfBatcher", f"add_session: all {len(self.sessions)} session slots are taken (max_sessions)")
+
+    def _check_dynamic(self, what, gain="lets sessions come and go"):
+        if not self.dynamic:
+            _refuse("NerfBatcher", f"{what}: this batcher was built for a fixed list of sessions; NerfBatcher(..., max_sessions=, max_pixels=) {gain}")
+
+    def add_session(self, session):
+        """A session joins: the lowest vacant slot.  The constructor's checks run for this one session and refuse before anything changes.  Nothing a running
+        step uses is resized and nothing is rendered: a session over a model object that is already here meets no first-time cost; one that brings a new model
+        object pays that model's (handles, workspaces, ray directions of a new size) at its first step, unless the caller ran `prewarm_session(session)` before.
+        The slot's EMA starts at None: a joiner's first frame is not smoothed against a leaver's.  Returns the slot."""
+        k = self.vacant_slot()
+        shape = self._check_session(k, session)
+        self.sessions[k], self.out_shape[k], self.enc_a[k] = session, shape, None
+        return k
+
+    def remove_session(self, k):
+        """Session k leaves: its slot is free for a joiner.  The caller knows that no step still renders it (a scheduler waits for the session's last batch in
+        flight).  Returns the session object."""
+        self._check_dynamic("remove_session")
+        k = int(k)
+        if not 0 <= k < len(self.sessions) or self.sessions[k] is None:
+            _refuse("NerfBatcher", f"remove_session({k}): no session there (live sessions: {self.live()})")
+        s = self.sessions[k]
+        self.sessions[k], self.out_shape[k], self.enc_a[k] = None, None, None
+        return s
 
     def _check_input(self, k, inp):
         B = self.batch_size
@@ -356,7 +513,8 @@ class NerfBatcher:
     def _frame_batch(self):
         if self._fb is None:
             from .nerf_driver import NerfFrameBatch
-            self._fb = NerfFrameBatch(NerfFrameBatch.MAX_FRAMES, max(s.H * s.W for s in self.sessions if self._can_frame_batch(s)))
+            most = self.max_pixels if self.dynamic else max(s.H * s.W for s in self.sessions if self._can_frame_batch(s))
+            self._fb = NerfFrameBatch(NerfFrameBatch.MAX_FRAMES, most)   # (sessions that come and go: sized once, by max_pixels; add_session refuses more)
         return self._fb
 
     def _frame_groups(self, items, key):
@@ -395,7 +553,9 @@ class NerfBatcher:
 
     def _most_frames(self, model):
         """the most frames one head call over `model` can get from this batcher: what its batch handle is sized for at the first call, so that it never has to be
-        rebuilt (a synchronising free of every frame slot) in the serving loop"""
+        rebuilt (a synchronising free of every frame slot) in the serving loop.  Where sessions come and go it does not depend on who is here"""
+        if self.dynamic:
+            return min(self.frames_per_render, self.batch_size * self.max_sessions_per_step)
         n = sum(1 for s in self.sessions if s.model is model and self._can_batch(s))
         return min(self.frames_per_render, self.batch_size * min(n, self.max_sessions_per_step))
 
@@ -409,32 +569,72 @@ class NerfBatcher:
             groups.setdefault(key, []).append((k, b, job))
         return list(groups.values())
 
+    def _prewarm_auds(self, auds, who):
+        if auds is None:
+            if self.pool is None:
+                _refuse(who, "without a feature pool the windows of one frame must be given")
+            auds = torch.zeros((self.pool.HIST if self.pool.att > 0 else 1, self.pool.audio_dim, 16), dtype=torch.float32, device=self.device)
+        return auds
+
+    @staticmethod
+    def _save(s):
+        return (s.index, s.last_index, s.last_audio_index, dict(s.custom_index), s.model.enc_a if hasattr(s.model, "enc_a") else None)
+
+    @staticmethod
+    def _restore(s, keep):
+        s.index, s.last_index, s.last_audio_index = keep[:3]
+        s.custom_index.clear()
+        s.custom_index.update(keep[3])
+        if hasattr(s.model, "enc_a"):
+            s.model.enc_a = keep[4]
+
+    def _prewarm_one(self, s, auds):
+        keep = self._save(s)
+        try:
+            s.step(auds, (0, 0))
+        finally:
+            self._restore(s, keep)
+
+    @torch.no_grad()
+    def prewarm_session(self, session, auds=None):
+        """`prewarm`'s per-session part for a session that is about to join (before add_session, outside the serving loop's step): one rendered frame, and -- for
+        a session that takes the batched route -- one head call of batch_size frames over its model with the frame slots a serving step reserves, so that a
+        model object the batcher has not seen builds its handles here.  The session's state is left as it was; the batcher's is not touched."""
+        auds = self._prewarm_auds(auds, "NerfBatcher.prewarm_session")
+        shape = self._check_session("(joining)", session)
+        self._prewarm_one(session, auds)
+        if self._can_batch(session) and os.environ.get("MF_NERF_BATCH", "1") != "0":
+            B, keep = self.batch_size, self._save(session)
+            frames = torch.empty((B,) + shape, dtype=torch.uint8, device=auds.device)
+            try:
+                jobs = [(b, session.begin(auds, (0, 0), out=frames[b])) for b in range(B)]
+                jobs = [(b, job) for b, job in jobs if isinstance(job, dict) and "custom" not in job]
+                box = [None]
+                for _, job in jobs:
+                    if hasattr(session.model, "enc_a"):
+                        job["ema"] = box
+                session.bind_aabb()
+                res = session.model.render_frames([job for _, job in jobs], reserve_frames=self._most_frames(session.model), **session.render_kw)
+                for (b, job), r in zip(jobs, res):
+                    session.end(job, r["image"], out=frames[b])
+            finally:
+                self._restore(session, keep)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
     @torch.no_grad()
     def prewarm(self, auds=None):
         """One rendered frame per session, so that the serving loop meets no first-time cost (ray directions per size, handles, workspaces).  Session state --
         the loader's position, custom-video counters, the EMA -- is left as it was.  auds: one frame's windows; default: zeros of the pool's shape."""
-        if auds is None:
-            if self.pool is None:
-                _refuse("NerfBatcher.prewarm", "without a feature pool the windows of one frame must be given")
-            auds = torch.zeros((self.pool.HIST if self.pool.att > 0 else 1, self.pool.audio_dim, 16), dtype=torch.float32, device=self.device)
-        def save(s):
-            return (s.index, s.last_index, s.last_audio_index, dict(s.custom_index), s.model.enc_a if hasattr(s.model, "enc_a") else None)
-
-        def restore(s, keep):
-            s.index, s.last_index, s.last_audio_index = keep[:3]
-            s.custom_index.clear()
-            s.custom_index.update(keep[3])
-            if hasattr(s.model, "enc_a"):
-                s.model.enc_a = keep[4]
-        for s in self.sessions:
-            keep = save(s)
-            try:
-                s.step(auds, (0, 0))
-            finally:
-                restore(s, keep)
+        auds = self._prewarm_auds(auds, "NerfBatcher.prewarm")
+        save, restore = self._save, self._restore
+        for k in self.live():
+            self._prewarm_one(self.sessions[k], auds)
+        if self.pool is not None and getattr(self.pool, "scratch", None) is not None:
+            self.pool.warm_state()                                       # (sessions that come and go: the joiners' audio state, computed here and not at a join)
         # ... and whole steps of rendered frames through the batched route, at most max_sessions_per_step sessions each as a serving step has them (the fullest
         # slices first), so that the batch handles exist with their frame slots and every session's size has been through the batched kernels
-        ks = [k for k, s in enumerate(self.sessions) if self._can_batch(s)]
+        ks = [k for k in self.live() if self._can_batch(self.sessions[k])]
         if ks and os.environ.get("MF_NERF_BATCH", "1") != "0":
             B, cap = self.batch_size, max(1, self.max_sessions_per_step)
             inp = (auds.unsqueeze(0).expand(B, *auds.shape), [(0, 0)] * B)
@@ -470,8 +670,53 @@ class NerfEndToEndScheduler(PipelinedScheduler):
         pool = batcher.pool if pool is None else pool
         if not isinstance(pool, NerfFeaturePool) or pool.n_sessions != len(batcher.sessions):     # before anything (streams, the parent's state) is created
             _refuse("NerfEndToEndScheduler", "a NerfFeaturePool with one row per session of the batcher is required")
+        if pool.live() != live_sessions(batcher):
+            _refuse("NerfEndToEndScheduler", f"the pool's live rows {pool.live()} are not the batcher's live sessions {live_sessions(batcher)}")
         super().__init__(batcher, rings=rings, period_s=period_s, hold_s=hold_s, clock=clock, depth=depth, single_stream=single_stream, frame_format=frame_format)
         self.pool = pool
+
+    # ---- sessions that come and go (NerfBatcher(..., max_sessions=) over NerfFeaturePool(..., max_sessions=)) ---------------------------------
+    def _check_join(self, k, session, ring, frontend):
+        """the constructor's checks for the joiner (slot k) and its ring, the batcher's included, before anything is stored anywhere"""
+        who = type(self).__name__
+        if frontend is not None:
+            _refuse(who, "add_session: the audio stage is the feature pool's row of the slot (frontend=None)")
+        self.pool._dynamic("NerfEndToEndScheduler.add_session")
+        if k not in self.pool.vacant:
+            _refuse(who, f"add_session: slot {k} is vacant in the batcher, but row {k} of the feature pool holds a session")
+        hw = self.batcher._check_session(k, session)[:2]
+        super()._check_join(k, session, ring, frontend)                  # (a ring as the scheduler was built; under i420 one of the frames' planes)
+        if ring is not None and self.frame_format == "packed" and tuple(getattr(ring, "frame_shape", ())) != hw + (3,):
+            _refuse(who, f"add_session: ring {k} has slots of shape {tuple(getattr(ring, 'frame_shape', ()))}; session {k}'s {hw[0]} x {hw[1]} frames need "
+                         f"{hw + (3,)} (FrameRing(slots, (H, W, 3)))")
+
+    def add_session(self, session, ring=None, frontend=None):
+        """A client connects: everything is checked first; then row k of the feature pool takes the warmed-up state (NerfFeaturePool.join: one launch on the
+        current stream, no net call, nothing waits) and the session takes slot k of the batcher.  The row was released only after the last batch of whoever
+        held it before had retired (`_drop`), so no step in flight reads what the launch writes.  Returns k."""
+        return super().add_session(session, ring=ring, frontend=frontend)   # (vacant_slot, _check_join, the batcher's add_session, _store: serving.py)
+
+    def _store(self, k, session, ring, frontend):
+        self.pool.join([k])
+        super()._store(k, session, ring, frontend)
+
+    def remove_session(self, k):
+        """serving.SessionScheduler.remove_session; a batcher or a pool built for a fixed list refuses here, before the slot is marked as leaving"""
+        self.batcher._check_dynamic("remove_session")
+        self.pool._dynamic("NerfEndToEndScheduler.remove_session")
+        super().remove_session(k)
+
+    def flush(self, k):
+        """serving.SessionScheduler.flush.  ER-NeRF's features advance when a batch is PICKED, so the audio of a dropped batch never enters the context: the
+        session's next batch continues the windows where the last picked one left them, as if the dropped audio had not been sent (Wav2Lip's window behaves
+        the same way; MuseTalk's slides at submit() and has seen it)."""
+        return super().flush(k)
+
+    def _drop(self, k):
+        """called when the leaver's last batch in flight has retired (`_release_left`): only now may a joiner's launch write row k -- a batch in flight holds
+        its `feats`, but the windows kernel reads non-wrapping windows as views of the ring on later frames of a step that picked the row"""
+        super()._drop(k)
+        self.pool.leave(k)
 
     def submit(self, k, pcm_chunks, t_arrival=None):
         """pcm_chunks: the batch's 2B 20 ms chunks, bare or (chunk, type) pairs (nerfasr.py:60-73; serving.split_batch).  Refused here when malformed."""

@@ -399,6 +399,36 @@ def nerf_feat_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
     return out
 
 
+def nerf_feat_rows_load(rings, hist, rows, src_ring=None, src_hist=None):
+    """A session joins, starts again or is reset (mf_nerf_feat_rows_load): rows `rows` (a host list) of rings [N, R, dim] are written from src_ring [R, dim]
+    and, where hist [N, 8, dim, 16] is not None, of hist from src_hist [8, dim, 16]; a source of None writes zeros.  ONE launch for all rows; a source may be a
+    view of another row of the same tensors, not of a named one.  In place; returns nothing."""
+    _require_cuda("nerf_feat_rows_load", rings)
+    if rings.dim() != 3:
+        raise RuntimeError(f"nerf_feat_rows_load: rings must be [N, R, dim], got {tuple(rings.shape)}")
+    N, R, dim = rings.shape
+    _fp32_pool("nerf_feat_rows_load", "rings", rings, (R, dim))
+    if hist is None and src_hist is not None:
+        raise RuntimeError("nerf_feat_rows_load: a history source without a history (att == 0 keeps none)")
+    if hist is not None:
+        _require_cuda("nerf_feat_rows_load", hist)
+        _fp32_pool("nerf_feat_rows_load", "hist", hist, (8, dim, 16))
+        if hist.shape[0] != N:
+            raise RuntimeError(f"nerf_feat_rows_load: {hist.shape[0]} histories for {N} rings")
+    for what, src, shape in (("src_ring", src_ring, (R, dim)), ("src_hist", src_hist, (8, dim, 16))):
+        if src is None:
+            continue
+        _require_cuda("nerf_feat_rows_load", src)
+        if not (src.dtype == torch.float32 and src.is_contiguous() and tuple(src.shape) == shape and src.device == rings.device):
+            raise RuntimeError(f"nerf_feat_rows_load: {what} must be a contiguous fp32 tensor {shape} on {rings.device}, got {src.dtype} {tuple(src.shape)} on "
+                               f"{src.device}")
+    crows, S = _ints(rows)
+    with torch.cuda.device(rings.device):
+        _lib.check(_lib.lib().mf_nerf_feat_rows_load(rings.data_ptr(), None if hist is None else hist.data_ptr(), N, R, dim, S, crows,
+                                                     None if src_ring is None else src_ring.data_ptr(), None if src_hist is None else src_hist.data_ptr(),
+                                                     _lib.stream_ptr(rings.device)), "nerf_feat_rows_load")
+
+
 # ---- MuseTalk / Whisper stages as custom ops too (the drop-in modules call these; handles are the C ABI's opaque pointers) ----------
 @torch.library.custom_op("merefusion::unet_forward", mutates_args=())
 def unet_forward(handle: int, latents: torch.Tensor, audio: torch.Tensor, add_pe: bool, out_channels: int) -> torch.Tensor:

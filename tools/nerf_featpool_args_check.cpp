@@ -1,4 +1,4 @@
-// Stand-alone host check of the argument validation of mf_nerf_feat_scatter and mf_nerf_feat_windows: every call below must be refused with MF_ERR_INVALID
+// Stand-alone host check of the argument validation of mf_nerf_feat_scatter, mf_nerf_feat_windows and mf_nerf_feat_rows_load: every call below must be refused with MF_ERR_INVALID
 // before anything touches a device, so the program runs on a box without a GPU -- built with the host side under AddressSanitizer + UBSan:
 //
 //   for f in mere-fusion_amd/csrc/mf_nerf_featpool.hip mere-fusion_amd/csrc/mf_api.cpp tools/nerf_featpool_args_check.cpp; do
@@ -88,6 +88,33 @@ int main() {
     std::vector<int> f0{3, 5}, nn0{1, 4}, one{1, 1}, fneg{3, -1};
     expect(windows(p, nullptr, N, R, 1024, 2, rows.data(), f0.data(), nullptr, nn0.data(), 0, p), "without attention", "windows att = 0, n_new = 4");
     expect(windows(p, nullptr, N, R, 1024, 2, rows.data(), fneg.data(), nullptr, one.data(), 0, p), "front", "windows att = 0, front = -1");
+
+    // mf_nerf_feat_rows_load: a pool of N = 3 rows as ONE host array with a fourth (scratch) row behind them, so that the overlap checks meet real addresses
+    const int dim = 44, ring_row = R * dim, hist_row = 8 * dim * 16;
+    alignas(16) static float rings[4 * 32 * 44], hist[4 * 8 * 44 * 16];
+    auto load = [&](float* rg, float* hs, int n, int r, int d, int S, const int* rw, const float* sr, const float* sh) {
+        return mf_nerf_feat_rows_load(rg, hs, n, r, d, S, rw, sr, sh, nullptr);
+    };
+    const float *sr = rings + 3 * ring_row, *sh = hist + 3 * hist_row;
+    expect(load(nullptr, hist, N, R, dim, 2, rows.data(), sr, sh), "null", "rows_load rings = NULL");
+    expect(load(rings, hist, N, R, dim, 2, nullptr, sr, sh), "null", "rows_load rows = NULL");
+    expect(load(rings, nullptr, N, R, dim, 2, rows.data(), sr, sh), "null history", "rows_load src_hist without hist");
+    for (int d : {0, -1, 1025, 1 << 30}) expect(load(rings, hist, N, R, d, 2, rows.data(), sr, sh), "dim", "rows_load dim outside 1..1024");
+    for (int r : {15, 0, -32, 1 << 30, 18}) expect(load(rings, hist, N, r, dim, 2, rows.data(), sr, sh), "ring", "rows_load R outside 16..65536 or no 4 * m");
+    for (int n : {0, -1, 1 << 30}) expect(load(rings, hist, n, R, dim, 2, rows.data(), sr, sh), "pool", "rows_load N outside 1..65536");
+    for (int S : {0, -2, 4, 1 << 30}) expect(load(rings, hist, N, R, dim, S, rows.data(), sr, sh), "picked", "rows_load n_rows outside 1..N (2 readable)");
+    for (int b : {-1, 3, 1 << 30}) {
+        std::vector<int> r{0, b};
+        expect(load(rings, hist, N, R, dim, 2, r.data(), sr, sh), "out of range", "rows_load row outside the pool");
+    }
+    expect(load(rings, hist, N, R, dim, 2, twice.data(), sr, sh), "twice", "rows_load a row twice");
+    expect(load(rings + 1, hist, N, R, dim, 2, rows.data(), sr, sh), "aligned", "rows_load rings off a 16-byte boundary");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), sr + 2, sh), "aligned", "rows_load src_ring off a 16-byte boundary");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), rings + 2 * ring_row, sh), "ring source overlaps", "rows_load src_ring is named row 2");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), rings + 2 * ring_row - 4, sh), "ring source overlaps", "rows_load src_ring ends inside row 2");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), rings + ring_row - 4, sh), "ring source overlaps", "rows_load src_ring starts inside row 0");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), sr, hist), "history source overlaps", "rows_load src_hist is named row 0");
+    expect(load(rings, hist, N, R, dim, 2, rows.data(), sr, hist + 3 * hist_row - 4), "history source overlaps", "rows_load src_hist starts inside row 2");
     std::printf(failures ? "%d FAILED\n" : "all refused as expected (%d failures)\n", failures);
     return failures ? 1 : 0;
 }
