@@ -214,6 +214,8 @@ struct ConvPlan {
     // binding-dependent (built by mf_conv_bind)
     int bound_in_ld = -1, bound_in_wp = -1;
     std::map<int, ConvTuned> tuned;           // batch -> configuration measured on this device (mf_conv_tune); empty: the cost model decides
+    int pick_batch = 0;                       // > 0: the implicit GEMM's tile, split-K depth and operand path are those of THIS batch whatever batch launches, so a
+                                              // sample's result does not depend on how many samples share the call (mf_wav2vec2: the handle's window capacity)
 };
 
 // the shortest phase's K tiles: a split deeper than this cannot launch

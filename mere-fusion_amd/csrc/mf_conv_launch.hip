@@ -71,14 +71,15 @@ int mf_conv_resolve(const ConvPlan* p, int batch, int tokens, int stats_groups, 
     }
     // ---- implicit GEMM
     const bool x3 = p->precision != MF_PREC_BF16;
-    ConvTile tc = mf_conv_pick_tile(p, batch);
+    const int pick = p->pick_batch > 0 ? p->pick_batch : batch;   // (ConvPlan::pick_batch: one K summation order for every batch a handle serves)
+    ConvTile tc = mf_conv_pick_tile(p, pick);
     int ld = -1;
     const ConvForce& force = mf_conv_force();
-    auto it = p->tuned.find(batch);
+    auto it = p->tuned.find(pick);
     if (it != p->tuned.end()) { ld = it->second.ld; c->pinned = !force.any; }
     if (force.ld >= 0 && !(force.ld >= 3 && (!x3 || p->q || tc.wgm * tc.wgn != 4 || tc.bn < 64 || tc.bm < 64))) ld = force.ld;   // (measurement, with MF_FORCE_TILE / MF_FORCE_SPLIT)
     const int Wq_eff = tokens > 0 ? tokens : p->Wq;
-    const int M = batch * p->Hq * Wq_eff;
+    const int M = pick * p->Hq * Wq_eff;
     if (tokens > 0) {
         // the cost model priced the full sequence: re-balance the split for the rows actually computed
         const int nt = cdiv(M, tc.bm) * cdiv(p->d.cout, tc.bn);

@@ -334,6 +334,10 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         if ((rc = mf_conv_bind(h->head, *h->xb))) return rc;
         h->vocab_pad = vp;
     }
+    // One configuration per layer for every window count the handle serves: the cost model picks tile and split-K depth from windows x frames, and another split
+    // sums the fp32 partials in another order -- on a one-frame window that moved a window's logits by 4e-5 between a call of its own and a call shared with three
+    // others.  Picked for the capacity, a window's logits are the same bits in any company.
+    for (auto& p : h->plans) p->pick_batch = max_windows;
     *out = h.release();
     return MF_OK;
 }

@@ -119,3 +119,74 @@ def test_oracle_melspectrogram_matches_transformers_spectrogram():
     got = mel_ref.melspectrogram(wav, "constant")
     assert got.shape == want.shape == (80, 84)
     np.testing.assert_allclose(got, want, rtol=0, atol=1e-5)
+
+
+# ---- edge lengths, floor signals, the windows kernel ----------------------------------------------------------------------------------------
+# (what each signal covers is pinned on the oracle alone in test_audio_frontend_ref.py)
+import audio_frontend_ref as A                                                    # noqa: E402
+from mere_fusion_amd import weights as W                                          # noqa: E402
+from audio_frontend_ref import MEL_SHARES, MEL_SIGNAL_N, mel_signal               # noqa: E402
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,modes", [(n, ("constant", "reflect")) for n in (401, 599, 600, 601, 1000)] + [(n, ("constant",)) for n in (1, 199, 200, 399, 400)])
+def test_hip_mel_edge_lengths(lib_built, n, modes):
+    """401: the shortest signal reflect padding takes (frame 0 reflects to sample 400); 399 / 400 and 599 / 600 / 601: where 1 + n // 200 steps; 1 and 199: a
+    single frame.  Loud at both ends, so either padding shows in the first and the last frames."""
+    from mere_fusion_amd import ops
+    from mere_fusion_amd.wav2lip import audio
+    for w in (W.make_speech_like_wav(n, n), A.burst_silence_hiss(n, 1.0)):
+        for mode in modes:
+            want = mel_ref.melspectrogram(w, mode)
+            got = ops.melspec(torch.from_numpy(w).cuda(), audio.PAD_MODES[mode]).cpu().numpy()
+            assert got.shape == want.shape == (80, 1 + n // 200)
+            err = np.abs(got - want).max()
+            print(f"[mel] n {n} {mode}: L-inf vs oracle {err:.2e}")
+            assert err <= 1e-5, (mode, err)
+    if n == 400:
+        with pytest.raises(RuntimeError, match="reflect"):
+            ops.melspec(torch.zeros(400).cuda(), audio.PAD_MODES["reflect"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(MEL_SHARES))
+@pytest.mark.parametrize("mode", ["constant", "reflect"])
+def test_hip_mel_floor_signals(lib_built, name, mode):
+    """the 1e-5 floor decides 55 % (burst) and 95 % (burst at 1e-3) of the cells; the rest lie strictly inside.  No case at +4: no signal with |x| <= 1
+    gets there (test_mel_plus_four_is_out_of_reach_of_a_full_scale_signal); loud_tone is the loudest the kernel is shown, 3.46."""
+    from mere_fusion_amd import ops
+    from mere_fusion_amd.wav2lip import audio
+    w = mel_signal(name, MEL_SIGNAL_N)
+    want = mel_ref.melspectrogram(w, mode)
+    got = ops.melspec(torch.from_numpy(w).cuda(), audio.PAD_MODES[mode]).cpu().numpy()
+    err, lo, inside = np.abs(got - want).max(), float((got == -4.0).mean()), float(((got > -4.0) & (got < 4.0)).mean())
+    print(f"[mel] {name} {mode}: L-inf vs oracle {err:.2e}; at -4: oracle {(want == -4.0).mean():.3f}, kernel {lo:.3f}; inside {inside:.3f}; max {got.max():.3f}")
+    assert err <= 1e-5
+    assert lo >= MEL_SHARES[name][0] and inside >= MEL_SHARES[name][1] and (got == 4.0).sum() == 0
+    assert np.abs(got[want == -4.0] + 4.0).max(initial=0.0) <= 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["constant", "reflect"])
+def test_hip_mel_windows_rows_gap_and_last_start(lib_built, mode):
+    """rows [loud, quiet, zeros] in one launch: every chunk is bit-equal to the row's own ops.melspec.  Starts 0, 1 (overlapping chunks: a frame stored twice),
+    40 (frames 17..39 are computed and stored nowhere) and T - 16 (the last frame of the signal).  The output lies inside a larger sentinel-filled
+    buffer: every element of it is overwritten, nothing around it is."""
+    from mere_fusion_amd import ops
+    from mere_fusion_amd.wav2lip import audio
+    n, T = 16640, 84
+    wav = torch.from_numpy(np.stack([A.loud_tone(n), A.burst_silence_hiss(n, 1e-3), np.zeros(n, np.float32)])).cuda()
+    starts = [0, 1, 40, T - 16]
+    numel, guard, sentinel = 3 * len(starts) * 80 * 16, 4096, -777.0
+    big = torch.full((guard + numel + guard,), sentinel, device="cuda")
+    out = big[guard:guard + numel].view(3 * len(starts), 1, 80, 16)
+    res = ops.melspec_windows(wav, starts, audio.PAD_MODES[mode], out=out)
+    torch.cuda.synchronize()
+    assert res.data_ptr() == out.data_ptr()
+    assert (big[:guard] == sentinel).all() and (big[guard + numel:] == sentinel).all()
+    assert (out != sentinel).all()
+    for r in range(3):
+        full = ops.melspec(wav[r], audio.PAD_MODES[mode])
+        for i, s in enumerate(starts):
+            assert torch.equal(out[r * len(starts) + i, 0], full[:, s:s + 16]), (r, s)
+    assert (out[2 * len(starts):] == -4.0).all()

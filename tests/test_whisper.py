@@ -166,3 +166,78 @@ def test_hip_windowed_context_is_an_approximation_and_says_so(a2f, wsd):
 def test_hip_long_audio_is_refused(a2f):
     with pytest.raises(RuntimeError, match="30 s"):
         a2f.audio2feat(np.zeros(480000 + 320, np.float32))
+
+
+# ---- floors, per-window maximum, stale state: against the float64 model of tests/audio_frontend_ref.py ------------------------------------
+# (the float32 oracle drifts where the floor decides the value; what each signal covers is pinned on the model alone in test_audio_frontend_ref.py)
+import audio_frontend_ref as A                                                    # noqa: E402
+from audio_frontend_ref import WHISPER_DYN_SHARE, WHISPER_LENGTHS, WHISPER_POW_SHARE         # noqa: E402
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", WHISPER_LENGTHS)
+def test_hip_log_mel_floor_cases(a2f, n):
+    """201: one frame; 320 / 479 / 480: two or three frames, all of them touching an end; every length above 200 takes the left reflect branch, 320, 480,
+    1600 and 3200 the right one too.  gain 1: `max - 8` decides 30-74 % of the cells from 480 samples on; gain 1e-3: the 1e-10 floor does and the window
+    maximum is negative; zeros: every cell at the power floor, maximum -10."""
+    cases = [("gain 1", A.burst_silence_hiss(n, 1.0), WHISPER_DYN_SHARE[n]), ("gain 1e-3", A.burst_silence_hiss(n, 1e-3), WHISPER_POW_SHARE[n]),
+             ("zeros", np.zeros(n, np.float32), 1.0), ("speech-like", W.make_speech_like_wav(n, 0), 0.0)]
+    for name, wav, share in cases:
+        got = a2f.log_mel_spectrogram(wav).cpu().numpy()
+        want = A.whisper_log_mel_f64(wav)
+        assert got.shape == want.shape == (80, n // 160)
+        err = np.abs(got - want).max()
+        floored = want == want.min()
+        at_floor = float((got == got.min()).mean()) if share else 0.0
+        print(f"[whisper log-mel] n {n} {name}: L-inf vs float64 model {err:.2e}; at the floor: model {floored.mean() if share else 0.0:.3f}, kernel {at_floor:.3f}")
+        assert np.isfinite(got).all() and err <= TOL_LOGMEL, (name, err)
+        if share:
+            assert floored.mean() >= share and at_floor >= share, (name, floored.mean(), at_floor)
+            assert np.abs(got[floored] - want.min()).max() <= TOL_LOGMEL, name
+    assert (a2f.log_mel_spectrogram(np.zeros(n, np.float32)).cpu().numpy() == -1.5).all()
+
+
+_window_refs = {}
+
+
+def _window_case(wsd, n):
+    """the four windows of a batched call and the reference's features of each, computed once per length"""
+    if n not in _window_refs:
+        wavs = np.stack([A.burst_silence_hiss(n, 1.0), A.burst_silence_hiss(n, 1e-3), np.zeros(n, np.float32), W.make_speech_like_wav(n, 0)])
+        _window_refs[n] = wavs, [A.whisper_features(wsd, w) for w in wavs]
+    return _window_refs[n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [3200, 11520])
+def test_hip_per_window_maximum(a2f, wsd, n):
+    """Four windows whose maxima differ (1.66, -4.34, -10, 0.44) in ONE call: each row is its own single-window call and the reference on the float64
+    log-mel.  With window 0's maximum window 1's features would move by ~3 (test_whisper_window_maximum_mixup_moves_the_features)."""
+    wavs, wants = _window_case(wsd, n)
+    a2f.set_mode("exact")
+    bat = a2f.audio2feat_windows_device(torch.from_numpy(wavs)).cpu().numpy()
+    assert bat.shape == (4, n // 320, 5, 384) and np.isfinite(bat).all()
+    for i in range(4):
+        one = a2f.audio2feat(wavs[i])
+        e1, e2 = np.abs(bat[i] - one).max(), np.abs(bat[i] - wants[i]).max()
+        print(f"[whisper windows] n {n} window {i}: vs its single call {e1:.2e}, vs the reference {e2:.2e}")
+        assert e1 <= 2e-4, (i, e1)
+        assert e2 <= TOL_FEAT, (i, e2)
+
+
+@pytest.mark.gpu
+def test_hip_whisper_no_stale_state(lib_built, wsd):
+    """A short quiet window after a long loud one, and again after set_batch regrew the workspace, gives the bits of a fresh handle: the frames past the
+    window's end and the window maximum (here negative, after a positive one) are reset by every call."""
+    from mere_fusion_amd.musetalk.whisper.audio2feature import Audio2Feature
+    short, long_ = A.burst_silence_hiss(1600, 1e-3), W.make_speech_like_wav(16640, 1)
+    fresh = Audio2Feature(state_dict=wsd, n_head=6, precision="bf16x3")
+    want_mel, want = fresh.log_mel_spectrogram(short).cpu(), fresh.audio2feat_device(short).cpu()
+    used = Audio2Feature(state_dict=wsd, n_head=6, precision="bf16x3")
+    used.audio2feat_device(long_)
+    assert torch.equal(used.audio2feat_device(short).cpu(), want)
+    used.log_mel_spectrogram(long_)
+    assert torch.equal(used.log_mel_spectrogram(short).cpu(), want_mel)
+    used.audio2feat_windows_device(torch.from_numpy(np.stack([long_, long_[::-1].copy(), long_ * 0.5])))      # set_batch(3): the workspace is reallocated
+    assert torch.equal(used.audio2feat_device(short).cpu(), want)
+    assert torch.equal(used.log_mel_spectrogram(short).cpu(), want_mel)
