@@ -315,17 +315,18 @@ int axis_taps(int filter, int in, int out) {
 // call run one behind the other on the stream, so they share the block.
 struct ChunkLayout { size_t tab_bytes, inter_bytes, pre_bytes, tmp_bytes, taps_bytes, total; };
 
+// first: index of the chunk's first job in the call, so that a refusal names the call's job.
 // sizes: [n][2] (box width, box height); out_w / out_h: the fixed output size (parse), or <= 0: the output is the box and the source is src_w x src_h (finish)
-int chunk_layout(const char* who, int finish, const int* sizes, int n, int S_h, int S_w, int channels, ChunkLayout& L, FmJob* jobs) {
+int chunk_layout(const char* who, int first, int finish, const int* sizes, int n, int S_h, int S_w, int channels, ChunkLayout& L, FmJob* jobs) {
     size_t tab = 0, inter = 0, pre = 0, tmp = 0;
     const int filter = finish ? 1 : 0;
     for (int i = 0; i < n; ++i) {
         const int bw = sizes[2 * i], bh = sizes[2 * i + 1];
-        MF_REQUIRE(bw >= 1 && bh >= 1 && bw <= 16384 && bh <= 16384, "%s: job %d: box %d x %d outside [1, 16384]", who, i, bw, bh);
+        MF_REQUIRE(bw >= 1 && bh >= 1 && bw <= 16384 && bh <= 16384, "%s: job %d: box %d x %d outside [1, 16384]", who, first + i, bw, bh);
         FmAxis ax{finish ? S_w : bw, finish ? bw : S_w, 0, 0}, ay{finish ? S_h : bh, finish ? bh : S_h, 0, 0};
         ax.taps = axis_taps(filter, ax.in, ax.out); ay.taps = axis_taps(filter, ay.in, ay.out);
         MF_REQUIRE(ax.taps <= MF_FM_MAX_TAPS && ay.taps <= MF_FM_MAX_TAPS,
-                   "%s: job %d: resampling %d x %d to %d x %d needs %d taps per pixel, the limit is MF_FM_MAX_TAPS = %d", who, i, ax.in, ay.in, ax.out, ay.out,
+                   "%s: job %d: resampling %d x %d to %d x %d needs %d taps per pixel, the limit is MF_FM_MAX_TAPS = %d", who, first + i, ax.in, ay.in, ax.out, ay.out,
                    ax.taps > ay.taps ? ax.taps : ay.taps, MF_FM_MAX_TAPS);
         ax.off = (int)(tab / sizeof(int)); tab += (size_t)ax.out * (2 + ax.taps) * sizeof(int);
         ay.off = (int)(tab / sizeof(int)); tab += (size_t)ay.out * (2 + ay.taps) * sizeof(int);
@@ -336,7 +337,7 @@ int chunk_layout(const char* who, int finish, const int* sizes, int n, int S_h, 
         if (ax.in != ax.out) inter += align256((size_t)ay.in * ax.out * channels);
         if (finish) {
             const int k = blur_kernel_size(bw);
-            MF_REQUIRE(k <= MF_FM_BLUR_MAX_K, "%s: job %d: a %d-pixel-wide mask needs a %d-tap blur, the LDS tiles hold MF_FM_BLUR_MAX_K = %d taps", who, i, bw, k,
+            MF_REQUIRE(k <= MF_FM_BLUR_MAX_K, "%s: job %d: a %d-pixel-wide mask needs a %d-tap blur, the LDS tiles hold MF_FM_BLUR_MAX_K = %d taps", who, first + i, bw, k,
                        MF_FM_BLUR_MAX_K);
             pre += align256((size_t)bw * bh);
             tmp += align256((size_t)bw * bh * sizeof(float));
@@ -358,7 +359,7 @@ extern "C" size_t mf_face_mask_workspace_bytes(int finish, const int* box_sizes,
     for (int j0 = 0; j0 < n_jobs; j0 += MF_FM_MAX_JOBS) {
         ChunkLayout L{};
         const int nj = n_jobs - j0 < MF_FM_MAX_JOBS ? n_jobs - j0 : MF_FM_MAX_JOBS;
-        if (chunk_layout("face_mask_workspace_bytes", finish, box_sizes + 2 * j0, nj, mask_h, mask_w, finish ? 1 : 3, L, nullptr)) return 0;
+        if (chunk_layout("face_mask_workspace_bytes", j0, finish, box_sizes + 2 * j0, nj, mask_h, mask_w, finish ? 1 : 3, L, nullptr)) return 0;
         if (L.total > need) need = L.total;
     }
     return need;
@@ -377,22 +378,35 @@ extern "C" int mf_face_mask_parse(mf_net* net, int in_buf, int head_buf, int n_c
     MF_REQUIRE(n_classes >= 14 && n_classes <= hb->C, "face_mask_parse: %d classes do not fit the head buffer's %d channels (classes 1..13 are the mask)", n_classes, hb->C);
     hipStream_t s = (hipStream_t)stream;
     int sizes[2 * MF_FM_MAX_JOBS];
+    size_t need = 0;                           // the largest chunk's workspace, as mf_face_mask_workspace_bytes reports it
+    // Every refusal is decided before the first launch: a job refused in a later chunk must not leave the earlier chunks' input planes written.
     for (int j0 = 0; j0 < n_jobs; j0 += MF_FM_MAX_JOBS) {
         const int nj = n_jobs - j0 < MF_FM_MAX_JOBS ? n_jobs - j0 : MF_FM_MAX_JOBS;
-        FmArgs a{};
         for (int i = 0; i < nj; ++i) {
             const int* q = jobs + 5 * (j0 + i);
             MF_REQUIRE(q[0] >= 0 && q[0] < n_frames, "face_mask_parse: job %d: frame index %d out of range (%d frames)", j0 + i, q[0], n_frames);
             MF_REQUIRE(q[3] > q[1] && q[4] > q[2], "face_mask_parse: job %d: crop box (%d, %d, %d, %d) is empty", j0 + i, q[1], q[2], q[3], q[4]);
             MF_REQUIRE(q[1] > -(1 << 20) && q[2] > -(1 << 20) && q[3] < (1 << 20) && q[4] < (1 << 20), "face_mask_parse: job %d: crop box coordinate beyond 2^20", j0 + i);
+            sizes[2 * i] = q[3] - q[1]; sizes[2 * i + 1] = q[4] - q[2];
+        }
+        ChunkLayout L{};
+        int rc = chunk_layout("face_mask_parse", j0, 0, sizes, nj, ib->H, ib->W, 3, L, nullptr);
+        if (rc) return rc;
+        if (L.total > need) need = L.total;
+    }
+    MF_REQUIRE(need <= workspace_bytes, "face_mask_parse: the workspace holds %zu bytes, %zu are needed (mf_face_mask_workspace_bytes)", workspace_bytes, need);
+    for (int j0 = 0; j0 < n_jobs; j0 += MF_FM_MAX_JOBS) {
+        const int nj = n_jobs - j0 < MF_FM_MAX_JOBS ? n_jobs - j0 : MF_FM_MAX_JOBS;
+        FmArgs a{};
+        for (int i = 0; i < nj; ++i) {
+            const int* q = jobs + 5 * (j0 + i);
             FmJob& j = a.job[i];
             j.src = q[0]; j.bx = q[1]; j.by = q[2]; j.bw = q[3] - q[1]; j.bh = q[4] - q[2]; j.slot = j0 + i;
             sizes[2 * i] = j.bw; sizes[2 * i + 1] = j.bh;
         }
         ChunkLayout L{};
-        int rc = chunk_layout("face_mask_parse", 0, sizes, nj, ib->H, ib->W, 3, L, a.job);
-        if (rc) return rc;
-        MF_REQUIRE(L.total <= workspace_bytes, "face_mask_parse: the workspace holds %zu bytes, %zu are needed (mf_face_mask_workspace_bytes)", workspace_bytes, L.total);
+        int rc = chunk_layout("face_mask_parse", j0, 0, sizes, nj, ib->H, ib->W, 3, L, a.job);
+        if (rc) return rc;                     // (accepted above)
         a.src = frames; a.SH = H; a.SW = W; a.rev = reverse_channels ? 1 : 0; a.filter = 0;
         a.tab = (int*)workspace; a.inter = (uint8_t*)workspace + L.tab_bytes; a.out = nullptr;
         a.hi = ib->hi; a.lo = ib->lo; a.halo = ib->halo; a.NH = ib->H; a.NW = ib->W;
@@ -425,25 +439,38 @@ extern "C" int mf_face_mask_finish(const uint8_t* masks, int mask_h, int mask_w,
     MF_REQUIRE(mask_h >= 1 && mask_w >= 1 && n_jobs >= 1, "face_mask_finish: bad size");
     hipStream_t s = (hipStream_t)stream;
     int sizes[2 * MF_FM_MAX_JOBS];
-    int64_t packed = 0;                        // job i's mask starts where job i - 1's ended, in `out` and in `pre_blur`
+    size_t need = 0;                           // the largest chunk's workspace, as mf_face_mask_workspace_bytes reports it
+    // Every refusal is decided before the first launch: a job refused in a later chunk must not leave the earlier chunks' masks written.
     for (int j0 = 0; j0 < n_jobs; j0 += MF_FM_MAX_JOBS) {
         const int nj = n_jobs - j0 < MF_FM_MAX_JOBS ? n_jobs - j0 : MF_FM_MAX_JOBS;
-        FmArgs a{};
         for (int i = 0; i < nj; ++i) {
             const int* q = jobs + 7 * (j0 + i);
             const int w = q[0], h = q[1];
             MF_REQUIRE(w >= 1 && h >= 1, "face_mask_finish: job %d: empty crop %d x %d", j0 + i, w, h);
             MF_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[4] <= w && q[5] <= h && q[4] >= q[2] && q[5] >= q[3],
                        "face_mask_finish: job %d: the face-box rectangle (%d, %d, %d, %d) must lie inside the %d x %d crop", j0 + i, q[2], q[3], q[4], q[5], w, h);
-            FmJob& j = a.job[i];
-            j.src = j0 + i; j.bx = 0; j.by = 0; j.bw = mask_w; j.bh = mask_h;
-            j.rx0 = q[2]; j.ry0 = q[3]; j.rx1 = q[4]; j.ry1 = q[5]; j.top = q[6];
             sizes[2 * i] = w; sizes[2 * i + 1] = h;
         }
         ChunkLayout L{};
-        int rc = chunk_layout("face_mask_finish", 1, sizes, nj, mask_h, mask_w, 1, L, a.job);
+        int rc = chunk_layout("face_mask_finish", j0, 1, sizes, nj, mask_h, mask_w, 1, L, nullptr);
         if (rc) return rc;
-        MF_REQUIRE(L.total <= workspace_bytes, "face_mask_finish: the workspace holds %zu bytes, %zu are needed (mf_face_mask_workspace_bytes)", workspace_bytes, L.total);
+        if (L.total > need) need = L.total;
+    }
+    MF_REQUIRE(need <= workspace_bytes, "face_mask_finish: the workspace holds %zu bytes, %zu are needed (mf_face_mask_workspace_bytes)", workspace_bytes, need);
+    int64_t packed = 0;                        // job i's mask starts where job i - 1's ended, in `out` and in `pre_blur`
+    for (int j0 = 0; j0 < n_jobs; j0 += MF_FM_MAX_JOBS) {
+        const int nj = n_jobs - j0 < MF_FM_MAX_JOBS ? n_jobs - j0 : MF_FM_MAX_JOBS;
+        FmArgs a{};
+        for (int i = 0; i < nj; ++i) {
+            const int* q = jobs + 7 * (j0 + i);
+            FmJob& j = a.job[i];
+            j.src = j0 + i; j.bx = 0; j.by = 0; j.bw = mask_w; j.bh = mask_h;
+            j.rx0 = q[2]; j.ry0 = q[3]; j.rx1 = q[4]; j.ry1 = q[5]; j.top = q[6];
+            sizes[2 * i] = q[0]; sizes[2 * i + 1] = q[1];
+        }
+        ChunkLayout L{};
+        int rc = chunk_layout("face_mask_finish", j0, 1, sizes, nj, mask_h, mask_w, 1, L, a.job);
+        if (rc) return rc;                     // (accepted above)
         uint8_t* ws = (uint8_t*)workspace;
         a.src = masks; a.SH = mask_h; a.SW = mask_w; a.rev = 0; a.filter = 1;
         a.tab = (int*)ws; a.inter = ws + L.tab_bytes;

@@ -89,14 +89,15 @@ def get_crop_box(box, expand):
     return [x_c - s, y_c - s, x_c + s, y_c + s], s
 
 
-def window(mask, face_box, crop_box, upper_boundary_ratio=0.5):
-    """blending.py:74-82 on the crop-size mask: zero outside the face-box rectangle and above top_boundary"""
+def window(mask, face_box, crop_box, upper_boundary_ratio=0.5, top=None):
+    """blending.py:74-82 on the crop-size mask: zero outside the face-box rectangle and above top_boundary (top: the boundary row itself, where a test sets one that
+    no ratio gives)"""
     x, y, x1, y1 = face_box
     x_s, y_s = crop_box[:2]
     h, w = mask.shape
     out = np.zeros_like(mask)
     out[y - y_s:y1 - y_s, x - x_s:x1 - x_s] = mask[y - y_s:y1 - y_s, x - x_s:x1 - x_s]
-    out[:int(h * upper_boundary_ratio)] = 0
+    out[:int(h * upper_boundary_ratio) if top is None else top] = 0
     return out
 
 
@@ -111,11 +112,25 @@ def gaussian_taps(k):
     return t / t.sum()
 
 
-def gaussian_blur(mask, k):
-    """float64 [h, w], not rounded"""
+def reflect101(i, n):
+    """BORDER_REFLECT_101 as the loop `while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i` states it, for an integer array i: bounces as often as needed"""
+    i = np.array(i, dtype=np.int64)
+    if n == 1:
+        return np.zeros_like(i)
+    while ((i < 0) | (i >= n)).any():
+        i = np.where(i < 0, -i, np.where(i >= n, 2 * n - 2 - i, i))
+    return i
+
+
+def gaussian_blur(mask, k, index=None):
+    """float64 [h, w], not rounded.  index(i, n): the border rule as a function of an index array and the axis length, in place of numpy's padding (reflect101 gives
+    the same image; a test hands in a deliberately different rule to show that its comparison notices)"""
     taps, r = gaussian_taps(k), k // 2
-    a = np.pad(mask.astype(np.float64), r, mode="reflect")       # numpy's "reflect" is BORDER_REFLECT_101
     h, w = mask.shape
+    if index is None:
+        a = np.pad(mask.astype(np.float64), r, mode="reflect")   # numpy's "reflect" is BORDER_REFLECT_101
+    else:
+        a = mask.astype(np.float64)[index(np.arange(-r, h + r), h)][:, index(np.arange(-r, w + r), w)]
     tmp = sum(taps[t] * a[:, t:t + w] for t in range(k))
     return sum(taps[t] * tmp[t:t + h, :] for t in range(k))
 

@@ -201,6 +201,59 @@ def test_hip_muse_blend_bit_exact(lib_built):
     assert np.array_equal(av.frames.cpu().numpy(), frames)            # the cache is never written (copy.deepcopy, musereal.py:237)
 
 
+def _border_boxes(H, W, w=23, h=19):
+    """(x1, y1, x2, y2): the bbox flush with the frame, and one in each corner"""
+    return [(0, 0, W, H), (0, 0, w, h), (W - w, 0, W, h), (0, H - h, w, H), (W - w, H - h, W, H)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W", [60, 61, 63])
+def test_hip_lip_paste_at_the_frame_border(lib_built, W):
+    """the bbox flush with the frame and in each corner; W % 4 = 0, 1, 3: the 12-byte row path and the bytewise one (whole rows, and the last group of a row) meet
+    x = 0 and x = W - 1"""
+    from mere_fusion_amd.paste import AvatarFrames
+    H = 50
+    rng = np.random.default_rng(30 + W)
+    boxes = _border_boxes(H, W)
+    frames = rng.integers(0, 256, (len(boxes), H, W, 3), dtype=np.uint8)
+    res = (rng.random((len(boxes), 96, 96, 3)) * 255).astype(np.float32)
+    av = AvatarFrames(frames, [(y1, y2, x1, x2) for x1, y1, x2, y2 in boxes], lip_order=True)
+    idx = list(range(len(boxes)))
+    got = av.paste(torch.from_numpy(res).cuda(), idx).cpu().numpy()
+    for k in idx:
+        x1, y1, x2, y2 = boxes[k]
+        want = R.lip_paste(frames[k], res[k], (y1, y2, x1, x2))
+        assert np.array_equal(got[k], want), (boxes[k], int((got[k] != want).sum()))
+    assert np.array_equal(got[0], R.resize_linear_u8(res[0].astype(np.uint8), W, H))      # flush: nothing of the cached frame is left
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W", [60, 61, 63])
+def test_hip_muse_blend_at_the_frame_border(lib_built, W):
+    """each border bbox with the crop box equal to the bbox and equal to the whole frame (the mask then reaches x = 0, x = W - 1, y = 0 and y = H - 1)"""
+    from mere_fusion_amd.paste import AvatarFrames
+    H = 50
+    rng = np.random.default_rng(40 + W)
+    boxes = [b for b in _border_boxes(H, W) for _ in range(2)][1:]                        # (flush, whole frame) once
+    crops = ([b if k % 2 else (0, 0, W, H) for k, b in enumerate([b for b in _border_boxes(H, W) for _ in range(2)])])[1:]
+    assert (boxes[0], crops[0]) == ((0, 0, W, H), (0, 0, W, H)) and sum(b == c for b, c in zip(boxes, crops)) == 5 and sum(c == (0, 0, W, H) for c in crops) == 5
+    n = len(boxes)
+    frames = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+    masks = [rng.integers(0, 256, (c[3] - c[1], c[2] - c[0], 3), dtype=np.uint8) for c in crops]
+    for m in masks[::2]:
+        m[:] = m[..., :1]                                                                  # grey masks, as cv2.imread of a grey png gives; the others keep colour
+    for m in masks:
+        m[0, :] = 255; m[-1, :] = 0; m[1:-1, 0] = 255; m[1:-1, -1] = 0                     # both ends of the blend on the mask's own border
+    res = rng.integers(0, 256, (n, 256, 256, 3), dtype=np.uint8)
+    av = AvatarFrames(frames, boxes, masks, crops)
+    idx = list(range(n))
+    got = av.paste(torch.from_numpy(res).cuda(), idx).cpu().numpy()
+    for k in idx:
+        want = R.muse_paste(frames[k], res[k], boxes[k], masks[k], crops[k])
+        assert np.array_equal(got[k], want), (boxes[k], crops[k], int((got[k] != want).sum()))
+    assert np.array_equal(av.frames.cpu().numpy(), frames)
+
+
 @pytest.mark.gpu
 def test_hip_get_image_blending_dropin(lib_built):
     from mere_fusion_amd.musetalk.utils.blending import get_crop_box, get_image_blending
