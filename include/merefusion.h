@@ -633,6 +633,23 @@ int mf_nerf_head_set_rounds(mf_nerf_head* h, int rounds);
 int mf_nerf_head_last_rounds(mf_nerf_head* h, int* rounds, int* error_flag);
 /* Diagnostics: the first n_ints words of the loop's control block (synchronous copy; layout in csrc/mf_nerf_march.h). */
 int mf_nerf_head_ctl_snapshot(mf_nerf_head* h, int* out, int n_ints);
+/* Diagnostics: the two per-round kernels of the loop, launched on the caller's device buffers instead of a handle's, so that a test can look at what they
+ * write.  ctl_dev is a control block of at least 12 ints the caller has written (layout in csrc/mf_nerf_march.h): [0] n_alive, [1] n_step, [2] the step count
+ * after this round, [3] n_alive * n_step, [6..7] and [10..11] zero, [8] the rounds so far.  Both calls copy its head back and check it before they launch (they
+ * wait for `stream` once); the launch itself is only enqueued.
+ * mf_nerf_loop_march_debug: the march of one round over blocks of 256 of the n_rays rays, as mf_march_rays with noises = 0 writes it -- and the slots a ray does
+ * not reach zeroed; xyzs / dirs [n_alive * n_step, 3], deltas [n_alive * n_step, 2], nothing beyond.  variant 0: the kernel mf_nerf_head_render would pick
+ * (the one-cascade kernel iff cascades == 1 and grid_size is a power of two up to 128), 1: the generic kernel, 2: the one-cascade kernel, MF_ERR_INVALID
+ * where the rule does not allow it.  Refused too: what mf_march_rays refuses, n_alive > n_rays, n_step outside 1..8.
+ * mf_nerf_loop_composite_debug: the tail of one round as mf_nerf_head_render launches it: the blend of mf_composite_rays_triplane, the survivors appended to
+ * alive_out (at least n_alive ints; in no particular order), and the head of the next round written to ctl_dev[0..3], [6..8] for a frame of N rays. */
+int mf_nerf_loop_march_debug(const int* ctl_dev, const int* rays_alive, const float* rays_t, const float* rays_o, const float* rays_d, uint32_t n_rays,
+                             float bound, float dt_gamma, uint32_t max_steps, uint32_t cascades, uint32_t grid_size, const uint8_t* bitfield,
+                             const float* fars, float* xyzs, float* dirs, float* deltas, int variant, void* stream);
+int mf_nerf_loop_composite_debug(int* ctl_dev, int N, int max_steps, float T_thresh, const int* alive_in, int* alive_out, float* rays_t,
+                                 const float* sigmas, const float* rgbs, const float* deltas, const float* ambs_aud, const float* ambs_eye,
+                                 const float* uncertainties, float* weights_sum, float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum,
+                                 float* uncertainty_sum, void* stream);
 /* The per-ray sums `run_cuda` also returns at inference (`results['ambient_aud' | 'ambient_eye' | 'uncertainty']`, renderer.py:286-288) of the LAST frame
  * rendered through `h`: device-to-device copies enqueued on `stream` behind that frame (any of the three may be NULL). */
 int mf_nerf_head_sums(mf_nerf_head* h, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream);

@@ -660,6 +660,52 @@ int mf_nerf_loop_composite(const NerfLoop& l, int round, const NerfFieldOut& f, 
     return MF_OK;
 }
 
+// ---- diagnostics: the loop's own march / composite kernels on the caller's buffers (merefusion.h; tests/test_ernerf_loop_kernels.py) --------------
+// Both read the head of the caller's control block back before they launch (a synchronous copy behind `stream`): the kernels trust it -- n_step sizes
+// k_loop_march's LDS slab, the composite appends from the counter in ctl[6] and posts through the pointer in ctl[10..11] -- and a handle cannot be wrong there.
+extern "C" int mf_nerf_loop_march_debug(const int* ctl_dev, const int* rays_alive, const float* rays_t, const float* rays_o, const float* rays_d, uint32_t n_rays,
+                                        float bound, float dt_gamma, uint32_t max_steps, uint32_t cascades, uint32_t grid_size, const uint8_t* bitfield,
+                                        const float* fars, float* xyzs, float* dirs, float* deltas, int variant, void* stream) {
+    MF_REQUIRE(ctl_dev && rays_alive && rays_t && rays_o && rays_d && bitfield && fars && xyzs && dirs && deltas, "nerf_loop_march_debug: null argument");
+    MF_REQUIRE(max_steps > 0 && cascades >= 1 && cascades <= 8 && grid_size >= 2 && grid_size <= 128, "nerf_loop_march_debug: max_steps=%u cascades=%u grid=%u",
+               max_steps, cascades, grid_size);
+    MF_REQUIRE(variant >= 0 && variant <= 2, "nerf_loop_march_debug: variant %d (0 the production rule, 1 generic, 2 FAST)", variant);
+    const bool fast_ok = cascades == 1 && (grid_size & (grid_size - 1)) == 0 && grid_size <= 128;        // mf_nerf_loop_march's rule
+    MF_REQUIRE(variant != 2 || fast_ok, "nerf_loop_march_debug: FAST needs one cascade and a power-of-two grid up to 128 (cascades=%u grid=%u)", cascades, grid_size);
+    if (n_rays == 0) return MF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int head[2] = {0, 0};
+    MF_HIP(hipMemcpyAsync(head, ctl_dev, sizeof(head), hipMemcpyDeviceToHost, s));
+    MF_HIP(hipStreamSynchronize(s));
+    MF_REQUIRE(head[0] >= 0 && (uint32_t)head[0] <= n_rays && head[1] >= 1 && head[1] <= LOOP_MAX_STEP, "nerf_loop_march_debug: ctl n_alive=%d (n_rays %u) n_step=%d (1..%d)",
+               head[0], n_rays, head[1], LOOP_MAX_STEP);
+    const auto kernel = (variant != 1 && fast_ok) ? k_loop_march<true> : k_loop_march<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks(n_rays)), dim3(NT), 0, s, ctl_dev, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, cascades, grid_size,
+                       bitfield, fars, xyzs, dirs, deltas);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+extern "C" int mf_nerf_loop_composite_debug(int* ctl_dev, int N, int max_steps, float T_thresh, const int* alive_in, int* alive_out, float* rays_t,
+                                            const float* sigmas, const float* rgbs, const float* deltas, const float* ambs_aud, const float* ambs_eye,
+                                            const float* uncertainties, float* weights_sum, float* depth, float* image, float* amb_aud_sum, float* amb_eye_sum,
+                                            float* uncertainty_sum, void* stream) {
+    MF_REQUIRE(ctl_dev && alive_in && alive_out && rays_t && sigmas && rgbs && deltas && ambs_aud && ambs_eye && uncertainties && weights_sum && depth && image &&
+               amb_aud_sum && amb_eye_sum && uncertainty_sum, "nerf_loop_composite_debug: null argument");
+    MF_REQUIRE(N > 0 && max_steps > 0 && ((uintptr_t)ctl_dev & 7) == 0, "nerf_loop_composite_debug: N=%d max_steps=%d, ctl 8-byte aligned", N, max_steps);
+    hipStream_t s = (hipStream_t)stream;
+    int head[LOOP_CTL_FB + 2];
+    MF_HIP(hipMemcpyAsync(head, ctl_dev, sizeof(head), hipMemcpyDeviceToHost, s));
+    MF_HIP(hipStreamSynchronize(s));
+    MF_REQUIRE(head[0] >= 0 && head[0] <= N && head[1] >= 0 && head[1] <= LOOP_MAX_STEP, "nerf_loop_composite_debug: ctl n_alive=%d (N %d) n_step=%d (0..%d)", head[0], N,
+               head[1], LOOP_MAX_STEP);
+    MF_REQUIRE(head[6] == 0 && head[7] == 0 && head[LOOP_CTL_FB] == 0 && head[LOOP_CTL_FB + 1] == 0,
+               "nerf_loop_composite_debug: ctl[6..7] (the round's counter) and ctl[10..11] (the feedback pointer) must be zero");
+    hipLaunchKernelGGL(k_loop_composite, dim3((unsigned)((N + CT - 1) / CT)), dim3(CT), 0, s, ctl_dev, N, max_steps, T_thresh, alive_in, alive_out, rays_t, sigmas, rgbs,
+                       deltas, ambs_aud, ambs_eye, uncertainties, weights_sum, depth, image, amb_aud_sum, amb_eye_sum, uncertainty_sum);
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
 // ---- the same four launches over the frames of a batch (mf_nerf_head_batch_render, mf_nerf_head_batch.hip): grid (blocks, n_frames) -------------------
 int mf_nerf_batch_init(const NerfBatchLoop& b, const float* aabb, float min_near, hipStream_t s) {
     hipLaunchKernelGGL(k_loop_init_batch, dim3(blocks(b.N), b.n_frames), dim3(NT), 0, s, b.frames, b.N, b.max_steps, aabb, min_near);
