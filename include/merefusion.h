@@ -245,6 +245,19 @@ int mf_gemm_bt_forward(const float* a, const float* b, float* out, int t, int n,
                        int pack_n, int pack_k, int precision, float* y_full, void* stream);
 /* (x / 2 + 0.5).clamp(0, 1) * 255, rounded half to even -> dst device uint8 [batch][h][w][3] with the channel order reversed; gx->c == 3. */
 int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_rows_geom* gx, int batch, int precision, void* stream);
+/* The uint8 producers and the head of Wav2Lip and of the VAE encoder, one launch each.  The two producers write 8-channel buffers of their own: a buffer of
+ * batch + 1 items [H + 2*halo][W + 2*halo][8] is poisoned, the kernel fills the interior of the first `batch`, and y_full (required) receives all of it
+ * with the allocation's tail, (batch + 1) * (H + 2*halo) * (W + 2*halo) * 8 + 64 fp32 values (hi + lo): ring, last item and tail must still be the poison.
+ * faces: device uint8 [.][H][W][3].  rows == NULL: face b of `faces` -> item b (channels 0-2 the face / 255 with rows y >= H / 2 zeroed, 3-5 the whole face,
+ * 6-7 zero).  rows: HOST int[batch], item b reads face rows[b] of a pool of n_pool faces (the table travels in the launch arguments, 256 rows per launch);
+ * a row outside [0, n_pool) is refused (MF_ERR_INVALID, the row named in mf_last_error) before anything is allocated or launched. */
+int mf_faces_u8_forward(const uint8_t* faces, const int* rows, int n_pool, int H, int W, int halo, int batch, int precision, float* y_full, void* stream);
+/* img: device uint8 BGR [batch][H][W][3] -> channels 0-2 = ((float)(c / 255.) [0 where half_mask and y >= H / 2] - 0.5) / 0.5 in R, G, B order, 3-7 zero. */
+int mf_vae_image_u8_forward(const uint8_t* img, int H, int W, int halo, int half_mask, int batch, int precision, float* y_full, void* stream);
+/* sigmoid(w x + b) of a 32-channel view: x device fp32 [batch][g->h * g->w][32] loaded into view g (g->c == 32, coff and cbuf multiples of 8) of a poisoned
+ * buffer; w: device fp32 [3][32], b: device fp32 [3].  out: device fp32 [batch][3][h][w] in [0, 1] (hwc255 == 0) or [batch][h][w][3] * 255 (hwc255 == 1). */
+int mf_head_sigmoid_forward(const float* x, const mf_rows_geom* g, const float* w, const float* b, int hwc255, float* out, int batch, int precision,
+                            void* stream);
 /* mf_attention_forward's contract on the five-launch path (pack K, GEMM, row softmax, pack V^T, GEMM) the VAE mid-block runs: any head_dim % 8 == 0. */
 int mf_attention_composite_forward(const float* q, const float* k, const float* v, float* out, int batch, int tq, int tk, int heads, int head_dim,
                                    int precision, float* y_full, void* stream);

@@ -3,7 +3,7 @@
 // poison value first (MF_NN_POISON_*), the input view is loaded over it, and `y_full` hands the whole padded output buffer back, so a test sees
 // every element an op wrote outside its view (halo ring, neighbouring channels of a wider buffer, tokens past a prefix).
 // mf_conv_view_forward and mf_attention_view_forward launch a conv layer and the fused attention on views the same way (sequence layers, token prefixes,
-// packed q | k | v).  mf_act_q_encode is the same kind of seam for the producers of the f16 + FP6-block activation format (mf_aux.hip): it hands back the raw planes.
+// packed q | k | v).  mf_faces_u8_forward, mf_vae_image_u8_forward and mf_head_sigmoid_forward are the seams of mf_aux.hip's uint8 producers and head.  mf_act_q_encode is the same kind of seam for the producers of the f16 + FP6-block activation format (mf_aux.hip): it hands back the raw planes.
 #include "mf_nn.h"
 #include "mf_aux.h"
 #include <cmath>
@@ -217,6 +217,66 @@ extern "C" int mf_vae_post_u8_forward(const float* x, uint8_t* dst, const mf_row
     if ((rc = bx.alloc(*gx, batch, x3, s))) return rc;
     if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*gx), batch, s))) return rc;
     if ((rc = mf_vae_post_u8(bx.view(*gx), dst, batch, s))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+// ---- the Wav2Lip and VAE edge kernels of mf_aux.hip: uint8 in, head out ------------------------------------------------------------------------------
+// The uint8 producers write whole 8-channel pixels of a buffer of their own, so nothing is loaded first: the buffer is poisoned for batch + 1 items, the
+// kernel fills the interior of the first `batch`, and y_full takes all of it back with the allocation's tail -- halo ring, the item behind the batch and
+// the tail must still be the poison.
+namespace {
+int u8_planes_args(const char* name, const void* src, int H, int W, int halo, int batch, const float* y_full) {
+    MF_REQUIRE(src && y_full, "%s: null argument", name);
+    MF_REQUIRE(H > 0 && W > 0 && halo >= 0 && batch > 0, "%s: H=%d W=%d halo=%d batch=%d", name, H, W, halo, batch);
+    MF_REQUIRE(((int64_t)batch + 1) * (H + 2 * halo) * (W + 2 * halo) * 8 < (int64_t)1 << 31, "%s: %d + 1 items of %d x %d (halo %d) reach 2^31 elements", name, batch, H, W, halo);
+    return MF_OK;
+}
+}  // namespace
+
+extern "C" int mf_faces_u8_forward(const uint8_t* faces, const int* rows, int n_pool, int H, int W, int halo, int batch, int precision, float* y_full, void* stream) {
+    int rc;
+    if ((rc = u8_planes_args("faces_u8_forward", faces, H, W, halo, batch, y_full))) return rc;
+    if (rows) {
+        MF_REQUIRE(n_pool > 0, "faces_u8_forward: a row table needs a pool, got n_pool=%d", n_pool);
+        for (int i = 0; i < batch; ++i)
+            MF_REQUIRE(rows[i] >= 0 && rows[i] < n_pool, "faces_u8_forward: rows[%d] = %d is outside the pool of %d faces", i, rows[i], n_pool);
+    }
+    MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "faces_u8_forward: unknown precision %d", precision);
+    hipStream_t s = (hipStream_t)stream;
+    PBuf b;
+    if ((rc = b.alloc(8, H, W, halo, batch + 1, precision == MF_PREC_BF16X3, s))) return rc;
+    if ((rc = rows ? mf_faces_u8_rows_to_act(faces, rows, b.b, batch, s) : mf_faces_u8_to_act(faces, b.b, batch, s))) return rc;
+    if ((rc = b.full(y_full, s, 64))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_vae_image_u8_forward(const uint8_t* img, int H, int W, int halo, int half_mask, int batch, int precision, float* y_full, void* stream) {
+    int rc;
+    if ((rc = u8_planes_args("vae_image_u8_forward", img, H, W, halo, batch, y_full))) return rc;
+    MF_REQUIRE(half_mask == 0 || half_mask == 1, "vae_image_u8_forward: half_mask is 0 or 1, got %d", half_mask);
+    MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "vae_image_u8_forward: unknown precision %d", precision);
+    hipStream_t s = (hipStream_t)stream;
+    PBuf b;
+    if ((rc = b.alloc(8, H, W, halo, batch + 1, precision == MF_PREC_BF16X3, s))) return rc;
+    if ((rc = mf_vae_image_u8_to_act(img, b.b, half_mask, batch, s))) return rc;
+    if ((rc = b.full(y_full, s, 64))) return rc;
+    MF_HIP(hipStreamSynchronize(s));
+    return MF_OK;
+}
+
+extern "C" int mf_head_sigmoid_forward(const float* x, const mf_rows_geom* g, const float* w, const float* b, int hwc255, float* out, int batch, int precision,
+                                       void* stream) {
+    MF_REQUIRE(x && w && b && out && geom_ok(g) && batch > 0, "head_sigmoid_forward: null argument or bad geometry");
+    MF_REQUIRE(g->c == 32 && g->coff % 8 == 0 && g->cbuf % 8 == 0, "head_sigmoid_forward: the head reads 32 channels in 8-channel groups, got c=%d coff=%d cbuf=%d", g->c,
+               g->coff, g->cbuf);
+    MF_REQUIRE(hwc255 == 0 || hwc255 == 1, "head_sigmoid_forward: hwc255 is 0 or 1, got %d", hwc255);
+    API_PREC("head_sigmoid_forward");
+    PBuf bx;
+    if ((rc = bx.alloc(*g, batch, x3, s))) return rc;
+    if ((rc = mf_rows_from_f32(x, nullptr, bx.view(*g), batch, s))) return rc;
+    if ((rc = mf_head_1x1_sigmoid(bx.view(*g), w, b, out, hwc255, batch, s))) return rc;
     MF_HIP(hipStreamSynchronize(s));
     return MF_OK;
 }
