@@ -10,35 +10,13 @@ import pytest
 import torch
 
 import nerf_serving_util as U
+from nerf_featpool_ref import emu_scatter as _emu_scatter, emu_windows as _emu_windows
 from serving_fakes import FakeRing, fake_cuda_events
 
 B = 4
 
 
-# ---- the two launches, restated from the header (host tensors) -----------------------------------------------------------------------------
-def _emu_scatter(feats, left, right, rings, rows, starts):
-    for i, (k, st) in enumerate(zip(rows, starts)):
-        assert 0 <= st and st + right - left <= rings.shape[1]
-        rings[k, st:st + right - left] = feats[i, left:right]
-
-
-def _emu_windows(rings, hist, rows, fronts, heads, n_new, att, out=None):
-    N, R, dim = rings.shape
-    o = torch.full((len(rows), 8 if att else 1, dim, 16), float("nan")) if out is None else out
-    n_out = 8 if att else 1
-    for i, k in enumerate(rows):
-        assert len(fronts[i]) == n_out
-        for q, f in enumerate(fronts[i]):
-            j = q - (n_out - n_new[i])
-            if j >= 0 or (f >= 0 and f + 16 < R):                        # a new window, or a view of the ring
-                o[i, q] = rings[k, [(f + t) % R for t in range(16)]].t()
-                if att and j >= 0:
-                    hist[k, (heads[i] + j) % 8] = o[i, q]
-            else:                                                        # a copy (it wrapped), or a zero window
-                o[i, q] = hist[k, (heads[i] + n_new[i] + q) % 8]
-    return o
-
-
+# ---- the two launches, restated from the header (host tensors): tests/nerf_featpool_ref.py, the model the GPU tier holds the launches to --------
 @pytest.fixture
 def host_ops(monkeypatch):
     from mere_fusion_amd import nerf_serving as S

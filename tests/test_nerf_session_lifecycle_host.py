@@ -11,28 +11,15 @@ import torch
 
 import nerf_serving_util as U
 from serving_fakes import FakeRing
-from test_nerf_serving_host import FakeModel, FakeSession, _emu_scatter, _emu_windows, _inp
+from nerf_featpool_ref import emu_rows_load as _emu_rows_load, emu_scatter as _emu_scatter, emu_windows as _emu_windows
+from test_nerf_serving_host import FakeModel, FakeSession, _inp
 from test_session_lifecycle_host import Events
 
 B = 4
 DIM = 5
 
 
-# ---- the new launch, restated from the header (host tensors) ---------------------------------------------------------------------------------
-def _emu_rows_load(rings, hist, rows, src_ring=None, src_hist=None):
-    rows = list(rows)
-    assert rows and len(set(rows)) == len(rows) and 0 <= min(rows) and max(rows) < rings.shape[0]
-    assert hist is not None or src_hist is None
-    for t, src in ((rings, src_ring), (hist, src_hist)):
-        if t is None:
-            continue
-        if src is not None:                                              # a source may be another row of the pool, never a named one
-            assert tuple(src.shape) == tuple(t.shape[1:]) and all(src.data_ptr() != t[k].data_ptr() for k in rows)
-        value = torch.zeros_like(t[0]) if src is None else src.clone()
-        for k in rows:
-            t[k] = value
-
-
+# ---- the three launches, restated from the header (host tensors): tests/nerf_featpool_ref.py ---------------------------------------------------------
 @pytest.fixture
 def host_ops(monkeypatch):
     from mere_fusion_amd import nerf_serving as S
