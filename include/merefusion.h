@@ -334,6 +334,43 @@ int mf_whisper_set_batch(mf_whisper* h, int max_windows);
 int mf_whisper_encode_windows(mf_whisper* h, const float* wav, int n, int n_windows, int ctx_tokens, float* feat, void* stream);
 void mf_whisper_destroy(mf_whisper* h);
 
+/* ---- Whisper text decoder: transcription by greedy decoding ------------------------------------ */
+/* The handle is untyped (void*): what mf_whisper_decoder_create stores in *out, passed back as `h`. */
+
+/* The DECODER half of the same checkpoint (`Whisper.decoder`, model.py:174-217): weights = the tensors named "decoder.*" as a Whisper
+ * state dict names them ("decoder.token_embedding.weight", "decoder.positional_embedding", "decoder.blocks.N.attn.query.weight",
+ * "decoder.blocks.N.cross_attn.key.weight", "decoder.ln.weight", ...).  "encoder.ln_post.weight" / ".bias" are optional: when present,
+ * mf_whisper_decoder_begin applies that LayerNorm (model.py:165) to the encoder states first -- mf_whisper_encode_audio returns the last
+ * block's output without it.  n_state / n_layer / n_text_ctx / n_vocab are inferred; n_state = 64 * n_head and a multiple of 128.
+ * max_batch: sequences decoded together, 1..8. */
+int mf_whisper_decoder_create(const mf_tensor* weights, int n_weights, int n_head, int precision, int max_batch, void** out);
+int mf_whisper_decoder_dims(const void* h, int* n_layer, int* n_text_ctx, int* n_state, int* n_vocab);
+
+/* Starts a segment for `batch` sequences: enc_states device fp32 [batch][T_audio][n_state], 1 <= T_audio <= 1500 (only these rows are read);
+ * projects the cross-attention keys and values of every layer once, zeroes the self-attention caches, sets every sequence's length to 0. */
+int mf_whisper_decoder_begin(void* h, const float* enc_states, int T_audio, int batch, void* stream);
+
+/* `TextDecoder.forward(tokens, xa, kv_cache)`: appends n tokens per sequence at the caches' current offset (0 after begin) under the causal
+ * mask and returns their logits.  tokens: device int32 [batch][n]; logits: device fp32 [batch][n][n_vocab].  n = 1 repeated is the decode
+ * step fed by the caller.  Refused when the offset + n exceeds n_text_ctx, and after a greedy run until the next begin. */
+int mf_whisper_decoder_logits(void* h, const int* tokens, int n, float* logits, int batch, void* stream);
+
+/* Greedy decoding of the segment begun last (GreedyDecoder of decoding.py at temperature 0, without timestamp rules): prefill of every prompt
+ * in one pass, then one token per sequence and step, chosen on the device as argmax(logits + suppress_mask), lowest index on a tie.
+ * prompts: HOST int32, the sequences' prompt tokens one after the other; prompt_lens: HOST int32 [batch], each 1..n_text_ctx / 2;
+ * suppress_mask: device fp32 [n_vocab] of 0 / -inf, or NULL; out_tokens: HOST int32 [batch][max_new] (the tokens before end-of-text, the
+ * rest 0); out_lens: HOST int32 [batch]; sum_logprobs: HOST fp32 [batch], log-softmax of the masked logits at every chosen token, the
+ * end-of-text token's included.  A sequence stops at `eot`, after max_new tokens, or when its cache is full (n_text_ctx rows); from then on no
+ * launch writes its cache rows, output or counters.  The host reads the done flags every `check_every` steps (>= 1) and at no other time;
+ * the result does not depend on check_every.  max_new <= n_text_ctx - (shortest prompt) + 1.  Returns when the tokens are on the host. */
+int mf_whisper_decoder_greedy(void* h, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new,
+                              int check_every, int* out_tokens, int* out_lens, float* sum_logprobs, int batch, void* stream);
+
+/* Test seam: the self-attention cache of one layer and sequence, k and v HOST fp32 [n_text_ctx][n_state] each, and the sequence's length.
+ * Synchronises the device. */
+int mf_whisper_decoder_cache_read(const void* h, int layer, int seq, float* k, float* v, int* len);
+void mf_whisper_decoder_destroy(void* h);
+
 /* ---- MuseTalk UNet (H4) and VAE decode (H5) --------------------------------------------------- */
 /* The reference builds both from diffusers with config files it does not ship (musetalk/models/unet.py:34-37,
  * vae.py:24), so the architecture is a parameter here.  Field meaning = the diffusers config keys. */

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmerefusion_hip.so")
 OBJ = os.path.normpath(os.path.join(HERE, "..", "build", "obj"))
 SOURCES = ["mf_api.cpp", "mf_conv.hip", "mf_conv_plan.hip", "mf_conv_launch.hip", "mf_conv_tune.hip", "mf_conv_debug.hip", "mf_conv_halo.hip", "mf_conv_halo2.hip", "mf_conv_thin.hip", "mf_conv_tail.hip", "mf_aux.hip", "mf_wav2lip.hip", "mf_conv_api.hip", "mf_mel.hip",
-           "mf_nn.hip", "mf_nn_api.hip", "mf_attn.hip", "mf_whisper.hip", "mf_schedule.hip", "mf_musetalk_build.hip", "mf_musetalk.hip", "mf_nerf.hip", "mf_nerf_net.hip", "mf_nerf_head.hip", "mf_nerf_head_batch.hip", "mf_nerf_fused.hip", "mf_nerf_occupancy.hip", "mf_nerf_torso.hip", "mf_nerf_audio.hip", "mf_nerf_frame.hip", "mf_nerf_frame_batch.hip", "mf_nerf_featpool.hip",
+           "mf_nn.hip", "mf_nn_api.hip", "mf_attn.hip", "mf_whisper.hip", "mf_whisper_dec.hip", "mf_schedule.hip", "mf_musetalk_build.hip", "mf_musetalk.hip", "mf_nerf.hip", "mf_nerf_net.hip", "mf_nerf_head.hip", "mf_nerf_head_batch.hip", "mf_nerf_fused.hip", "mf_nerf_occupancy.hip", "mf_nerf_torso.hip", "mf_nerf_audio.hip", "mf_nerf_frame.hip", "mf_nerf_frame_batch.hip", "mf_nerf_featpool.hip",
            "mf_blend.hip", "mf_i420.hip", "mf_frame_gather.hip", "mf_window_push.hip", "mf_session.hip", "mf_graph_run.hip", "mf_wav2vec2.hip", "mf_net.hip", "mf_s3fd_detect.hip", "mf_face_mask.hip", "mf_crop_resize.hip", "mf_dwpose_ops.hip", "mf_rtmcc_head.hip", "mf_dwpose.hip", "mf_sync.hip", "mf_probe.hip"]
 # -pragma-unroll-threshold: the 256 x 256 implicit-GEMM tile's `#pragma unroll` loops (128 accumulator registers, 8 x 4 fragments) exceed LLVM's default
 # cap of 16384 for pragma-driven unrolling; a loop left rolled indexes the accumulator array dynamically, which puts it in scratch (592 bytes per lane,
