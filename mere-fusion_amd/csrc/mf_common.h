@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstdarg>
 #include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include "../../include/merefusion.h"
@@ -33,6 +35,19 @@ static inline const mf_tensor* mf_sd_find(const MfStateDict& sd, const char* who
     for (int i = 0; i < it->second->ndim; ++i) n *= it->second->shape[i];
     if (n != numel) { mf_set_error("%stensor '%s' has %lld elements, expected %lld", pre.c_str(), k.c_str(), (long long)n, (long long)numel); return nullptr; }
     return it->second;
+}
+
+// The state dict of a create call: every tensor must carry a name and data (the error says "<who>: " and which tensor does not; who == "": no prefix); each
+// of strip_prefixes, in order, is taken off a name that begins with it (keys of a full checkpoint), and a later tensor replaces an earlier one of the same name.
+static inline int mf_sd_build(const mf_tensor* weights, int n, const char* who, std::initializer_list<const char*> strip_prefixes, MfStateDict* sd) {
+    for (int i = 0; i < n; ++i) {
+        if (!weights[i].name || !weights[i].data) { mf_set_error("%s%stensor %d has no name/data", who, *who ? ": " : "", i); return MF_ERR_INVALID; }
+        std::string k = weights[i].name;
+        for (const char* pre : strip_prefixes)
+            if (k.rfind(pre, 0) == 0) k = k.substr(strlen(pre));
+        (*sd)[k] = &weights[i];
+    }
+    return MF_OK;
 }
 
 #define MF_HIP(call)                                                                       \
@@ -93,5 +108,16 @@ __device__ __forceinline__ void mf_gn_affine_pair(double sum, double sumsq, doub
 __device__ __forceinline__ float mf_sum4(float a, float b, float c, float d) {
     const float ab = a + mf_opaque(b), cd = c + mf_opaque(d);
     return mf_opaque(ab) + mf_opaque(cd);
+}
+// round-to-nearest-even fp32 -> bf16 bits on the device: mf_f2bf's integer arithmetic without its NaN case (the kernels never had one), and the (hi, lo) split of
+// a bf16x3 plane pair.  v - hi is exact in fp32, so the split gives the same bits under any contraction setting.
+__device__ __forceinline__ unsigned mf_bf16_rne(float f) {
+    unsigned u = __float_as_uint(f);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+__device__ __forceinline__ void mf_split_bf16(float v, unsigned& hi, unsigned& lo) {
+    hi = mf_bf16_rne(v);
+    lo = mf_bf16_rne(v - __uint_as_float(hi << 16));
 }
 #endif

@@ -81,14 +81,7 @@ __global__ __launch_bounds__(256) void k_ca_scale(Pl X, int xoff, const float* _
     Y.st(Y.at(b, y, x) + yoff + c, X.ld(X.at(b, y, x) + xoff + c) * s[(int64_t)b * C + c]);
 }
 
-int upload(mf_net* h, const std::vector<float>& v, float** out) {
-    float* d = nullptr;
-    MF_HIP(hipMalloc(&d, v.size() * sizeof(float)));
-    h->dev.push_back(d);
-    MF_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = d;
-    return MF_OK;
-}
+int upload(mf_net* h, const std::vector<float>& v, float** out) { return h->upload(v.data(), v.size(), out); }
 
 }  // namespace
 

@@ -195,8 +195,7 @@ __global__ __launch_bounds__(256) void k_fm_pass_v(const FmArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float f = fm_normalize(v[c < C ? c : 0], a.mean[c], a.std[c]);
-            h[c] = nfb(f);
-            l[c] = nfb(f - nbf(h[c]));
+            mf_split_bf16(f, h[c], l[c]);
         }
         const int64_t o = (((int64_t)j.slot * (a.NH + 2 * a.halo) + y + a.halo) * (a.NW + 2 * a.halo) + x + a.halo) * 8;
         *reinterpret_cast<uint4*>(a.hi + o) = make_uint4(h[0] | h[1] << 16, h[2], 0u, 0u);

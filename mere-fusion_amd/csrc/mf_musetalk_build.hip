@@ -108,10 +108,7 @@ Builder::~Builder() {
 int Builder::init(const mf_tensor* weights, int n, int prec, int max_batch, int max_groups, int ln_tokens_per_sample) {
     precision = prec; cap = max_batch;
     gn_affine_fuse = env_on("MF_GN_AFFINE_FUSE");
-    for (int i = 0; i < n; ++i) {
-        if (!weights[i].name || !weights[i].data) { mf_set_error("tensor %d has no name/data", i); return MF_ERR_INVALID; }
-        sd[weights[i].name] = &weights[i];
-    }
+    if (mf_sd_build(weights, n, "", {}, &sd)) return MF_ERR_INVALID;
     // one slice of fp64 (sum, sum of squares) per GroupNorm op; the whole array is zeroed by ONE kernel at the head
     // of the op list, so a GroupNorm is two launches (statistics, apply) instead of four
     gn_slice = (size_t)max_batch * max_groups * 2;

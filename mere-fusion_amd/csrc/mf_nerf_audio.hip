@@ -234,11 +234,9 @@ struct mf_audio_encoder {
 extern "C" int mf_audio_encoder_create(const mf_tensor* weights, int n_weights, int use_att, mf_audio_encoder** out) {
     MF_REQUIRE(weights && out && n_weights > 0, "audio_encoder_create: bad argument");
     *out = nullptr;
-    std::map<std::string, const mf_tensor*> sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "audio_encoder_create: tensor %d has no name/data", i);
-        sd[weights[i].name] = &weights[i];
-    }
+    MfStateDict sd;
+    int rc = mf_sd_build(weights, n_weights, "audio_encoder_create", {}, &sd);
+    if (rc) return rc;
     std::unique_ptr<mf_audio_encoder> h(new mf_audio_encoder());
     std::vector<float> arena;                                   // every layer's [weight | bias], each padded to 4 floats
     auto up = [&](const std::string& k, int64_t n, int* off) -> int {
@@ -268,7 +266,6 @@ extern "C" int mf_audio_encoder_create(const mf_tensor* weights, int n_weights, 
     h->in_dim = in_dim;
     h->a.in_dim = wide ? 32 : in_dim;
     h->a.use_att = use_att ? 1 : 0;
-    int rc;
     const int cc[5] = {in_dim, 32, 32, 64, 64};                 // network.py:46-53 (Sequential indices 0, 2, 4, 6)
     if (wide) {
         auto b = sd.find("audio_net.encoder_conv.0.bias");

@@ -44,16 +44,9 @@ struct FusedArgs {
     float *sigmas, *rgbs, *amb_aud, *amb_eye, *unc;
 };
 
-__device__ __forceinline__ uint32_t fbf(float f) {
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ float bff(uint32_t h) { return __uint_as_float(h << 16); }
-
 // a B fragment half (4 channels of one 16-block): bf16 (hi, lo) pairs of 4 fp32 values -> 2 + 2 dwords
 struct Half { uint32_t h[2], l[2]; };
-// (hi, lo) split of two values with gfx950's packed converter: v_cvt_pk_bf16_f32 rounds to nearest even exactly as fbf() does, and the whole
+// (hi, lo) split of two values with gfx950's packed converter: v_cvt_pk_bf16_f32 rounds to nearest even exactly as mf_bf16_rne() does, and the whole
 // split is 5 instructions where the integer form needs ~23 -- the kernel packs ~30 of these quads per 16 samples and is VALU-bound
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));

@@ -116,36 +116,17 @@ int mf_nerf_torso_grid_launch(const NerfTorsoConsts& t, const float* bias, const
 constexpr int TW = 1024;                 // tokens per "image" of the token buffers
 
 // shared by the field and the torso net: token buffers of 1 x TW "images", bias-free Linears as bound 1x1-conv plans
-struct TokenNet {
+struct TokenNet : NetStore {
     int precision = MF_PREC_BF16X3;
     int cap_batches = 0;
-    std::vector<std::unique_ptr<ActBuf>> bufs;
-    std::vector<std::unique_ptr<ConvPlan>> plans;
-    std::vector<void*> dev;
 
-    ~TokenNet() {
-        for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) mf_actbuf_free(b.get());
-        for (void* d : dev) (void)hipFree(d);
-    }
-    ActBuf* seq(int C) {
-        bufs.emplace_back(new ActBuf());
-        ActBuf* b = bufs.back().get();
-        b->C = C; b->H = 1; b->W = TW; b->halo = 0;
-        return b;
-    }
-    int alloc() {
-        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap_batches, precision); if (rc) return rc; }
-        return MF_OK;
-    }
+    ActBuf* seq(int C) { return buf(C, 1, TW, 0); }
+    int alloc() { return NetStore::alloc(cap_batches, precision); }
     // Linear(cin -> cout, bias=False) (network.py:79) as a 1x1 convolution; `w` is [cout][cin_buf] with the input-channel order of
     // the buffer view it reads
     int linear(ConvPlan** out, const std::vector<float>& w, int cin, int cout, int act, ActBuf* in) {
-        plans.emplace_back(new ConvPlan());
-        ConvPlan* p = plans.back().get();
-        mf_conv2d_desc d{};
-        d.cin = cin; d.cout = cout; d.kh = d.kw = 1; d.stride_h = d.stride_w = 1; d.act = act; d.in_h = 1; d.in_w = TW;
-        int rc = mf_conv_plan_create(p, d, w.data(), nullptr, nullptr, nullptr, nullptr, nullptr, precision);
+        ConvPlan* p = new_plan();
+        int rc = mf_seq_conv_plan(p, w.data(), nullptr, cin, cout, TW, act, 0, precision);
         if (rc) return rc;
         if ((rc = mf_conv_bind(p, *in))) return rc;
         *out = p;

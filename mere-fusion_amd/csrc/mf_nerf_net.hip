@@ -151,11 +151,9 @@ extern "C" int mf_nerf_field_create(const mf_nerf_field_config* cfg, const mf_te
                "nerf_field_create: built for the reference's fixed field (12 levels x 1, audio 32, hidden 64, geo 64: network.py:122-143)");
     MF_REQUIRE(cfg->individual_dim >= 0 && cfg->individual_dim <= 8 && cfg->bound > 0, "nerf_field_create: individual_dim / bound");
     *out = nullptr;
-    std::map<std::string, const mf_tensor*> sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "nerf_field_create: tensor %d has no name/data", i);
-        sd[weights[i].name] = &weights[i];
-    }
+    MfStateDict sd;
+    int rc = mf_sd_build(weights, n_weights, "nerf_field_create", {}, &sd);
+    if (rc) return rc;
     std::unique_ptr<mf_nerf_field> h(new mf_nerf_field());
     h->precision = precision;
     h->cfg = *cfg;
@@ -166,8 +164,7 @@ extern "C" int mf_nerf_field_create(const mf_nerf_field_config* cfg, const mf_te
 
     h->SI = h->seq(SI_C); h->CI = h->seq(CI_C); h->T1 = h->seq(64); h->AU = h->seq(AUD); h->T2 = h->seq(16); h->EY = h->seq(8);
     h->S1 = h->seq(64); h->S2 = h->seq(64); h->C1 = h->seq(64); h->RGB = h->seq(8);
-    int rc = h->alloc();
-    if (rc) return rc;
+    if ((rc = h->alloc())) return rc;
     const size_t cap = (size_t)h->cap_batches * TW;
     MF_HIP(hipMalloc(&h->coords, cap * 6 * sizeof(float))); h->dev.push_back(h->coords);
     MF_HIP(hipMalloc(&h->enc, cap * ENC * sizeof(float))); h->dev.push_back(h->enc);
@@ -410,11 +407,9 @@ extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_te
     MF_REQUIRE(cfg->num_levels == 16 && cfg->level_dim == 2 && cfg->individual_dim >= 0 && cfg->individual_dim <= 8 && cfg->grid_size > 1,
                "nerf_torso_create: built for the reference's torso nets (tiled grid 16 x 2, ind_dim_torso <= 8: network.py:155-159)");
     *out = nullptr;
-    std::map<std::string, const mf_tensor*> sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "nerf_torso_create: tensor %d has no name/data", i);
-        sd[weights[i].name] = &weights[i];
-    }
+    MfStateDict sd;
+    int rc = mf_sd_build(weights, n_weights, "nerf_torso_create", {}, &sd);
+    if (rc) return rc;
     std::unique_ptr<mf_nerf_torso> h(new mf_nerf_torso());
     h->precision = precision;
     h->cfg = *cfg;
@@ -423,8 +418,7 @@ extern "C" int mf_nerf_torso_create(const mf_nerf_torso_config* cfg, const mf_te
     const int din = FQ + ncst, tin = TG + FQ + ncst;
     h->TX = h->seq(TX_C); h->TH = h->seq(TH_C); h->D1 = h->seq(32); h->D2 = h->seq(32); h->DX = h->seq(8); h->U1 = h->seq(32); h->U2 = h->seq(32);
     h->OUT = h->seq(8);
-    int rc = h->alloc();
-    if (rc) return rc;
+    if ((rc = h->alloc())) return rc;
     const size_t cap = (size_t)h->cap_batches * TW;
     auto dmalloc = [&](float** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(float))); h->dev.push_back(*p); return MF_OK; };
     if ((rc = dmalloc(&h->xs, cap * 2)) || (rc = dmalloc(&h->coords01, cap * 2)) || (rc = dmalloc(&h->feat, cap * TG))) return rc;

@@ -143,9 +143,7 @@ extern "C" int mf_net_create(int max_batch, int precision, mf_net** out) {
 
 extern "C" int mf_net_buffer(mf_net* h, int C, int H, int W, int halo) {
     MF_REQUIRE(h && C > 0 && H > 0 && W > 0 && halo >= 0, "net_buffer: bad geometry");
-    h->bufs.emplace_back(new ActBuf());
-    ActBuf* b = h->bufs.back().get();
-    b->C = (C + 7) / 8 * 8; b->H = H; b->W = W; b->halo = halo;
+    ActBuf* b = h->buf((C + 7) / 8 * 8, H, W, halo);
     const int rc = mf_actbuf_alloc(b, h->cap, h->precision);
     return rc ? rc : (int)h->bufs.size() - 1;
 }
@@ -161,8 +159,7 @@ extern "C" int mf_net_conv(mf_net* h, const mf_conv2d_desc* d, const float* weig
     dd.in_h = ib->H; dd.in_w = ib->W; dd.residual = rb ? (d->residual ? d->residual : 1) : 0;
     std::vector<float> zero;
     if (!bias) { zero.assign(dd.cout, 0.f); bias = zero.data(); }
-    h->plans.emplace_back(new ConvPlan());
-    ConvPlan* p = h->plans.back().get();
+    ConvPlan* p = h->new_plan();
     int rc = mf_conv_plan_create(p, dd, weight, bias, bn_gamma, bn_beta, bn_mean, bn_var, h->precision);
     if (rc) return rc;
     if ((rc = mf_conv_bind(p, *ib))) return rc;
@@ -195,9 +192,8 @@ extern "C" int mf_net_l2norm(mf_net* h, int in_buf, int out_buf, const float* we
     NET_BUF(ib, in_buf); NET_BUF(ob, out_buf);
     MF_REQUIRE(ib->H == ob->H && ib->W == ob->W && C <= ib->C && C <= ob->C, "net_l2norm: shape mismatch");
     float* dw = nullptr;
-    MF_HIP(hipMalloc(&dw, C * sizeof(float)));
-    MF_HIP(hipMemcpy(dw, weight, C * sizeof(float), hipMemcpyHostToDevice));
-    h->dev.push_back(dw);
+    const int rc = h->upload(weight, C, &dw);
+    if (rc) return rc;
     h->sch.push("l2norm", "", 0.0, [ib, ob, dw, C, eps](int B, hipStream_t s) {
         const int64_t px = (int64_t)B * ib->H * ib->W;
         hipLaunchKernelGGL(k_l2norm, dim3((unsigned)((px + 3) / 4)), dim3(256), 0, s, pl_of(*ib), pl_of(*ob), dw, eps, C, px);

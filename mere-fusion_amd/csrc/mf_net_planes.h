@@ -6,16 +6,11 @@
 namespace {
 
 __device__ __forceinline__ float nbf(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t nfb(float f) {
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 struct Pl {   // one buffer's geometry for the elementwise kernels
     bf16_t* hi; bf16_t* lo; int C, H, W, halo;
     __device__ int64_t at(int b, int y, int x) const { return (((int64_t)b * (H + 2 * halo) + y + halo) * (W + 2 * halo) + x + halo) * C; }
     __device__ float ld(int64_t o) const { float v = nbf(hi[o]); if (lo) v += nbf(lo[o]); return v; }
-    __device__ void st(int64_t o, float v) const { const uint32_t h = nfb(v); hi[o] = (bf16_t)h; if (lo) lo[o] = (bf16_t)nfb(v - nbf(h)); }
+    __device__ void st(int64_t o, float v) const { unsigned h, l; mf_split_bf16(v, h, l); hi[o] = (bf16_t)h; if (lo) lo[o] = (bf16_t)l; }
 };
 inline Pl pl_of(const ActBuf& b) { return Pl{b.hi, b.lo, b.C, b.H, b.W, b.halo}; }
 

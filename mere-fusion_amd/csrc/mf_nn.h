@@ -6,6 +6,62 @@
 // epilogues (bias, GELU, residual).
 #pragma once
 #include "mf_conv.h"
+#include <memory>
+#include <vector>
+
+// What a static-schedule handle owns on the device: activation buffers, conv plans and plain allocations (uploaded tensors, scratch).  The handles derive from
+// it (mf_whisper, mf_wav2vec2, TokenNet, mf_net), so their own members -- a GraphRunner, a Schedule -- are destroyed first: graphs go before the memory they
+// point into.  Not for Builder (it also owns tail convs, a statistics slab and an error channel of its own) nor mf_wav2lip (its plans live inside its Steps).
+struct NetStore {
+    std::vector<std::unique_ptr<ActBuf>> bufs;
+    std::vector<std::unique_ptr<ConvPlan>> plans;
+    std::vector<void*> dev;                           // hipFree'd with the store; a handle may append allocations of its own
+
+    NetStore() = default;
+    NetStore(const NetStore&) = delete;
+    ~NetStore() {
+        for (auto& p : plans) mf_conv_plan_destroy(p.get());
+        for (auto& b : bufs) mf_actbuf_free(b.get());
+        for (void* d : dev) (void)hipFree(d);
+    }
+    // the geometry only; alloc() gives every buffer its planes
+    ActBuf* buf(int C, int H, int W, int halo) {
+        bufs.emplace_back(new ActBuf());
+        ActBuf* b = bufs.back().get();
+        b->C = C; b->H = H; b->W = W; b->halo = halo;
+        return b;
+    }
+    ConvPlan* new_plan() { plans.emplace_back(new ConvPlan()); return plans.back().get(); }
+    int upload(const float* host, size_t n, float** out) {
+        MF_HIP(hipMalloc(out, n * sizeof(float)));
+        dev.push_back(*out);
+        MF_HIP(hipMemcpy(*out, host, n * sizeof(float), hipMemcpyHostToDevice));
+        return MF_OK;
+    }
+    // (re)allocates every buffer for `cap` batch items, zero-filled
+    int alloc(int cap, int precision) {
+        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap, precision); if (rc) return rc; }
+        return MF_OK;
+    }
+};
+
+// A (1 x k) convolution over a token sequence of T_in tokens (buffers {C, H = 1, W = T}) as a ConvPlan: k = 1 is a Linear.  act / residual as mf_conv2d_desc.
+int mf_seq_conv_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int T_in, int act, int residual, int precision, int k = 1, int stride = 1,
+                     int pad = 0);
+
+// One transformer encoder layer over a token sequence: q | k | v as one GEMM, out-projection, two-layer GELU MLP, two LayerNorms.  The owner fetches the
+// tensors under its own key names and calls the attention itself between mf_seq_block_front and mf_seq_block_back.
+struct SeqBlock { ConvPlan *qkv, *out, *fc1, *fc2; float *g1, *b1, *g2, *b2; };
+struct SeqBlockWeights { const float *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *f1w, *f1b, *f2w, *f2b, *g1, *b1, *g2, *b2; };   // kb null: key has no bias
+struct SeqScratch { ActBuf *ln, *qkv, *ao, *h1; };    // {C, 3C, C, ffn} x T: normalised input, q | k | v, attention output, MLP hidden
+enum SeqLn { SEQ_PRE_LN, SEQ_POST_LN };
+// plans and LayerNorm vectors into `st`; the plans are bound to the buffers of `sc` they read (qkv and fc1: ln, out: ao, fc2: h1)
+int mf_seq_block_create(NetStore& st, const SeqBlockWeights& w, int C, int ffn, int T, int precision, const SeqScratch& sc, SeqBlock* out);
+// front: q | k | v of LN1(x) (pre-LN, through sc.ln) or of x itself (post-LN) into sc.qkv.  The attention writes sc.ao.  back, pre-LN:
+// y = x + out(ao); x = y + fc2(gelu(fc1(LN2(y)))).  post-LN: y = x + out(ao); x = LN1(y); y = x + fc2(gelu(fc1(x))); x = LN2(y).  The layer ends in x either way.
+// tc / tq > 0: only that token prefix of every batch item (front: the context; back: the rows whose output is wanted)
+int mf_seq_block_front(const SeqBlock& L, SeqLn mode, const ActBuf* x, const SeqScratch& sc, float eps, int batch, hipStream_t s, int tc = 0);
+int mf_seq_block_back(const SeqBlock& L, SeqLn mode, const ActBuf* x, const ActBuf* y, const SeqScratch& sc, float eps, int batch, hipStream_t s, int tq = 0);
 
 // y = (x - mean) / sqrt(var + eps) * gamma + beta over the C channels of every token (fp32 math)
 // tokens > 0: only the first `tokens` tokens of every batch item (a sequence prefix; the buffers keep their geometry)

@@ -634,3 +634,56 @@ int mf_rows_to_f32(const ActView& x, float* dst, int batch, hipStream_t s) {
     MF_HIP(hipGetLastError());
     return MF_OK;
 }
+
+// ---- the transformer encoder layer of the sequence stages (Whisper encoder, wav2vec2 / HuBERT) -----------------------------------------------------------
+int mf_seq_conv_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int T_in, int act, int residual, int precision, int k, int stride, int pad) {
+    mf_conv2d_desc d{};
+    d.cin = cin; d.cout = cout; d.kh = 1; d.kw = k; d.stride_h = 1; d.stride_w = stride; d.pad_h = 0; d.pad_w = pad;
+    d.act = act; d.residual = residual; d.in_h = 1; d.in_w = T_in;
+    return mf_conv_plan_create(p, d, w, b, nullptr, nullptr, nullptr, nullptr, precision);
+}
+
+int mf_seq_block_create(NetStore& st, const SeqBlockWeights& w, int C, int ffn, int T, int precision, const SeqScratch& sc, SeqBlock* out) {
+    // one GEMM for q | k | v; without a key bias its rows of the concatenated bias stay zero
+    const size_t CC = (size_t)C * C;
+    std::vector<float> wqkv(3 * CC), bqkv((size_t)3 * C, 0.f);
+    std::copy(w.qw, w.qw + CC, wqkv.begin());
+    std::copy(w.kw, w.kw + CC, wqkv.begin() + CC);
+    std::copy(w.vw, w.vw + CC, wqkv.begin() + 2 * CC);
+    std::copy(w.qb, w.qb + C, bqkv.begin());
+    if (w.kb) std::copy(w.kb, w.kb + C, bqkv.begin() + C);
+    std::copy(w.vb, w.vb + C, bqkv.begin() + 2 * C);
+    SeqBlock L{};
+    L.qkv = st.new_plan(); L.out = st.new_plan(); L.fc1 = st.new_plan(); L.fc2 = st.new_plan();
+    int rc;
+    if ((rc = mf_seq_conv_plan(L.qkv, wqkv.data(), bqkv.data(), C, 3 * C, T, 0, 0, precision))) return rc;
+    if ((rc = mf_seq_conv_plan(L.out, w.ow, w.ob, C, C, T, 0, 1, precision))) return rc;          // + residual
+    if ((rc = mf_seq_conv_plan(L.fc1, w.f1w, w.f1b, C, ffn, T, 3, 0, precision))) return rc;      // GELU
+    if ((rc = mf_seq_conv_plan(L.fc2, w.f2w, w.f2b, ffn, C, T, 0, 1, precision))) return rc;      // + residual
+    if ((rc = mf_conv_bind(L.qkv, *sc.ln)) || (rc = mf_conv_bind(L.out, *sc.ao)) || (rc = mf_conv_bind(L.fc1, *sc.ln)) || (rc = mf_conv_bind(L.fc2, *sc.h1))) return rc;
+    if ((rc = st.upload(w.g1, C, &L.g1)) || (rc = st.upload(w.b1, C, &L.b1)) || (rc = st.upload(w.g2, C, &L.g2)) || (rc = st.upload(w.b2, C, &L.b2))) return rc;
+    *out = L;
+    return MF_OK;
+}
+
+static ActView whole(const ActBuf* b) { return ActView{b, 0, b->C}; }
+
+int mf_seq_block_front(const SeqBlock& L, SeqLn mode, const ActBuf* x, const SeqScratch& sc, float eps, int batch, hipStream_t s, int tc) {
+    int rc;
+    if (mode == SEQ_PRE_LN && (rc = mf_layernorm(whole(x), whole(sc.ln), L.g1, L.b1, eps, batch, s, tc))) return rc;
+    return mf_conv_launch(L.qkv, whole(mode == SEQ_PRE_LN ? sc.ln : x), whole(sc.qkv), ActView{}, batch, s, tc);
+}
+
+int mf_seq_block_back(const SeqBlock& L, SeqLn mode, const ActBuf* x, const ActBuf* y, const SeqScratch& sc, float eps, int batch, hipStream_t s, int tq) {
+    int rc;
+    if ((rc = mf_conv_launch(L.out, whole(sc.ao), whole(y), whole(x), batch, s, tq))) return rc;                      // y = x + out(ao)
+    if (mode == SEQ_PRE_LN) {
+        if ((rc = mf_layernorm(whole(y), whole(sc.ln), L.g2, L.b2, eps, batch, s, tq))) return rc;
+        if ((rc = mf_conv_launch(L.fc1, whole(sc.ln), whole(sc.h1), ActView{}, batch, s, tq))) return rc;
+        return mf_conv_launch(L.fc2, whole(sc.h1), whole(x), whole(y), batch, s, tq);                                 // x = y + fc2(.)
+    }
+    if ((rc = mf_layernorm(whole(y), whole(x), L.g1, L.b1, eps, batch, s, tq))) return rc;                            // x = LN1(y)
+    if ((rc = mf_conv_launch(L.fc1, whole(x), whole(sc.h1), ActView{}, batch, s, tq))) return rc;
+    if ((rc = mf_conv_launch(L.fc2, whole(sc.h1), whole(y), whole(x), batch, s, tq))) return rc;                      // y = x + fc2(.)
+    return mf_layernorm(whole(y), whole(x), L.g2, L.b2, eps, batch, s, tq);                                           // x = LN2(y)
+}

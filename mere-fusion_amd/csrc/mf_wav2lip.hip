@@ -232,9 +232,10 @@ extern "C" int mf_wav2lip_create(const mf_tensor* weights, int n_weights, int pr
     MF_REQUIRE(weights && out && n_weights > 0, "wav2lip_create: null argument");
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "wav2lip_create: unknown precision %d", precision);
     *out = nullptr;
-    MfStateDict sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "wav2lip_create: tensor %d has no name/data", i);
+    MfStateDict named, sd;
+    int rc = mf_sd_build(weights, n_weights, "wav2lip_create", {}, &named);
+    if (rc) return rc;
+    for (int i = 0; i < n_weights; ++i) {                                          // "module." goes wherever it stands in a name, not only in front
         std::string k = weights[i].name;
         size_t pos;
         while ((pos = k.find("module.")) != std::string::npos) k.erase(pos, 7);   // lipreal.py:48-49
@@ -243,7 +244,7 @@ extern "C" int mf_wav2lip_create(const mf_tensor* weights, int n_weights, int pr
     std::unique_ptr<mf_wav2lip> h(new mf_wav2lip());
     h->precision = precision;
     MF_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    int rc = h->graph.init(mf_no_graph_mode() != 1);   // eager under MF_NO_GRAPH=1 only: =2 (the MuseTalk nets' single-stream mode) leaves this handle on its graphs
+    rc = h->graph.init(mf_no_graph_mode() != 1);   // eager under MF_NO_GRAPH=1 only: =2 (the MuseTalk nets' single-stream mode) leaves this handle on its graphs
     if (rc) return rc;
     MF_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     MF_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));

@@ -48,15 +48,10 @@ __global__ __launch_bounds__(1024) void k_w2v_normalize(const float* __restrict_
     if (lo) lo += (int64_t)blockIdx.x * per_batch;
     for (int i = tid; i < n; i += 1024) {
         const float v = (float)(((double)x[i] - mean) * rstd);
-        unsigned u = __float_as_uint(v);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        const unsigned h = u >> 16;
+        unsigned h, l;
+        mf_split_bf16(v, h, l);
         hi[(int64_t)i * C] = (bf16_t)h;
-        if (lo) {
-            unsigned l = __float_as_uint(v - __uint_as_float(h << 16));
-            l += 0x7fffu + ((l >> 16) & 1u);
-            lo[(int64_t)i * C] = (bf16_t)(l >> 16);
-        }
+        if (lo) lo[(int64_t)i * C] = (bf16_t)l;
     }
 }
 
@@ -64,14 +59,12 @@ ActView V(ActBuf* b) { return ActView{b, 0, b->C}; }
 
 }  // namespace
 
-struct mf_wav2vec2 {
+// (the GraphRunner member goes before the NetStore base does: its graphs are dropped before the buffers they point into are freed)
+struct mf_wav2vec2 : NetStore {
     mf_wav2vec2_config cfg{};
     int precision = MF_PREC_BF16X3;
     int n = 0, cap = 1, T = 0;
     std::vector<int> frames;                       // sequence length after each conv layer
-    std::vector<std::unique_ptr<ActBuf>> bufs;
-    std::vector<std::unique_ptr<ConvPlan>> plans;
-    std::vector<float*> dev_f32;
     ActBuf* wav_in = nullptr;
     std::vector<ActBuf*> conv_out, conv_ln;
     std::vector<ConvPlan*> convs;
@@ -81,31 +74,9 @@ struct mf_wav2vec2 {
     ConvPlan *proj = nullptr, *head = nullptr;
     int vocab_pad = 0;                             // lm_head rows rounded up to a channel quad
     std::vector<ConvPlan*> pos;
-    struct Layer { ConvPlan *qkv, *out, *fc1, *fc2; float *g1, *b1, *g2, *b2; };
-    std::vector<Layer> layers;
+    std::vector<SeqBlock> layers;
 
-    ~mf_wav2vec2() {
-        for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) mf_actbuf_free(b.get());
-        for (float* f : dev_f32) (void)hipFree(f);
-    }
-    ActBuf* seq(int C, int T_, int halo = 0) {
-        bufs.emplace_back(new ActBuf());
-        ActBuf* b = bufs.back().get();
-        b->C = (C + 7) / 8 * 8; b->H = 1; b->W = T_; b->halo = halo;
-        return b;
-    }
-    int alloc() {
-        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap, precision); if (rc) return rc; }
-        return MF_OK;
-    }
-    ConvPlan* new_plan() { plans.emplace_back(new ConvPlan()); return plans.back().get(); }
-    int upload(const float* host, size_t cnt, float** dev) {
-        MF_HIP(hipMalloc(dev, cnt * sizeof(float)));
-        MF_HIP(hipMemcpy(*dev, host, cnt * sizeof(float), hipMemcpyHostToDevice));
-        dev_f32.push_back(*dev);
-        return MF_OK;
-    }
+    ActBuf* seq(int C, int T_, int halo = 0) { return buf((C + 7) / 8 * 8, 1, T_, halo); }
     int forward(const float* wav, int S, float* out, hipStream_t s);
     int body(int S, hipStream_t s);
     GraphRunner graph;   // the ~240 launches between the input normalisation and the output copy: one hipGraph per window count
@@ -114,13 +85,6 @@ struct mf_wav2vec2 {
 namespace {
 
 const mf_tensor* get(const MfStateDict& sd, const std::string& k, int64_t numel, bool required = true) { return mf_sd_find(sd, "wav2vec2", k, numel, required); }
-
-int conv1d_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int k, int stride, int pad, int T_in, int act, int residual, int precision) {
-    mf_conv2d_desc d{};
-    d.cin = cin; d.cout = cout; d.kh = 1; d.kw = k; d.stride_h = 1; d.stride_w = stride; d.pad_h = 0; d.pad_w = pad;
-    d.act = act; d.residual = residual; d.in_h = 1; d.in_w = T_in;
-    return mf_conv_plan_create(p, d, w, b, nullptr, nullptr, nullptr, nullptr, precision);
-}
 
 }  // namespace
 
@@ -155,28 +119,14 @@ int mf_wav2vec2::body(int S, hipStream_t s) {
     // them ("stable" pre-LN), which work in xa.  Every layer ends in the buffer it began in, so the last hidden state is xb whatever the depth.
     ActBuf *cur = cfg.stable_ln ? xa : xb, *oth = cfg.stable_ln ? xb : xa;
     if (!cfg.stable_ln && (rc = mf_layernorm(V(xa), V(xb), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
+    // pre-LN: h = x + attn(LN(x)); x = h + ff(LN(h)) (Wav2Vec2EncoderLayerStableLayerNorm).  post-LN: h = LN(x + attn(x)); x = LN(h + ff(h)) (Wav2Vec2EncoderLayer)
+    const SeqLn mode = cfg.stable_ln ? SEQ_PRE_LN : SEQ_POST_LN;
+    const SeqScratch scr{ln, qkv, ao, h1};
     for (auto& L : layers) {
-        if (cfg.stable_ln) {
-            // h = x + attn(LN(x)); x = h + ff(LN(h))   (Wav2Vec2EncoderLayerStableLayerNorm)
-            if ((rc = mf_layernorm(V(cur), V(ln), L.g1, L.b1, cfg.layer_norm_eps, S, s))) return rc;
-            if ((rc = mf_conv_launch(L.qkv, V(ln), V(qkv), ActView{}, S, s))) return rc;
-            if ((rc = mf_attention(ActView{qkv, 0, cfg.hidden}, ActView{qkv, cfg.hidden, cfg.hidden}, ActView{qkv, 2 * cfg.hidden, cfg.hidden}, V(ao), cfg.n_head, S,
-                                   precision, s))) return rc;
-            if ((rc = mf_conv_launch(L.out, V(ao), V(oth), V(cur), S, s))) return rc;
-            if ((rc = mf_layernorm(V(oth), V(ln), L.g2, L.b2, cfg.layer_norm_eps, S, s))) return rc;
-            if ((rc = mf_conv_launch(L.fc1, V(ln), V(h1), ActView{}, S, s))) return rc;
-            if ((rc = mf_conv_launch(L.fc2, V(h1), V(cur), V(oth), S, s))) return rc;
-        } else {
-            // h = LN(x + attn(x)); x = LN(h + ff(h))   (Wav2Vec2EncoderLayer)
-            if ((rc = mf_conv_launch(L.qkv, V(cur), V(qkv), ActView{}, S, s))) return rc;
-            if ((rc = mf_attention(ActView{qkv, 0, cfg.hidden}, ActView{qkv, cfg.hidden, cfg.hidden}, ActView{qkv, 2 * cfg.hidden, cfg.hidden}, V(ao), cfg.n_head, S,
-                                   precision, s))) return rc;
-            if ((rc = mf_conv_launch(L.out, V(ao), V(oth), V(cur), S, s))) return rc;
-            if ((rc = mf_layernorm(V(oth), V(cur), L.g1, L.b1, cfg.layer_norm_eps, S, s))) return rc;
-            if ((rc = mf_conv_launch(L.fc1, V(cur), V(h1), ActView{}, S, s))) return rc;
-            if ((rc = mf_conv_launch(L.fc2, V(h1), V(oth), V(cur), S, s))) return rc;
-            if ((rc = mf_layernorm(V(oth), V(cur), L.g2, L.b2, cfg.layer_norm_eps, S, s))) return rc;
-        }
+        if ((rc = mf_seq_block_front(L, mode, cur, scr, cfg.layer_norm_eps, S, s))) return rc;
+        if ((rc = mf_attention(ActView{qkv, 0, cfg.hidden}, ActView{qkv, cfg.hidden, cfg.hidden}, ActView{qkv, 2 * cfg.hidden, cfg.hidden}, V(ao), cfg.n_head, S,
+                               precision, s))) return rc;
+        if ((rc = mf_seq_block_back(L, mode, cur, oth, scr, cfg.layer_norm_eps, S, s))) return rc;
     }
     if (cfg.stable_ln && (rc = mf_layernorm(V(xa), V(xb), enc_g, enc_b, cfg.layer_norm_eps, S, s))) return rc;
     if (cfg.out_hidden) return MF_OK;
@@ -199,17 +149,11 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
     MF_REQUIRE(c.out_hidden || c.vocab > 0, "wav2vec2_create: vocab size missing");
     MF_REQUIRE(max_windows >= 1 && max_windows <= 64, "wav2vec2_create: 1..64 windows per call");
     MfStateDict sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "wav2vec2_create: tensor %d has no name/data", i);
-        std::string k = weights[i].name;
-        for (const char* pre : {"wav2vec2.", "hubert."})
-            if (k.rfind(pre, 0) == 0) k = k.substr(strlen(pre));
-        sd[k] = &weights[i];
-    }
+    int rc = mf_sd_build(weights, n_weights, "wav2vec2_create", {"wav2vec2.", "hubert."}, &sd);
+    if (rc) return rc;
     std::unique_ptr<mf_wav2vec2> h(new mf_wav2vec2());
     h->cfg = c; h->precision = precision; h->n = n_samples; h->cap = max_windows;
-    int rc = h->graph.init(mf_no_graph_mode() == 0);   // eager for any non-zero MF_NO_GRAPH
-    if (rc) return rc;
+    if ((rc = h->graph.init(mf_no_graph_mode() == 0))) return rc;   // eager for any non-zero MF_NO_GRAPH
     int L = n_samples;
     for (int i = 0; i < c.n_conv; ++i) {
         MF_REQUIRE(c.conv_kernel[i] >= 1 && c.conv_stride[i] >= 1 && c.conv_dim[i] % 8 == 0, "wav2vec2_create: bad conv layer %d", i);
@@ -223,7 +167,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
     h->fp_ln = h->seq(Cf, T); h->hid = h->seq(C, T, half);
     h->xa = h->seq(C, T); h->xb = h->seq(C, T); h->ln = h->seq(C, T); h->qkv = h->seq(3 * C, T); h->ao = h->seq(C, T); h->h1 = h->seq(c.ffn, T);
     if (!c.out_hidden) h->logit = h->seq(c.vocab, T);
-    if ((rc = h->alloc())) return rc;
+    if ((rc = h->alloc(h->cap, precision))) return rc;
 
     auto ln_pair = [&](const std::string& p, int ch, float** g, float** b) -> int {
         const mf_tensor *gw = get(sd, p + ".weight", ch), *gb = get(sd, p + ".bias", ch);
@@ -239,7 +183,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         const mf_tensor* b = c.conv_bias ? get(sd, p + ".conv.bias", cout) : nullptr;
         if (!w || (c.conv_bias && !b)) return MF_ERR_INVALID;
         ConvPlan* pl = h->new_plan();
-        if ((rc = conv1d_plan(pl, w->data, b ? b->data : nullptr, cin, cout, k, c.conv_stride[i], 0, i == 0 ? n_samples : h->frames[i - 1], 0, 0, precision))) return rc;
+        if ((rc = mf_seq_conv_plan(pl, w->data, b ? b->data : nullptr, cin, cout, i == 0 ? n_samples : h->frames[i - 1], 0, 0, precision, k, c.conv_stride[i]))) return rc;
         if ((rc = mf_conv_bind(pl, i == 0 ? *h->wav_in : *h->conv_ln[i - 1]))) return rc;
         h->convs.push_back(pl);
         float *g = nullptr, *bb = nullptr;
@@ -252,7 +196,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         const mf_tensor *w = get(sd, "feature_projection.projection.weight", (int64_t)C * Cf), *b = get(sd, "feature_projection.projection.bias", C);
         if (!w || !b) return MF_ERR_INVALID;
         h->proj = h->new_plan();
-        if ((rc = conv1d_plan(h->proj, w->data, b->data, Cf, C, 1, 1, 0, T, 0, 0, precision))) return rc;
+        if ((rc = mf_seq_conv_plan(h->proj, w->data, b->data, Cf, C, T, 0, 0, precision))) return rc;
         if ((rc = mf_conv_bind(h->proj, *h->fp_ln))) return rc;
     }
     // ---- positional convolution: weight_norm(dim = 2) folded on the host, one plan per channel group, a zero tap appended -----------
@@ -289,7 +233,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
                 }
             ConvPlan* pl = h->new_plan();
             // GELU in the epilogue, then + hidden (residual after the activation)
-            if ((rc = conv1d_plan(pl, wg.data(), b->data + g * gc, gc, gc, K + 1, 1, half, T, 3, 2, precision))) return rc;
+            if ((rc = mf_seq_conv_plan(pl, wg.data(), b->data + g * gc, gc, gc, T, 3, 2, precision, K + 1, 1, half))) return rc;
             if ((rc = mf_conv_bind(pl, *h->hid))) return rc;
             h->pos.push_back(pl);
         }
@@ -305,21 +249,14 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         const mf_tensor *f1w = get(sd, p + "feed_forward.intermediate_dense.weight", (int64_t)c.ffn * C), *f1b = get(sd, p + "feed_forward.intermediate_dense.bias", c.ffn);
         const mf_tensor *f2w = get(sd, p + "feed_forward.output_dense.weight", (int64_t)c.ffn * C), *f2b = get(sd, p + "feed_forward.output_dense.bias", C);
         if (!qw || !qb || !kw || !kb || !vw || !vb || !ow || !ob || !f1w || !f1b || !f2w || !f2b) return MF_ERR_INVALID;
-        std::vector<float> w((size_t)3 * C * C), b((size_t)3 * C);
-        std::copy(qw->data, qw->data + (size_t)C * C, w.begin());
-        std::copy(kw->data, kw->data + (size_t)C * C, w.begin() + (size_t)C * C);
-        std::copy(vw->data, vw->data + (size_t)C * C, w.begin() + (size_t)2 * C * C);
-        std::copy(qb->data, qb->data + C, b.begin());
-        std::copy(kb->data, kb->data + C, b.begin() + C);
-        std::copy(vb->data, vb->data + C, b.begin() + 2 * C);
-        mf_wav2vec2::Layer Ly{};
-        Ly.qkv = h->new_plan(); Ly.out = h->new_plan(); Ly.fc1 = h->new_plan(); Ly.fc2 = h->new_plan();
-        if ((rc = conv1d_plan(Ly.qkv, w.data(), b.data(), C, 3 * C, 1, 1, 0, T, 0, 0, precision))) return rc;
-        if ((rc = conv1d_plan(Ly.out, ow->data, ob->data, C, C, 1, 1, 0, T, 0, 1, precision))) return rc;
-        if ((rc = conv1d_plan(Ly.fc1, f1w->data, f1b->data, C, c.ffn, 1, 1, 0, T, 3, 0, precision))) return rc;
-        if ((rc = conv1d_plan(Ly.fc2, f2w->data, f2b->data, c.ffn, C, 1, 1, 0, T, 0, 1, precision))) return rc;
-        if ((rc = mf_conv_bind(Ly.qkv, *h->ln)) || (rc = mf_conv_bind(Ly.out, *h->ao)) || (rc = mf_conv_bind(Ly.fc1, *h->ln)) || (rc = mf_conv_bind(Ly.fc2, *h->h1))) return rc;
-        if ((rc = ln_pair(p + "layer_norm", C, &Ly.g1, &Ly.b1)) || (rc = ln_pair(p + "final_layer_norm", C, &Ly.g2, &Ly.b2))) return rc;
+        const mf_tensor *g1 = get(sd, p + "layer_norm.weight", C), *b1 = get(sd, p + "layer_norm.bias", C);
+        if (!g1 || !b1) return MF_ERR_INVALID;
+        const mf_tensor *g2 = get(sd, p + "final_layer_norm.weight", C), *b2 = get(sd, p + "final_layer_norm.bias", C);
+        if (!g2 || !b2) return MF_ERR_INVALID;
+        const SeqBlockWeights w{qw->data, qb->data, kw->data, kb->data, vw->data, vb->data, ow->data, ob->data, f1w->data, f1b->data, f2w->data, f2b->data,
+                                g1->data, b1->data, g2->data, b2->data};
+        SeqBlock Ly{};
+        if ((rc = mf_seq_block_create(*h, w, C, c.ffn, T, precision, SeqScratch{h->ln, h->qkv, h->ao, h->h1}, &Ly))) return rc;
         h->layers.push_back(Ly);
     }
     if (!c.out_hidden) {
@@ -330,7 +267,7 @@ extern "C" int mf_wav2vec2_create(const mf_wav2vec2_config* cfg, const mf_tensor
         std::copy(w->data, w->data + (size_t)c.vocab * C, wp.begin());
         std::copy(b->data, b->data + c.vocab, bp.begin());
         h->head = h->new_plan();
-        if ((rc = conv1d_plan(h->head, wp.data(), bp.data(), C, vp, 1, 1, 0, T, 0, 0, precision))) return rc;
+        if ((rc = mf_seq_conv_plan(h->head, wp.data(), bp.data(), C, vp, T, 0, 0, precision))) return rc;
         if ((rc = mf_conv_bind(h->head, *h->xb))) return rc;
         h->vocab_pad = vp;
     }

@@ -132,31 +132,22 @@ __global__ __launch_bounds__(256) void k_wlogmel_fin(const float* raw, const uns
     const float v = (fmaxf(raw[idx], floor_v) + 4.0f) / 4.0f;
     if (out_f32) out_f32[idx] = v;
     if (mel_hi) {
-        unsigned u = __float_as_uint(v);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        const unsigned h = u >> 16;
+        unsigned h, l;
+        mf_split_bf16(v, h, l);
         const int64_t o = tok0 + (int64_t)t * C + m;
         mel_hi[o] = (bf16_t)h;
-        if (mel_lo) {
-            unsigned l = __float_as_uint(v - __uint_as_float(h << 16));
-            l += 0x7fffu + ((l >> 16) & 1u);
-            mel_lo[o] = (bf16_t)(l >> 16);
-        }
+        if (mel_lo) mel_lo[o] = (bf16_t)l;
     }
 }
 
 }  // namespace
 
-struct mf_whisper {
+struct mf_whisper : NetStore {
     int precision = MF_PREC_BF16X3;
     int n_mels = 80, n_ctx = 1500, C = 384, n_head = 6, n_layer = 4;
-    std::vector<std::unique_ptr<ActBuf>> bufs;
-    std::vector<std::unique_ptr<ConvPlan>> plans;
-    std::vector<float*> dev_f32;
     ActBuf *mel_in, *c1, *pos, *xa, *xb, *ln, *qkv, *sc, *pm, *ao, *h1;
     ConvPlan *conv1, *conv2, *scores, *pv;
-    struct Layer { ConvPlan *qkv, *out, *fc1, *fc2; float *ln1_g, *ln1_b, *ln2_g, *ln2_b; };
-    std::vector<Layer> layers;
+    std::vector<SeqBlock> layers;
     float* raw = nullptr;       // [cap][80][3000] fp32 scratch of the log-mel
     unsigned* gmax = nullptr;   // [cap]
     int cap = 1;                // windows one call can encode (mf_whisper_set_batch)
@@ -164,21 +155,14 @@ struct mf_whisper {
     bool fused_attn = true;     // one k_attention launch per layer; false (set by mf_whisper_create for a head dim mf_attention_supported declines,
                                 // nothing else switches it): per-head pack + GEMM + softmax + pack + GEMM
 
-    ~mf_whisper() {
-        for (auto& p : plans) mf_conv_plan_destroy(p.get());
-        for (auto& b : bufs) mf_actbuf_free(b.get());
-        for (float* f : dev_f32) (void)hipFree(f);
+    ~mf_whisper() {   // raw / gmax move with the capacity, so they are not in the store's list
         if (raw) (void)hipFree(raw);
         if (gmax) (void)hipFree(gmax);
     }
-    ActBuf* seq(int C_, int T) {
-        bufs.emplace_back(new ActBuf());
-        ActBuf* b = bufs.back().get();
-        b->C = C_; b->H = 1; b->W = T; b->halo = 1;
-        return b;
-    }
+    ActBuf* seq(int C_, int T) { return buf(C_, 1, T, 1); }
     int alloc() {
-        for (auto& b : bufs) { const int rc = mf_actbuf_alloc(b.get(), cap, precision); if (rc) return rc; }
+        int rc = NetStore::alloc(cap, precision);
+        if (rc) return rc;
         if (raw) (void)hipFree(raw);
         if (gmax) (void)hipFree(gmax);
         raw = nullptr; gmax = nullptr;
@@ -190,18 +174,11 @@ struct mf_whisper {
             const size_t n1 = pos_host.size();
             MF_HIP(hipMalloc(&d, (size_t)cap * n1 * sizeof(float)));
             for (int b = 0; b < cap; ++b) MF_HIP(hipMemcpy(d + (size_t)b * n1, pos_host.data(), n1 * sizeof(float), hipMemcpyHostToDevice));
-            const int rc = mf_nchw_to_act(d, C, *pos, cap, nullptr);
+            rc = mf_nchw_to_act(d, C, *pos, cap, nullptr);
             MF_HIP(hipDeviceSynchronize());
             (void)hipFree(d);
             if (rc) return rc;
         }
-        return MF_OK;
-    }
-    ConvPlan* new_plan() { plans.emplace_back(new ConvPlan()); return plans.back().get(); }
-    int upload(const float* host, size_t n, float** dev) {
-        MF_HIP(hipMalloc(dev, n * sizeof(float)));
-        MF_HIP(hipMemcpy(*dev, host, n * sizeof(float), hipMemcpyHostToDevice));
-        dev_f32.push_back(*dev);
         return MF_OK;
     }
     int log_mel_into_input(const float* wav, int n, float* out_f32, bool to_input, hipStream_t s, int S = 1);
@@ -213,13 +190,6 @@ namespace {
 ActView W(ActBuf* b) { return ActView{b, 0, b->C}; }
 
 const mf_tensor* get(const MfStateDict& sd, const std::string& k, int64_t numel) { return mf_sd_find(sd, "whisper", k, numel); }
-
-int linear_plan(ConvPlan* p, const float* w, const float* b, int cin, int cout, int T, int act, int residual, int precision) {
-    mf_conv2d_desc d{};
-    d.cin = cin; d.cout = cout; d.kh = d.kw = 1; d.stride_h = d.stride_w = 1; d.act = act; d.residual = residual;
-    d.in_h = 1; d.in_w = T;
-    return mf_conv_plan_create(p, d, w, b, nullptr, nullptr, nullptr, nullptr, precision);
-}
 
 }  // namespace
 
@@ -277,11 +247,10 @@ int mf_whisper::encode(float* emb, hipStream_t s, int S, int ctx, int keep) {
     ActBuf* y = xb;
     const int dh = C / n_head;
     const float scale = 1.0f / std::sqrt((float)dh);        // (dh^-0.25 on q) * (dh^-0.25 on k), model.py:91-93
+    const SeqScratch scr{ln, qkv, ao, h1};
     for (int l = 0; l < n_layer; ++l) {
-        Layer& L = layers[l];
         const int tq = (keep > 0 && l == n_layer - 1) ? keep : tc;      // rows the rest of this block computes (0 = all)
-        if ((rc = mf_layernorm(W(x), W(ln), L.ln1_g, L.ln1_b, 1e-5f, S, s, tc))) return rc;
-        if ((rc = mf_conv_launch(L.qkv, W(ln), W(qkv), ActView{}, S, s, tc))) return rc;
+        if ((rc = mf_seq_block_front(layers[l], SEQ_PRE_LN, x, scr, 1e-5f, S, s, tc))) return rc;
         // softmax(q k^T * dh^-0.5) v, all heads in one fused launch (mf_attn.hip); model.py:91-93 applies the same
         // scale as dh^-0.25 on q and on k
         if (fused_attn) {
@@ -298,10 +267,7 @@ int mf_whisper::encode(float* emb, hipStream_t s, int S, int ctx, int keep) {
                 if ((rc = mf_conv_launch(pv, W(pm), ActView{ao, h * dh, dh}, ActView{}, 1, s))) return rc;
             }
         }
-        if ((rc = mf_conv_launch(L.out, W(ao), W(y), W(x), S, s, tq))) return rc;                 // x + attn(ln(x))
-        if ((rc = mf_layernorm(W(y), W(ln), L.ln2_g, L.ln2_b, 1e-5f, S, s, tq))) return rc;
-        if ((rc = mf_conv_launch(L.fc1, W(ln), W(h1), ActView{}, S, s, tq))) return rc;            // gelu(fc1)
-        if ((rc = mf_conv_launch(L.fc2, W(h1), W(x), W(y), S, s, tq))) return rc;                  // y + fc2(.) -> x
+        if ((rc = mf_seq_block_back(layers[l], SEQ_PRE_LN, x, y, scr, 1e-5f, S, s, tq))) return rc;   // y = x + attn(ln(x)); x = y + mlp(ln(y))
         if ((rc = emit(x, l + 1))) return rc;
     }
     return MF_OK;
@@ -312,13 +278,9 @@ extern "C" int mf_whisper_create(const mf_tensor* weights, int n_weights, int n_
     MF_REQUIRE(weights && out && n_weights > 0 && n_head > 0, "whisper_create: bad argument");
     MF_REQUIRE(precision == MF_PREC_BF16 || precision == MF_PREC_BF16X3, "whisper_create: unknown precision %d", precision);
     *out = nullptr;
-    std::map<std::string, const mf_tensor*> sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "whisper_create: tensor %d has no name/data", i);
-        std::string k = weights[i].name;
-        if (k.rfind("encoder.", 0) == 0) k = k.substr(8);   // keys of a full Whisper checkpoint
-        sd[k] = &weights[i];
-    }
+    MfStateDict sd;
+    int rc = mf_sd_build(weights, n_weights, "whisper_create", {"encoder."}, &sd);   // "encoder.": keys of a full Whisper checkpoint
+    if (rc) return rc;
     auto it = sd.find("conv1.weight");
     MF_REQUIRE(it != sd.end() && it->second->ndim == 3 && it->second->shape[2] == 3, "whisper_create: conv1.weight [C, n_mels, 3] missing");
     std::unique_ptr<mf_whisper> h(new mf_whisper());
@@ -353,25 +315,21 @@ extern "C" int mf_whisper_create(const mf_tensor* weights, int n_weights, int n_
                 pe[(size_t)(c + C / 2) * T + t] = std::cos(st);
             }
     }
-    int rc = h->alloc();
-    if (rc) return rc;
+    if ((rc = h->alloc())) return rc;
 
     // conv1 / conv2: Conv1d(k=3) as a (1 x 3) convolution over the frame axis
     {
         const mf_tensor *w1 = get(sd, "conv1.weight", (int64_t)C * W_MELS * 3), *b1 = get(sd, "conv1.bias", C);
         const mf_tensor *w2 = get(sd, "conv2.weight", (int64_t)C * C * 3), *b2 = get(sd, "conv2.bias", C);
         if (!w1 || !b1 || !w2 || !b2) return MF_ERR_INVALID;
-        mf_conv2d_desc d{};
-        d.cin = W_MELS; d.cout = C; d.kh = 1; d.kw = 3; d.stride_h = d.stride_w = 1; d.pad_h = 0; d.pad_w = 1;
-        d.act = 3; d.in_h = 1; d.in_w = W_FRAMES;
         h->conv1 = h->new_plan();
-        if ((rc = mf_conv_plan_create(h->conv1, d, w1->data, b1->data, nullptr, nullptr, nullptr, nullptr, precision))) return rc;
+        if ((rc = mf_seq_conv_plan(h->conv1, w1->data, b1->data, W_MELS, C, W_FRAMES, 3, 0, precision, 3, 1, 1))) return rc;
         if ((rc = mf_conv_bind(h->conv1, *h->mel_in))) return rc;
-        d.cin = C; d.stride_w = 2; d.residual = 2;   // x = gelu(conv2(x)) + positional_embedding (model.py:152-156)
-        h->conv2 = h->new_plan();
-        if ((rc = mf_conv_plan_create(h->conv2, d, w2->data, b2->data, nullptr, nullptr, nullptr, nullptr, precision))) return rc;
+        h->conv2 = h->new_plan();   // x = gelu(conv2(x)) + positional_embedding (model.py:152-156)
+        if ((rc = mf_seq_conv_plan(h->conv2, w2->data, b2->data, C, C, W_FRAMES, 3, 2, precision, 3, 2, 1))) return rc;
         if ((rc = mf_conv_bind(h->conv2, *h->c1))) return rc;
     }
+    const SeqScratch scr{h->ln, h->qkv, h->ao, h->h1};
     for (int l = 0; l < L; ++l) {
         const std::string p = "blocks." + std::to_string(l) + ".";
         const mf_tensor *qw = get(sd, p + "attn.query.weight", (int64_t)C * C), *qb = get(sd, p + "attn.query.bias", C);
@@ -383,23 +341,11 @@ extern "C" int mf_whisper_create(const mf_tensor* weights, int n_weights, int n_
         const mf_tensor *f2w = get(sd, p + "mlp.2.weight", (int64_t)4 * C * C), *f2b = get(sd, p + "mlp.2.bias", C);
         const mf_tensor *g2 = get(sd, p + "mlp_ln.weight", C), *b2 = get(sd, p + "mlp_ln.bias", C);
         if (!qw || !qb || !kw || !vw || !vb || !ow || !ob || !g1 || !b1 || !f1w || !f1b || !f2w || !f2b || !g2 || !b2) return MF_ERR_INVALID;
-        // one GEMM for q | k | v (key has no bias, model.py:62)
-        std::vector<float> w((size_t)3 * C * C), b((size_t)3 * C, 0.f);
-        std::copy(qw->data, qw->data + (size_t)C * C, w.begin());
-        std::copy(kw->data, kw->data + (size_t)C * C, w.begin() + (size_t)C * C);
-        std::copy(vw->data, vw->data + (size_t)C * C, w.begin() + (size_t)2 * C * C);
-        std::copy(qb->data, qb->data + C, b.begin());
-        std::copy(vb->data, vb->data + C, b.begin() + 2 * C);
-        mf_whisper::Layer Ly{};
-        Ly.qkv = h->new_plan(); Ly.out = h->new_plan(); Ly.fc1 = h->new_plan(); Ly.fc2 = h->new_plan();
-        if ((rc = linear_plan(Ly.qkv, w.data(), b.data(), C, 3 * C, T, 0, 0, precision))) return rc;
-        if ((rc = linear_plan(Ly.out, ow->data, ob->data, C, C, T, 0, 1, precision))) return rc;
-        if ((rc = linear_plan(Ly.fc1, f1w->data, f1b->data, C, 4 * C, T, 3, 0, precision))) return rc;
-        if ((rc = linear_plan(Ly.fc2, f2w->data, f2b->data, 4 * C, C, T, 0, 1, precision))) return rc;
-        if ((rc = mf_conv_bind(Ly.qkv, *h->ln)) || (rc = mf_conv_bind(Ly.out, *h->ao)) || (rc = mf_conv_bind(Ly.fc1, *h->ln)) ||
-            (rc = mf_conv_bind(Ly.fc2, *h->h1))) return rc;
-        if ((rc = h->upload(g1->data, C, &Ly.ln1_g)) || (rc = h->upload(b1->data, C, &Ly.ln1_b)) ||
-            (rc = h->upload(g2->data, C, &Ly.ln2_g)) || (rc = h->upload(b2->data, C, &Ly.ln2_b))) return rc;
+        // key has no bias (model.py:62)
+        const SeqBlockWeights w{qw->data, qb->data, kw->data, nullptr, vw->data, vb->data, ow->data, ob->data, f1w->data, f1b->data, f2w->data, f2b->data,
+                                g1->data, b1->data, g2->data, b2->data};
+        SeqBlock Ly{};
+        if ((rc = mf_seq_block_create(*h, w, C, 4 * C, T, precision, scr, &Ly))) return rc;
         h->layers.push_back(Ly);
     }
     h->scores = h->new_plan(); h->pv = h->new_plan();

@@ -41,11 +41,7 @@ __device__ __forceinline__ bool row_idle(const Rows& r, int m) { return r.done &
 
 __device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float round_bf16(float v) {
-    unsigned u = __float_as_uint(v);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xffff0000u);
-}
+__device__ __forceinline__ float round_bf16(float v) { return bf_lo(mf_bf16_rne(v)); }
 __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -418,10 +414,8 @@ extern "C" int mf_whisper_decoder_create(const mf_tensor* weights, int n_weights
     MF_REQUIRE(max_batch >= 1 && max_batch <= MAX_DEC_BATCH, "whisper_decoder_create: max_batch = %d, 1..%d sequences decode together", max_batch, MAX_DEC_BATCH);
     *out = nullptr;
     MfStateDict sd;
-    for (int i = 0; i < n_weights; ++i) {
-        MF_REQUIRE(weights[i].name && weights[i].data, "whisper_decoder_create: tensor %d has no name/data", i);
-        sd[weights[i].name] = &weights[i];
-    }
+    int rc = mf_sd_build(weights, n_weights, "whisper_decoder_create", {}, &sd);
+    if (rc) return rc;
     auto it = sd.find("decoder.token_embedding.weight");
     MF_REQUIRE(it != sd.end() && it->second->ndim == 2, "whisper_decoder_create: decoder.token_embedding.weight [n_vocab, n_state] missing");
     auto ip = sd.find("decoder.positional_embedding");
@@ -441,7 +435,6 @@ extern "C" int mf_whisper_decoder_create(const mf_tensor* weights, int n_weights
     h->n_layer = L;
     const char* who = "whisper_decoder";
     auto get = [&](const std::string& k, int64_t n) { return mf_sd_find(sd, who, k, n); };
-    int rc;
     const size_t CC = (size_t)C * C;
     if ((rc = h->upload_planes(it->second->data, (size_t)h->n_vocab * C, &h->emb))) return rc;
     if ((rc = h->upload(ip->second->data, (size_t)h->n_ctx * C, &h->pos_emb))) return rc;

@@ -241,3 +241,26 @@ def test_hip_whisper_no_stale_state(lib_built, wsd):
     used.audio2feat_windows_device(torch.from_numpy(np.stack([long_, long_[::-1].copy(), long_ * 0.5])))      # set_batch(3): the workspace is reallocated
     assert torch.equal(used.audio2feat_device(short).cpu(), want)
     assert torch.equal(used.log_mel_spectrogram(short).cpu(), want_mel)
+
+
+@pytest.mark.gpu
+def test_hip_per_head_attention_fallback_vs_oracle(lib_built):
+    """Head width 48 (n_state 96, 2 heads: a multiple of 8 that mf_attention_supported declines) puts the handle on the per-head attention -- pack K, scores GEMM,
+    row softmax, pack V^T, weights x V GEMM -- which serves mf_whisper_encode_audio alone.  One window of 3200 samples, one layer: both hidden states of all
+    1500 tokens against the oracle, at the tolerance of test_hip_audio2feat_vs_oracle_and_golden."""
+    from mere_fusion_amd import _lib
+    from mere_fusion_amd.musetalk.whisper.audio2feature import Audio2Feature
+    sd = W.make_whisper_encoder_state_dict(0, dict(W.WHISPER_TINY, n_audio_state=96, n_audio_head=2, n_audio_layer=1))
+    a2f = Audio2Feature(state_dict=sd, n_head=2, precision="bf16x3")
+    assert (a2f.n_layer, a2f.n_ctx, a2f.n_state) == (1, 1500, 96)
+    wav = W.make_speech_like_wav(3200, 0)
+    dev = a2f._wav(wav)
+    emb = torch.empty((2, 1500, 96), dtype=torch.float32, device=dev.device)
+    _lib.check(_lib.lib().mf_whisper_encode_audio(a2f._h, dev.data_ptr(), dev.numel(), emb.data_ptr(), _lib.stream_ptr(dev.device)), "whisper_encode_audio")
+    _, want = R.encoder_forward(sd, R.pad_or_trim(R.log_mel_spectrogram(wav))[None], n_head=2, n_layer=1)          # (1, 2, 1500, 96)
+    err = np.abs(emb.cpu().numpy() - want[0].numpy())
+    for l in range(2):
+        print(f"[whisper per-head attention] hidden state {l}: L-inf vs oracle {err[l].max():.2e} (tol {TOL_FEAT})")
+        assert err[l].max() <= TOL_FEAT, (l, err[l].max())
+    with pytest.raises(RuntimeError, match="needs the fused attention kernel"):      # the batched / pruned call is the fused kernel's: the handle is on the fallback
+        a2f.audio2feat(wav)
