@@ -642,11 +642,15 @@ int mf_nerf_loop_init(const NerfLoop& l, const NerfRaySums& r, float* nears, con
     MF_HIP(hipGetLastError());
     return MF_OK;
 }
+// Whether a march launch takes the FAST kernel: one cascade and a power-of-two grid up to 128 (k_loop_march's spread table).  allow_env: MF_NERF_MARCH=generic forces
+// the reference-shaped index arithmetic (tests); read per call
+static bool nerf_march_fast(uint32_t cascades, uint32_t grid_size, bool allow_env) {
+    const char* e = allow_env ? getenv("MF_NERF_MARCH") : nullptr;
+    return cascades == 1 && (grid_size & (grid_size - 1)) == 0 && grid_size <= 128 && !(e && !strcmp(e, "generic"));
+}
 // march (the round's n_alive / n_step were set by k_loop_init or the previous round's tail)
 int mf_nerf_loop_march(const NerfLoop& l, int round, float bound, hipStream_t s) {
-    const char* e = getenv("MF_NERF_MARCH");                                 // "generic" forces the reference-shaped index arithmetic (tests); read per call
-    const bool fast = l.cascades == 1 && (l.grid_size & (l.grid_size - 1)) == 0 && l.grid_size <= 128 && !(e && !strcmp(e, "generic"));   // 128: k_loop_march's spread table
-    const auto kernel = fast ? k_loop_march<true> : k_loop_march<false>;
+    const auto kernel = nerf_march_fast(l.cascades, l.grid_size, true) ? k_loop_march<true> : k_loop_march<false>;
     hipLaunchKernelGGL(kernel, dim3(blocks(l.N)), dim3(NT), 0, s, l.ctl, l.alive[round & 1], l.rays_t, l.rays_o, l.rays_d, bound,
                        l.dt_gamma, (uint32_t)l.max_steps, l.cascades, l.grid_size, l.bitfield, l.fars, l.xyzs, l.dirs, l.deltas);
     MF_HIP(hipGetLastError());
@@ -670,7 +674,7 @@ extern "C" int mf_nerf_loop_march_debug(const int* ctl_dev, const int* rays_aliv
     MF_REQUIRE(max_steps > 0 && cascades >= 1 && cascades <= 8 && grid_size >= 2 && grid_size <= 128, "nerf_loop_march_debug: max_steps=%u cascades=%u grid=%u",
                max_steps, cascades, grid_size);
     MF_REQUIRE(variant >= 0 && variant <= 2, "nerf_loop_march_debug: variant %d (0 the production rule, 1 generic, 2 FAST)", variant);
-    const bool fast_ok = cascades == 1 && (grid_size & (grid_size - 1)) == 0 && grid_size <= 128;        // mf_nerf_loop_march's rule
+    const bool fast_ok = nerf_march_fast(cascades, grid_size, false);
     MF_REQUIRE(variant != 2 || fast_ok, "nerf_loop_march_debug: FAST needs one cascade and a power-of-two grid up to 128 (cascades=%u grid=%u)", cascades, grid_size);
     if (n_rays == 0) return MF_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -713,9 +717,7 @@ int mf_nerf_batch_init(const NerfBatchLoop& b, const float* aabb, float min_near
     return MF_OK;
 }
 int mf_nerf_batch_march(const NerfBatchLoop& b, int round, float bound, hipStream_t s) {
-    const char* e = getenv("MF_NERF_MARCH");                                 // as mf_nerf_loop_march
-    const bool fast = b.cascades == 1 && (b.grid_size & (b.grid_size - 1)) == 0 && b.grid_size <= 128 && !(e && !strcmp(e, "generic"));
-    const auto kernel = fast ? k_loop_march_batch<true> : k_loop_march_batch<false>;
+    const auto kernel = nerf_march_fast(b.cascades, b.grid_size, true) ? k_loop_march_batch<true> : k_loop_march_batch<false>;
     hipLaunchKernelGGL(kernel, dim3(blocks(b.N), b.n_frames), dim3(NT), 0, s, b.frames, round & 1, bound, b.dt_gamma, (uint32_t)b.max_steps, b.cascades,
                        b.grid_size, b.bitfield);
     MF_HIP(hipGetLastError());

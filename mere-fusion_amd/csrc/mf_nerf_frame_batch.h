@@ -3,6 +3,7 @@
 // the torso handle is defined) needs of the batch handle.
 #pragma once
 #include "mf_nerf_host.h"
+#include "mf_nerf_table_ring.h"
 
 struct NerfBgFrame {                     // k_nerf_frame_background_batch (mf_nerf_frame.hip)
     const uint8_t* torso;
@@ -31,11 +32,6 @@ int mf_nerf_frame_background_batch_launch(const NerfBgFrame* tab_dev, int n_fram
 int mf_nerf_frame_out_batch_launch(const NerfOutFrame* tab_dev, int n_frames, int h, int w, int H, int W, int FH, int FW, int srgb, uint8_t* out, hipStream_t s);
 int mf_nerf_torso_batch_launch(const NerfTorsoConsts& t, const NerfTorsoFrame* tab_dev, int n_frames, const float* density, int N, hipStream_t s);
 
-// ---- the handle's ring, for the entry points that fill a table ------------------------------------------------------------------------------------
+// ---- the handle's limits and ring, for the entry points that fill a table ---------------------------------------------------------------------------
 int mf_nerf_frame_batch_limits(const mf_nerf_frame_batch* h, int* max_frames, int* max_pixels);
-// the next ring entry (allocating the ring at the first call; waits only when every entry belongs to a call still in flight): its pinned table to fill
-int mf_nerf_frame_batch_acquire(mf_nerf_frame_batch* h, int* slot, void** tab_host);
-// the table's first `bytes` to the entry's device copy on `s`; *tab_dev is what the kernel reads
-int mf_nerf_frame_batch_upload(mf_nerf_frame_batch* h, int slot, size_t bytes, hipStream_t s, const void** tab_dev);
-// behind the call's last launch (also after a failed one: the copy is on the stream)
-int mf_nerf_frame_batch_release(mf_nerf_frame_batch* h, int slot, hipStream_t s);
+TableRing& mf_nerf_frame_batch_ring(mf_nerf_frame_batch* h);           // 16 entries of max_frames x NERF_FRAME_BATCH_ENTRY bytes, allocated at the first call

@@ -3,9 +3,8 @@
 // (mf_nerf_frame_batch_out).  Host code only: each frame-indexed kernel stands beside the single-frame kernel whose per-pixel function it calls
 // (mf_nerf_frame.hip, mf_nerf_torso.hip), so frame i of a call is the same bits as the single-frame entry point gives.
 //
-// The handle owns a ring of frame tables, as mf_nerf_head_batch does: a call fills the next table in pinned host memory, copies it to the entry's device table on
-// the caller's stream and records an event behind its launch; the entry is written again only after that event.  A serving step makes up to three calls per group
-// of frames, so the ring is 16 deep: nothing waits for the host unless 16 calls are in flight.  The ring is allocated at the first accepted call, so creating a
+// The handle owns a TableRing of frame tables (mf_nerf_table_ring.h), the type mf_nerf_head_batch holds for its own.  A serving step makes up to three calls per
+// group of frames, so the ring is 16 deep: nothing waits for the host unless 16 calls are in flight.  The ring is allocated at the first accepted call, so creating a
 // handle and every refusal touch no device.
 #include "mf_nerf_frame_batch.h"
 
@@ -16,19 +15,7 @@ constexpr int MAX_FRAMES = 64;           // as mf_nerf_head_batch: the frames of
 
 struct mf_nerf_frame_batch {
     int max_frames = 0, max_pixels = 0;
-    bool ready = false;
-    void* tab_host[RING] = {};           // pinned staging, max_frames x NERF_FRAME_BATCH_ENTRY bytes each
-    void* tab_dev[RING] = {};
-    hipEvent_t done[RING] = {};          // behind the launch of the call that used the entry
-    bool used[RING] = {};
-    int next = 0;
-    ~mf_nerf_frame_batch() {
-        for (int r = 0; r < RING; ++r) {
-            if (done[r]) { if (used[r]) (void)hipEventSynchronize(done[r]); (void)hipEventDestroy(done[r]); }
-            if (tab_host[r]) (void)hipHostFree(tab_host[r]);
-            if (tab_dev[r]) (void)hipFree(tab_dev[r]);
-        }
-    }
+    TableRing ring{RING};                // entries of max_frames x NERF_FRAME_BATCH_ENTRY bytes
 };
 
 extern "C" int mf_nerf_frame_batch_create(int max_frames, int max_pixels, mf_nerf_frame_batch** out) {
@@ -38,6 +25,7 @@ extern "C" int mf_nerf_frame_batch_create(int max_frames, int max_pixels, mf_ner
     MF_REQUIRE(max_pixels >= 1, "nerf_frame_batch_create: max_pixels %d", max_pixels);
     mf_nerf_frame_batch* h = new mf_nerf_frame_batch();
     h->max_frames = max_frames; h->max_pixels = max_pixels;
+    h->ring.bytes = (size_t)max_frames * NERF_FRAME_BATCH_ENTRY;
     *out = h;
     return MF_OK;
 }
@@ -50,34 +38,7 @@ int mf_nerf_frame_batch_limits(const mf_nerf_frame_batch* h, int* max_frames, in
     return MF_OK;
 }
 
-int mf_nerf_frame_batch_acquire(mf_nerf_frame_batch* h, int* slot, void** tab_host) {
-    if (!h->ready) {
-        const size_t bytes = (size_t)h->max_frames * NERF_FRAME_BATCH_ENTRY;
-        for (int r = 0; r < RING; ++r) {
-            if (!h->tab_host[r]) MF_HIP(hipHostMalloc(&h->tab_host[r], bytes, hipHostMallocDefault));
-            if (!h->tab_dev[r]) MF_HIP(hipMalloc(&h->tab_dev[r], bytes));
-            if (!h->done[r]) MF_HIP(hipEventCreateWithFlags(&h->done[r], hipEventDisableTiming));
-        }
-        h->ready = true;
-    }
-    const int r = h->next;
-    if (h->used[r]) MF_HIP(hipEventSynchronize(h->done[r]));           // returns at once unless RING calls are in flight
-    h->next = (r + 1) % RING;
-    *slot = r; *tab_host = h->tab_host[r];
-    return MF_OK;
-}
-
-int mf_nerf_frame_batch_upload(mf_nerf_frame_batch* h, int slot, size_t bytes, hipStream_t s, const void** tab_dev) {
-    MF_HIP(hipMemcpyAsync(h->tab_dev[slot], h->tab_host[slot], bytes, hipMemcpyHostToDevice, s));
-    h->used[slot] = true;
-    *tab_dev = h->tab_dev[slot];
-    return MF_OK;
-}
-
-int mf_nerf_frame_batch_release(mf_nerf_frame_batch* h, int slot, hipStream_t s) {
-    MF_HIP(hipEventRecord(h->done[slot], s));
-    return MF_OK;
-}
+TableRing& mf_nerf_frame_batch_ring(mf_nerf_frame_batch* h) { return h->ring; }
 
 // what every call checks first, before anything touches a device
 static int check_call(const char* who, const mf_nerf_frame_batch* h, const void* descs, int n_frames) {
@@ -96,16 +57,12 @@ extern "C" int mf_nerf_frame_batch_background(mf_nerf_frame_batch* h, const mf_n
         MF_REQUIRE(((uintptr_t)descs[i].torso_rgba & 3) == 0, "nerf_frame_batch_background: frame %d: the RGBA image must be 4-byte aligned", i);
     }
     hipStream_t s = (hipStream_t)stream;
-    int slot;
-    void* host;
-    if ((rc = mf_nerf_frame_batch_acquire(h, &slot, &host))) return rc;
-    NerfBgFrame* tab = (NerfBgFrame*)host;
-    for (int i = 0; i < n_frames; ++i) tab[i] = NerfBgFrame{descs[i].torso_rgba, descs[i].bg_image, descs[i].bg_color, descs[i].bg_const, descs[i].half_mode != 0};
-    const void* dev;
-    if ((rc = mf_nerf_frame_batch_upload(h, slot, (size_t)n_frames * sizeof(NerfBgFrame), s, &dev))) return rc;
-    rc = mf_nerf_frame_background_batch_launch((const NerfBgFrame*)dev, n_frames, H * W, s);
-    const int rc2 = mf_nerf_frame_batch_release(h, slot, s);
-    return rc ? rc : rc2;
+    return h->ring.call<NerfBgFrame>(
+        n_frames, s,
+        [&](NerfBgFrame* tab) {
+            for (int i = 0; i < n_frames; ++i) tab[i] = NerfBgFrame{descs[i].torso_rgba, descs[i].bg_image, descs[i].bg_color, descs[i].bg_const, descs[i].half_mode != 0};
+        },
+        [&](const NerfBgFrame* dev) { return mf_nerf_frame_background_batch_launch(dev, n_frames, H * W, s); });
 }
 
 extern "C" int mf_nerf_frame_batch_out(mf_nerf_frame_batch* h, const mf_nerf_out_desc* descs, int n_frames, int rh, int rw, int H, int W, int FH, int FW,
@@ -129,14 +86,11 @@ extern "C" int mf_nerf_frame_batch_out(mf_nerf_frame_batch* h, const mf_nerf_out
                        "nerf_frame_batch_out: frame %d: a %d x %d frame at (%d, %d) leaves the %d x %d body frame", i, W, H, d.x0, d.y0, FW, FH);
     }
     hipStream_t s = (hipStream_t)stream;
-    int slot;
-    void* host;
-    if ((rc = mf_nerf_frame_batch_acquire(h, &slot, &host))) return rc;
-    NerfOutFrame* tab = (NerfOutFrame*)host;
-    for (int i = 0; i < n_frames; ++i) tab[i] = NerfOutFrame{descs[i].render, descs[i].body_bgr, descs[i].render ? descs[i].x0 : 0, descs[i].render ? descs[i].y0 : 0};
-    const void* dev;
-    if ((rc = mf_nerf_frame_batch_upload(h, slot, (size_t)n_frames * sizeof(NerfOutFrame), s, &dev))) return rc;
-    rc = mf_nerf_frame_out_batch_launch((const NerfOutFrame*)dev, n_frames, rh, rw, H, W, FH, FW, linear_to_srgb, frames_rgb, s);
-    const int rc2 = mf_nerf_frame_batch_release(h, slot, s);
-    return rc ? rc : rc2;
+    return h->ring.call<NerfOutFrame>(
+        n_frames, s,
+        [&](NerfOutFrame* tab) {
+            for (int i = 0; i < n_frames; ++i)
+                tab[i] = NerfOutFrame{descs[i].render, descs[i].body_bgr, descs[i].render ? descs[i].x0 : 0, descs[i].render ? descs[i].y0 : 0};
+        },
+        [&](const NerfOutFrame* dev) { return mf_nerf_frame_out_batch_launch(dev, n_frames, rh, rw, H, W, FH, FW, linear_to_srgb, frames_rgb, s); });
 }

@@ -6,44 +6,15 @@
 // reference allows, so only as many rounds as the frames before needed are enqueued as launches and ONE tail launch (k_loop_tail, mf_nerf_fused.hip) stands for
 // the rest: it finds the loop ended, or runs the remaining rounds itself -- no round is ever dropped, and nothing waits for the host.  The whole frame is
 // capturable as one hipGraph.
-#include "mf_nerf_host.h"
-#include "mf_nerf_march.h"
-#include <cstdlib>
-#include <cstring>
+#include "mf_nerf_head_slot.h"
 
-struct mf_nerf_head {
-    mf_nerf_field* field = nullptr;
-    int cap = 0;
-    std::vector<void*> dev;
-    float *aabb, *nears, *fars, *rays_t, *xyzs, *dirs, *deltas, *sig, *rgb, *aa, *ae, *un, *wsum, *aasum, *aesum, *unsum;
-    int *alive[2], *ctl;
+struct mf_nerf_head : HeadCommon {
+    HeadSlot slot;
     const float* eye_dev = nullptr;      // mf_nerf_head_set_eye: the eye feature stays on the device
-    const float* aabb_user = nullptr;    // mf_nerf_head_set_aabb: the caller's aabb_infer (device), read instead of `aabb` below
-    // round-count feedback: two words of pinned host memory the device posts to when a frame's loop ends ([0] rounds the frame ran, [1] the tail's error flag);
-    // read without a sync, so it tells about a frame that finished some calls ago
-    volatile int* fb = nullptr;
-    int hist[4] = {0, 0, 0, 0}, hist_n = 0;
+    const float* aabb_user = nullptr;    // mf_nerf_head_set_aabb: the caller's aabb_infer (device), read instead of `aabb`
     int fixed_rounds = -1;               // mf_nerf_head_set_rounds: >= 0 pins the launched-round count (a captured graph is keyed on it), -1 = follow the feedback
-    ~mf_nerf_head() {
-        for (void* d : dev) (void)hipFree(d);
-        if (fb) (void)hipHostFree((void*)fb);
-    }
+    int plan_rounds(int max_steps) { return plan.next(fb[0], max_steps); }
 };
-
-// How many rounds of the next frame are enqueued as (march, field, composite) launches; the tail launch covers the rest.  The most rounds any of the last four
-// observed frames ran; every round (no tail) until a first frame has reported.  MF_NERF_TAIL_AFTER=<k> fixes it (nerf_tail_after_env, mf_nerf_host.h).
-static int head_plan(mf_nerf_head* h, int max_steps) {
-    const int fixed = nerf_tail_after_env(max_steps);
-    if (fixed >= 0) return fixed;
-    const int seen = h->fb ? h->fb[0] : 0;
-    if (seen > 0) { h->hist[h->hist_n & 3] = seen; h->hist_n++; }
-    if (h->hist_n == 0) return max_steps;
-    int m = 0;
-    for (int i = 0; i < 4; ++i) m = h->hist[i] > m ? h->hist[i] : m;
-    // no margin: a frame that needs more rounds than its predecessors runs them in the tail launch (and the next frames follow); a margin of one round was three
-    // launches per frame that found nothing to do (2 043 -> 2 068 frames/s)
-    return m < max_steps ? m : max_steps;
-}
 
 extern "C" int mf_nerf_head_create(mf_nerf_field* field, int max_rays, mf_nerf_head** out) {
     MF_REQUIRE(field && out && max_rays > 0, "nerf_head_create: bad argument");
@@ -51,29 +22,8 @@ extern "C" int mf_nerf_head_create(mf_nerf_field* field, int max_rays, mf_nerf_h
     MF_REQUIRE(max_rays <= field->cap_batches * TW, "nerf_head_create: %d rays exceed the field's sample capacity %d", max_rays, field->cap_batches * TW);
     *out = nullptr;
     std::unique_ptr<mf_nerf_head> h(new mf_nerf_head());
-    h->field = field; h->cap = max_rays;
-    auto fm = [&](float** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(float))); h->dev.push_back(*p); return MF_OK; };
-    auto im = [&](int** p, size_t n) -> int { MF_HIP(hipMalloc(p, n * sizeof(int))); h->dev.push_back(*p); return MF_OK; };
-    const size_t N = (size_t)max_rays;
     int rc;
-    if ((rc = fm(&h->aabb, 6)) || (rc = fm(&h->nears, N)) || (rc = fm(&h->fars, N)) || (rc = fm(&h->rays_t, N)) || (rc = fm(&h->xyzs, 3 * N)) ||
-        (rc = fm(&h->dirs, 3 * N)) || (rc = fm(&h->deltas, 2 * N)) || (rc = fm(&h->sig, N)) || (rc = fm(&h->rgb, 3 * N)) || (rc = fm(&h->aa, N)) ||
-        (rc = fm(&h->ae, N)) || (rc = fm(&h->un, N)) || (rc = fm(&h->wsum, N)) || (rc = fm(&h->aasum, N)) || (rc = fm(&h->aesum, N)) ||
-        (rc = fm(&h->unsum, N)) || (rc = im(&h->alive[0], N)) || (rc = im(&h->alive[1], N)) || (rc = im(&h->ctl, loop_ctl_ints(HEAD_MAX_ROUNDS))))
-        return rc;
-    MF_HIP(hipMemset(h->ctl, 0, loop_ctl_ints(HEAD_MAX_ROUNDS) * sizeof(int)));
-    {
-        int* fb = nullptr;
-        MF_HIP(hipHostMalloc((void**)&fb, 4 * sizeof(int), hipHostMallocMapped));
-        fb[0] = fb[1] = fb[2] = fb[3] = 0;
-        h->fb = fb;
-        void* fb_dev = nullptr;
-        MF_HIP(hipHostGetDevicePointer(&fb_dev, fb, 0));
-        MF_HIP(hipMemcpy(h->ctl + LOOP_CTL_FB, &fb_dev, sizeof(fb_dev), hipMemcpyHostToDevice));
-    }
-    const float b = field->cfg.bound;
-    const float aabb[6] = {-b, -b / 2, -b, b, b / 2, b};                                    // aabb_infer, renderer.py:86-89
-    MF_HIP(hipMemcpy(h->aabb, aabb, sizeof(aabb), hipMemcpyHostToDevice));
+    if ((rc = h->init(field, max_rays, 1)) || (rc = h->slot.alloc(max_rays, h->fb))) return rc;
     *out = h.release();
     return MF_OK;
 }
@@ -87,16 +37,15 @@ extern "C" int mf_nerf_head_render(mf_nerf_head* h, const float* rays_o, const f
     hipStream_t s = (hipStream_t)stream;
     const NerfFieldConsts f = h->field->consts();
     MF_REQUIRE(f.n_ind == 0 || ind_code, "nerf_head_render: the field was built with an individual code");
-    const char* skip_env = getenv("MF_NERF_SKIP_EMPTY");                       // "0": evaluate every slot as the reference does (A/B); read per call
-    const NerfLoop loop{h->ctl, n_rays, max_steps, {h->alive[0], h->alive[1]}, h->rays_t, h->fars, rays_o, rays_d, density_bitfield, (uint32_t)cascades,
-                        (uint32_t)grid_size, dt_gamma, T_thresh, h->xyzs, h->dirs, h->deltas, !(skip_env && skip_env[0] == '0')};
+    const HeadSlot& k = h->slot;
+    const NerfLoop loop = k.loop(n_rays, max_steps, rays_o, rays_d, density_bitfield, cascades, grid_size, dt_gamma, T_thresh, nerf_skip_empty_env());
     const NerfFrameInputs in{enc_a, ind_code, eye, h->eye_dev, density_scale};
-    const NerfFieldOut out{h->sig, h->rgb, h->aa, h->ae, h->un};
-    const NerfRaySums sums{weights_sum ? weights_sum : h->wsum, depth, image, h->aasum, h->aesum, h->unsum};
+    const NerfFieldOut out = k.out();
+    const NerfRaySums sums = k.sums(weights_sum, depth, image);
     int rc;
-    if ((rc = mf_nerf_loop_init(loop, sums, h->nears, h->aabb_user ? h->aabb_user : h->aabb, min_near, s))) return rc;
-    MF_REQUIRE(!h->fb || h->fb[1] == 0, "nerf_head_render: the tail kernel of an earlier frame gave up waiting for a round (control block error flag)");
-    const int rounds = h->fixed_rounds >= 0 ? (h->fixed_rounds < max_steps ? h->fixed_rounds : max_steps) : head_plan(h, max_steps);
+    if ((rc = mf_nerf_loop_init(loop, sums, k.nears, h->aabb_user ? h->aabb_user : h->aabb, min_near, s))) return rc;
+    MF_REQUIRE(h->fb[1] == 0, "nerf_head_render: the tail kernel of an earlier frame gave up waiting for a round (control block error flag)");
+    const int rounds = h->fixed_rounds >= 0 ? (h->fixed_rounds < max_steps ? h->fixed_rounds : max_steps) : h->plan_rounds(max_steps);
     for (int it = 0; it < rounds; ++it)
         if ((rc = mf_nerf_loop_march(loop, it, f.bound, s)) || (rc = mf_nerf_fused_launch(f, in, loop.xyzs, loop.dirs, loop.N, out, s, &loop)) ||
             (rc = mf_nerf_loop_composite(loop, it, out, sums, s)))
@@ -104,13 +53,13 @@ extern "C" int mf_nerf_head_render(mf_nerf_head* h, const float* rays_o, const f
     // at least one sample per alive ray and round, so max_steps rounds always suffice (step += n_step >= 1, renderer.py:270): with every round enqueued there is no tail
     if (rounds < max_steps && (rc = mf_nerf_tail_launch(f, in, out, loop, sums, rounds, s))) return rc;
     if (bg_per_ray < 0) return MF_OK;                                                       // finished later by mf_nerf_head_finish
-    return mf_nerf_finish(image, depth, sums.wsum, h->nears, h->fars, bg_color, bg_per_ray, bg_const, n_rays, frame_u8, stream);
+    return k.finish(n_rays, bg_color, bg_per_ray, bg_const, image, depth, weights_sum, frame_u8, stream);
 }
 
 extern "C" int mf_nerf_head_finish(mf_nerf_head* h, int n_rays, const float* bg_color, int bg_per_ray, float bg_const, float* image, float* depth,
                                    const float* weights_sum, uint8_t* frame_u8, void* stream) {
     MF_REQUIRE(h && image && depth && n_rays > 0 && n_rays <= h->cap && bg_per_ray >= 0, "nerf_head_finish: bad argument");
-    return mf_nerf_finish(image, depth, weights_sum ? weights_sum : h->wsum, h->nears, h->fars, bg_color, bg_per_ray, bg_const, n_rays, frame_u8, stream);
+    return h->slot.finish(n_rays, bg_color, bg_per_ray, bg_const, image, depth, weights_sum, frame_u8, stream);
 }
 
 extern "C" int mf_nerf_head_set_eye(mf_nerf_head* h, const float* eye_dev) {
@@ -127,7 +76,7 @@ extern "C" int mf_nerf_head_set_aabb(mf_nerf_head* h, const float* aabb_dev) {
 
 extern "C" int mf_nerf_head_plan_rounds(mf_nerf_head* h, int max_steps, int* rounds) {
     MF_REQUIRE(h && rounds && max_steps > 0 && max_steps <= HEAD_MAX_ROUNDS, "nerf_head_plan_rounds: bad argument");
-    *rounds = head_plan(h, max_steps);
+    *rounds = h->plan_rounds(max_steps);
     return MF_OK;
 }
 
@@ -146,18 +95,13 @@ extern "C" int mf_nerf_head_last_rounds(mf_nerf_head* h, int* rounds, int* error
 
 extern "C" int mf_nerf_head_ctl_snapshot(mf_nerf_head* h, int* out, int n_ints) {
     MF_REQUIRE(h && out && n_ints > 0 && (size_t)n_ints <= loop_ctl_ints(HEAD_MAX_ROUNDS), "nerf_head_ctl_snapshot: bad argument");
-    MF_HIP(hipMemcpy(out, h->ctl, (size_t)n_ints * sizeof(int), hipMemcpyDeviceToHost));
+    MF_HIP(hipMemcpy(out, h->slot.ctl, (size_t)n_ints * sizeof(int), hipMemcpyDeviceToHost));
     return MF_OK;
 }
 
 extern "C" int mf_nerf_head_sums(mf_nerf_head* h, int n_rays, float* ambient_aud, float* ambient_eye, float* uncertainty, void* stream) {
     MF_REQUIRE(h && n_rays > 0 && n_rays <= h->cap, "nerf_head_sums: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)n_rays * sizeof(float);
-    if (ambient_aud) MF_HIP(hipMemcpyAsync(ambient_aud, h->aasum, bytes, hipMemcpyDeviceToDevice, s));
-    if (ambient_eye) MF_HIP(hipMemcpyAsync(ambient_eye, h->aesum, bytes, hipMemcpyDeviceToDevice, s));
-    if (uncertainty) MF_HIP(hipMemcpyAsync(uncertainty, h->unsum, bytes, hipMemcpyDeviceToDevice, s));
-    return MF_OK;
+    return h->slot.copy_sums(n_rays, ambient_aud, ambient_eye, uncertainty, (hipStream_t)stream);
 }
 
 extern "C" void mf_nerf_head_destroy(mf_nerf_head* h) { delete h; }

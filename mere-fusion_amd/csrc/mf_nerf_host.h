@@ -84,6 +84,11 @@ inline int nerf_tail_after_env(int max_steps) {
     const int k = atoi(e);
     return k < 0 ? max_steps : (k < max_steps ? k : max_steps);
 }
+// MF_NERF_SKIP_EMPTY=0: evaluate every slot as the reference does (A/B); read per call.  What NerfLoop::skip_empty / NerfBatchLoop::skip_empty get
+inline bool nerf_skip_empty_env() {
+    const char* e = getenv("MF_NERF_SKIP_EMPTY");
+    return !(e && e[0] == '0');
+}
 
 // ---- mf_nerf.hip: the launches of a round --------------------------------------------------------------------------------------------------------
 // init: alive[0] = 0..N-1, near / far of every ray (raymarching.cu:92-145), zeroed sums, the first round's head

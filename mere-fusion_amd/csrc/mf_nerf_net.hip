@@ -565,24 +565,20 @@ extern "C" int mf_nerf_torso_forward_batch(mf_nerf_torso* torso, mf_nerf_frame_b
     for (int i = 0; i < n_frames; ++i)
         MF_REQUIRE(descs[i].bg_coords && descs[i].bg_out, "nerf_torso_forward_batch: frame %d: null bg_coords or bg_out", i);
     hipStream_t s = (hipStream_t)stream;
-    int slot;
-    void* host;
-    if ((rc = mf_nerf_frame_batch_acquire(h, &slot, &host))) return rc;
-    NerfTorsoFrame* tab = (NerfTorsoFrame*)host;
-    for (int i = 0; i < n_frames; ++i) {
-        const mf_nerf_torso_desc& d = descs[i];
-        NerfTorsoFrame& t = tab[i];
-        float bias[64];
-        torso->frame_bias(d.frame_consts, bias);
-        for (int o = 0; o < 32; ++o) { t.bias_d[o] = bias[o]; t.bias_t[o] = bias[32 + o]; }
-        t.bg_coords = d.bg_coords; t.bg = d.bg_color; t.out = d.bg_out; t.alpha_out = d.torso_alpha; t.deform = d.deform;
-        t.thresh = d.density_thresh; t.bg_const = d.bg_const; t.bg_per_ray = d.bg_per_ray; t.pad = 0;
-    }
-    const void* dev;
-    if ((rc = mf_nerf_frame_batch_upload(h, slot, (size_t)n_frames * sizeof(NerfTorsoFrame), s, &dev))) return rc;
-    rc = mf_nerf_torso_batch_launch(torso->consts(), (const NerfTorsoFrame*)dev, n_frames, torso->sampled(), n_pixels, s);
-    const int rc2 = mf_nerf_frame_batch_release(h, slot, s);
-    return rc ? rc : rc2;
+    auto fill = [&](NerfTorsoFrame* tab) {
+        for (int i = 0; i < n_frames; ++i) {
+            const mf_nerf_torso_desc& d = descs[i];
+            NerfTorsoFrame& t = tab[i];
+            float bias[64];
+            torso->frame_bias(d.frame_consts, bias);
+            for (int o = 0; o < 32; ++o) { t.bias_d[o] = bias[o]; t.bias_t[o] = bias[32 + o]; }
+            t.bg_coords = d.bg_coords; t.bg = d.bg_color; t.out = d.bg_out; t.alpha_out = d.torso_alpha; t.deform = d.deform;
+            t.thresh = d.density_thresh; t.bg_const = d.bg_const; t.bg_per_ray = d.bg_per_ray; t.pad = 0;
+        }
+    };
+    return mf_nerf_frame_batch_ring(h).call<NerfTorsoFrame>(n_frames, s, fill, [&](const NerfTorsoFrame* dev) {
+        return mf_nerf_torso_batch_launch(torso->consts(), dev, n_frames, torso->sampled(), n_pixels, s);
+    });
 }
 
 extern "C" int mf_nerf_torso_set_grid(mf_nerf_torso* h, const float* density_grid) {

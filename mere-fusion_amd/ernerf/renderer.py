@@ -78,13 +78,36 @@ class HipHeadRenderer:
                                                   _lib.stream_ptr()), "mf_nerf_resize_frame")
         return res
 
+    @staticmethod
+    def _bg_args(bg_color, N):
+        """`bg_color` (None: white, a number, a [3] or a per-ray [N, 3] tensor) as the finish kernels take it: (tensor or None, per_ray, constant)"""
+        bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
+        return bg, bg is not None and bg.numel() == 3 * N, float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
+
+    @staticmethod
+    def _frame_args(rays_o, rays_d, enc_a, ind_code, eye, want_u8):
+        """One frame's inputs as the device loops take them -> (rays_o, rays_d, enc_a, ind_code or None, eye_dev or None, eye value, fresh); fresh() allocates
+        the frame's dict of output tensors."""
+        rays_o = rays_o.contiguous().view(-1, 3).float()
+        rays_d = rays_d.contiguous().view(-1, 3).float()
+        N, dev = rays_o.shape[0], rays_o.device
+        ea = enc_a.float().reshape(-1).contiguous()
+        ic = ind_code.float().reshape(-1).contiguous() if ind_code is not None else None
+        # the eye feature: a device tensor (the reference's loader hands one over, provider.py) is read by the kernels where it lives -- no device -> host copy, no
+        # sync in front of the frame; a host tensor / None goes by value as before
+        eye_dev = eye.float().reshape(-1)[:1].contiguous() if (torch.is_tensor(eye) and eye.is_cuda) else None
+        ev = 0.0 if (eye is None or eye_dev is not None) else float(eye.reshape(-1)[0])
+
+        def fresh():
+            return {"image": torch.empty(N, 3, device=dev), "depth": torch.empty(N, device=dev), "weights_sum": torch.empty(N, device=dev),
+                    "frame_u8": torch.empty(N, 3, dtype=torch.uint8, device=dev) if want_u8 else None}
+        return rays_o, rays_d, ea, ic, eye_dev, ev, fresh
+
     def finish_device(self, out, bg_color):
         """Background mix / depth normalisation / uint8 frame for a run_cuda_device(finish=False) result."""
         N = out["image"].shape[0]
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
-        per_ray = bg is not None and bg.numel() == 3 * N
-        bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
+        bg, per_ray, bgc = self._bg_args(bg_color, N)
         _lib.check(self._lib.mf_nerf_head_finish(self._head, N, p(bg), int(per_ray), bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]),
                                                  p(out["frame_u8"]), _lib.stream_ptr()), "mf_nerf_head_finish")
         return out
@@ -104,9 +127,8 @@ class HipHeadRenderer:
                         graph=False, finish=True):
         """The same frame as run_cuda with the round control on the device (mf_nerf_head_render): one enqueue, no host sync between
         rounds.  graph=True captures the enqueue once per (ray count, tensors, launched rounds) into a CUDA graph and replays it."""
-        rays_o = rays_o.contiguous().view(-1, 3).float()
-        rays_d = rays_d.contiguous().view(-1, 3).float()
-        N, dev = rays_o.shape[0], rays_o.device
+        rays_o, rays_d, ea, ic, eye_dev, ev, fresh = self._frame_args(rays_o, rays_d, enc_a, ind_code, eye, want_u8)
+        N = rays_o.shape[0]
         if getattr(self, "_head", None) is None or self._head_cap < N:
             if getattr(self, "_head", None):
                 self._lib.mf_nerf_head_destroy(self._head)
@@ -114,15 +136,7 @@ class HipHeadRenderer:
             _lib.check(self._lib.mf_nerf_head_create(self.field._h, N, C.byref(self._head)), "mf_nerf_head_create")
             self._head_cap, self._graphs = N, {}
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
-        per_ray = bg is not None and bg.numel() == 3 * N
-        bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
-        ea = enc_a.float().reshape(-1).contiguous()
-        ic = ind_code.float().reshape(-1).contiguous() if ind_code is not None else None
-        # the eye feature: a device tensor (the reference's loader hands one over, provider.py) is read by the kernels where it lives -- no device -> host copy, no
-        # sync in front of the frame; a host tensor / None goes by value as before
-        eye_dev = eye.float().reshape(-1)[:1].contiguous() if (torch.is_tensor(eye) and eye.is_cuda) else None
-        ev = 0.0 if (eye is None or eye_dev is not None) else float(eye.reshape(-1)[0])
+        bg, per_ray, bgc = self._bg_args(bg_color, N)
         self._eye_keep = eye_dev
         _lib.check(self._lib.mf_nerf_head_set_eye(self._head, p(eye_dev)), "mf_nerf_head_set_eye")
         # the box of near / far: the reference reads its persistent buffer `self.aabb_infer` every frame (renderer.py:226); the head reads a rebound one where it
@@ -136,9 +150,6 @@ class HipHeadRenderer:
                                                      bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]), p(out["frame_u8"]),
                                                      _lib.stream_ptr()), "mf_nerf_head_render")
 
-        def fresh():
-            return {"image": torch.empty(N, 3, device=dev), "depth": torch.empty(N, device=dev), "weights_sum": torch.empty(N, device=dev),
-                    "frame_u8": torch.empty(N, 3, dtype=torch.uint8, device=dev) if want_u8 else None}
         if not graph:
             out = fresh()
             enqueue(out)
@@ -208,24 +219,15 @@ class HipHeadRenderer:
             raise RuntimeError(f"HipHeadRenderer.run_cuda_device_batch: {F} frames (1..{self.MAX_BATCH_FRAMES} per call)")
         p = lambda t: t.data_ptr() if t is not None else None
         descs = (_lib.MfNerfFrameDesc * F)()
-        keep, outs, N, dev = [], [], None, None
+        keep, outs, N = [], [], None
         for i, fr in enumerate(frames):
-            rays_o = fr["rays_o"].contiguous().view(-1, 3).float()
-            rays_d = fr["rays_d"].contiguous().view(-1, 3).float()
+            rays_o, rays_d, ea, ic, eye_dev, ev, fresh = self._frame_args(fr["rays_o"], fr["rays_d"], fr["enc_a"], fr.get("ind_code", self.ind_code), fr.get("eye"), want_u8)
             if N is None:
-                N, dev = rays_o.shape[0], rays_o.device
+                N = rays_o.shape[0]
             elif rays_o.shape[0] != N:
                 raise RuntimeError(f"HipHeadRenderer.run_cuda_device_batch: frame {i} has {rays_o.shape[0]} rays, frame 0 has {N} (one ray count per call)")
-            bg_color, eye, ind_code = fr.get("bg_color"), fr.get("eye"), fr.get("ind_code", self.ind_code)
-            bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
-            per_ray = bg is not None and bg.numel() == 3 * N
-            bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
-            ea = fr["enc_a"].float().reshape(-1).contiguous()
-            ic = ind_code.float().reshape(-1).contiguous() if ind_code is not None else None
-            eye_dev = eye.float().reshape(-1)[:1].contiguous() if (torch.is_tensor(eye) and eye.is_cuda) else None      # as run_cuda_device
-            ev = 0.0 if (eye is None or eye_dev is not None) else float(eye.reshape(-1)[0])
-            out = {"image": torch.empty(N, 3, device=dev), "depth": torch.empty(N, device=dev), "weights_sum": torch.empty(N, device=dev),
-                   "frame_u8": torch.empty(N, 3, dtype=torch.uint8, device=dev) if want_u8 else None}
+            bg, per_ray, bgc = self._bg_args(fr.get("bg_color"), N)
+            out = fresh()
             d = descs[i]
             d.rays_o, d.rays_d, d.enc_a, d.ind_code, d.eye_dev, d.eye = p(rays_o), p(rays_d), p(ea), p(ic), p(eye_dev), ev
             d.bg_color, d.bg_per_ray, d.bg_const = p(bg), (int(per_ray) if finish else -1), bgc
@@ -246,9 +248,7 @@ class HipHeadRenderer:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         for i, (out, bg_color) in enumerate(zip(outs, bg_colors)):
             N = out["image"].shape[0]
-            bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
-            per_ray = bg is not None and bg.numel() == 3 * N
-            bgc = float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color))
+            bg, per_ray, bgc = self._bg_args(bg_color, N)
             _lib.check(self._lib.mf_nerf_head_batch_finish(self._batch, i, N, p(bg), int(per_ray), bgc, p(out["image"]), p(out["depth"]), p(out["weights_sum"]),
                                                            p(out["frame_u8"]), _lib.stream_ptr()), "mf_nerf_head_batch_finish")
         return outs
@@ -396,11 +396,9 @@ class HipHeadRenderer:
             trace.append((n_alive, n_step))
             step += n_step
         frame = torch.empty(N, 3, dtype=torch.uint8, device=dev) if want_u8 else None
-        per_ray = torch.is_tensor(bg_color) and bg_color.numel() == 3 * N
-        bg = bg_color.float().contiguous() if torch.is_tensor(bg_color) else None
+        bg, per_ray, bgc = self._bg_args(bg_color, N)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(self._lib.mf_nerf_finish(p(image), p(depth), p(weights_sum), p(nears), p(fars), p(bg), int(per_ray),
-                                            float(1.0 if bg_color is None else (0.0 if bg is not None else bg_color)), N, p(frame),
-                                            _lib.stream_ptr()), "mf_nerf_finish")
+        _lib.check(self._lib.mf_nerf_finish(p(image), p(depth), p(weights_sum), p(nears), p(fars), p(bg), int(per_ray), bgc, N, p(frame), _lib.stream_ptr()),
+                   "mf_nerf_finish")
         return {"image": image, "depth": depth, "ambient_aud": amb_aud_sum, "ambient_eye": amb_eye_sum, "uncertainty": unc_sum,
                 "weights_sum": weights_sum, "frame_u8": frame, "trace": trace}

@@ -272,3 +272,70 @@ def test_batcher_batched_route_equals_one_step_per_frame(lib_built, monkeypatch)
                 assert got[step][k][1] == want[step][k][1] and torch.equal(got[step][k][0], want[step][k][0]), (kw, step, k)
         assert all(torch.equal(a, b) for a, b in zip(ema, want_ema)) and custom == want_custom and index == want_index
     assert float(want[1][0][0].float().std()) > 1.0
+
+
+# ---- 7. more calls in flight than a table ring holds -------------------------------------------------------------------------------------------
+def _hold_the_stream():
+    """10 to 200 ms of device time on the current stream (the counter runs at 0.1 to 2 GHz): what is enqueued behind it in the next few milliseconds is all in
+    flight at once, and the call that comes round to a used ring entry has to wait for it"""
+    torch.cuda._sleep(20_000_000)
+
+
+def test_nine_batched_calls_in_flight_are_each_the_frames_rendered_alone(runner, monkeypatch):
+    """2 * 4 + 1 calls of F = 2 back to back with no synchronise between them, twice round the head batch's ring of four frame tables and once more; every call
+    has its own enc_a and bg_color (a constant for frame 0, a per-ray image for frame 1).  Outputs start as NaN / 0x5A, so a frame a call never wrote shows; the
+    default round plan, so the calls hand over to the tail wherever the feedback words of the moment say."""
+    r, N = runner, runner.ro.shape[0]
+    calls = [[dict(_frame(r, enc=0.6 + 0.05 * (2 * c + j), eye=0.1 + 0.04 * c),
+                   bg_color=torch.rand(N, 3, generator=torch.Generator().manual_seed(50 + c)).cuda() if j else c / 8) for j in range(2)] for c in range(9)]
+    want = [_alone(r, frames) for frames in calls]
+    r.r.run_cuda_device_batch(calls[0])                                  # the handle exists: no allocation among the nine
+    torch.cuda.synchronize()
+    empty = torch.empty
+
+    def poisoned(*a, **kw):
+        t = empty(*a, **kw)
+        return t.fill_(float("nan") if t.is_floating_point() else 0x5A)
+    with monkeypatch.context() as m:
+        m.setattr(torch, "empty", poisoned)
+        _hold_the_stream()
+        got = [r.r.run_cuda_device_batch(frames, want_u8=True) for frames in calls]
+    torch.cuda.synchronize()
+    for c, (outs, alone) in enumerate(zip(got, want)):
+        for j, (out, (w, _)) in enumerate(zip(outs, alone)):
+            for key, b in zip(KEYS[:4], w):
+                assert _eq(out[key], b), (c, j, key)
+    assert not _eq(got[0][0]["image"], got[1][0]["image"]) and not _eq(got[0][1]["image"], got[8][1]["image"])      # the calls differ: nothing compares a frame with itself
+
+
+def test_thirty_three_frame_out_calls_in_flight_are_each_the_single_frame_bytes(lib_built):
+    """2 * 16 + 1 mf_nerf_frame_batch_out calls of F = 2 at 8 x 8 pixels with no synchronise between them, twice round the frame batch's ring of sixteen tables and
+    once more, each with its own renders, against mf_nerf_frame_out; the output blocks start as 0x5A"""
+    from mere_fusion_amd import _lib
+    _lib.init_device(0)
+    lib, S, CALLS = _lib.lib(), 8, 33
+    renders = torch.rand(CALLS, 2, S, S, 3, generator=torch.Generator().manual_seed(43)).cuda()
+    want = torch.empty(CALLS, 2, S, S, 3, dtype=torch.uint8, device="cuda")
+    for c in range(CALLS):
+        for j in range(2):
+            _lib.check(lib.mf_nerf_frame_out(_p(renders[c, j]), S, S, S, S, None, S, S, 0, 0, 1, _p(want[c, j]), _stream()), "mf_nerf_frame_out")
+    torch.cuda.synchronize()
+    h = C.c_void_p()
+    _lib.check(lib.mf_nerf_frame_batch_create(2, S * S, C.byref(h)), "mf_nerf_frame_batch_create")
+    try:
+        got = torch.full((CALLS, 2, S, S, 3), 0x5A, dtype=torch.uint8, device="cuda")
+        scratch, d0 = torch.empty(2, S, S, 3, dtype=torch.uint8, device="cuda"), (_lib.MfNerfOutDesc * 2)()
+        d0[0].render = d0[1].render = _p(renders[0, 0])
+        _lib.check(lib.mf_nerf_frame_batch_out(h, d0, 2, S, S, S, S, S, S, 1, _p(scratch), _stream()), "mf_nerf_frame_batch_out")      # the ring exists: no allocation among the 33
+        torch.cuda.synchronize()
+        _hold_the_stream()
+        for c in range(CALLS):
+            descs = (_lib.MfNerfOutDesc * 2)()
+            for j in range(2):
+                descs[j].render, descs[j].body_bgr, descs[j].x0, descs[j].y0 = _p(renders[c, j]), None, 0, 0
+            _lib.check(lib.mf_nerf_frame_batch_out(h, descs, 2, S, S, S, S, S, S, 1, _p(got[c]), _stream()), "mf_nerf_frame_batch_out")
+        torch.cuda.synchronize()
+    finally:
+        lib.mf_nerf_frame_batch_destroy(h)
+    assert torch.equal(got, want)
+    assert not torch.equal(want[0, 0], want[0, 1]) and not torch.equal(want[0], want[32]) and float(want.float().std()) > 10
