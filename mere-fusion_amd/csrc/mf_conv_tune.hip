@@ -269,6 +269,10 @@ int mf_conv_tune(ConvPlan* p, const ActView& in, const ActView& out, const ActVi
     float base_us = 0.f;
     int rc = measure(best_c, &base_us);
     float best_us = base_us;
+    // ... and the fastest single-pass configuration beside it: a split-K winner costs a second launch (the combine) on the step's dependent chain, which a
+    // layer timed alone does not show, so it has to be clearly ahead of the best configuration without one
+    ConvTuned best1_c = best_c;
+    float best1_us = base.nsplit > 1 ? 1e30f : base_us;
     for (const IgemmTile& t : MF_IGEMM_TILES) {
         if (rc) break;
         if (!t.tunable) continue;
@@ -289,12 +293,15 @@ int mf_conv_tune(ConvPlan* p, const ActView& in, const ActView& out, const ActVi
                 float us = 0.f;
                 if ((rc = measure(c, &us))) break;
                 if (us < best_us) { best_us = us; best_c = c; }
+                if (S == 1 && us < best1_us) { best1_us = us; best1_c = c; }
             }
             if (rc) break;
         }
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc) { p->tuned.erase(batch); return rc; }
+    const float split_us = best_us;                                                  // (what MF_DEBUG=tune reports beside the single-pass time)
+    if (best_c.tile.nsplit > 1 && 0.97f * best1_us <= best_us) { best_c = best1_c; best_us = best1_us; }
     // keep the model's pick unless the measured winner is clearly ahead (event timing of a 10-100 us launch is good to ~1 us)
     if (extend && best_us > 0.97f * base_us) {                                        // the entry stands (nothing is appended)
         if (had_entry) p->tuned[batch] = entry; else p->tuned.erase(batch);
@@ -302,7 +309,8 @@ int mf_conv_tune(ConvPlan* p, const ActView& in, const ActView& out, const ActVi
     else { p->tuned[batch] = best_c; tune_cache_store(key, best_c); }
     static const bool verbose = mf_debug_has("tune");
     if (verbose)
-        fprintf(stderr, "[mf_conv_tune] M %d N %d K %d: model %dx%d split %d %.1f us -> %s %dx%d split %d ld %d %.1f us\n", M, N, ktm * 64, base.bm, base.bn, base.nsplit,
-                base_us, p->tuned.count(batch) ? "tuned" : "kept", best_c.tile.bm, best_c.tile.bn, best_c.tile.nsplit, best_c.ld, best_us);
+        fprintf(stderr, "[mf_conv_tune] %s M %d N %d K %d: model %dx%d split %d %.1f us -> %s %dx%d split %d ld %d %.1f us (best overall %.1f us, best single-pass %dx%d ld %d %.1f us)\n",
+                key.c_str(), M, N, ktm * 64, base.bm, base.bn, base.nsplit, base_us, p->tuned.count(batch) ? "tuned" : "kept", best_c.tile.bm, best_c.tile.bn, best_c.tile.nsplit,
+                best_c.ld, best_us, split_us, best1_c.tile.bm, best1_c.tile.bn, best1_c.ld, best1_us);
     return MF_OK;
 }

@@ -90,6 +90,8 @@ struct Builder {
     // ---- blocks -----------------------------------------------------------------------------------------------
     int resnet(const std::string& p, ActView x, ActView y, int cin, int cout, int groups, float eps, const std::vector<float>* temb_act);
     int transformer(const std::string& p, ActView x, ActView y, int C, int heads, int groups, ActView ctx, KvHoist* kv);
+    int ff_proj_out(const std::string& f2, const std::string& po, ActView in, ActView y, ActView x, int C);   // a transformer block's ff.net.2 + proj_out as one layer
+    bool ff_fold_measured(int C, int H, int W);   // the tuning table holds the fused layer of a C-channel block on an H x W map at this handle's capacity
     int vae_mid_attention(const std::string& a, ActView x, ActView y, ActView residual, int groups);
     int hoist_kv_begin(KvHoist* kv, ActView ctx, int total);
     int hoist_kv_finish(KvHoist* kv);

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <thread>
 
 namespace {
 
@@ -12,6 +13,9 @@ struct Switches {
     bool conv_q = env_on("MF_CONV_Q");           // 0: bf16x3 everywhere, no f16 + FP6 conv
     bool q_equalize = env_on("MF_Q_EQUALIZE");   // 0: no channel equalisation of the f16 + FP6 operands
     bool tail_fuse = env_on("MF_TAIL_FUSE");     // 0: GroupNorm + conv_out always as the two-op chain (A/B)
+    // a transformer block's ff.net.2 and proj_out as one layer (Builder::ff_proj_out).  Unset: where the tuning table holds the fused layer at the handle's
+    // capacity (ff_fold_measured); 0: never, the two-op chain (A/B); any other value: always (tests, and measuring the fused shapes for the table)
+    int ff_proj_fold = getenv("MF_FF_PROJ_FOLD") ? (atoi(getenv("MF_FF_PROJ_FOLD")) != 0 ? 2 : 0) : 1;
 };
 const Switches& switches() { static const Switches s{}; return s; }
 
@@ -37,6 +41,15 @@ std::vector<float> cat_rows(std::initializer_list<const float*> parts, size_t n_
     w.reserve(parts.size() * n_each);
     for (const float* p : parts) w.insert(w.end(), p, p + n_each);
     return w;
+}
+
+// f(i) for i in [0, n) on a few host threads (create-time weight arithmetic)
+template <class F> void parallel_for(int n, F f) {
+    const int nt = std::max(1, std::min({n, 8, (int)std::thread::hardware_concurrency()}));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back([=] { for (int i = t; i < n; i += nt) f(i); });
+    for (int i = 0; i < n; i += nt) f(i);
+    for (auto& x : th) x.join();
 }
 
 // GroupNorm -> SiLU -> the f16 + FP6 format in front of a conv of that format.  `fuse` (maps of a multiple of 64 pixels): the conversion kernel forms the per-channel
@@ -540,10 +553,14 @@ int Builder::transformer(const std::string& p, ActView x, ActView y, int C, int 
     const int H = x.buf->H, W = x.buf->W, X = ctx.C;
     ActBuf *g0 = tmp("xf.gn", C, H, W, 0), *hA = tmp("xf.hA", C, H, W, 0), *hB = tmp("xf.hB", C, H, W, 0);
     ActBuf *nb = tmp("xf.ln", C, H, W, 0), *qkv = tmp("xf.qkv", 3 * C, H, W, 0), *ao = tmp("xf.ao", C, H, W, 0);
-    ActBuf *kvb = tmp("xf.kv", 2 * C, ctx.buf->H, ctx.buf->W, 0), *gg = tmp("xf.geglu", 4 * C, H, W, 0);
+    // ff.net.2 and proj_out folded into one layer (ff_proj_out): the feed-forward buffer is [GEGLU output (4C) | residual stream behind the cross-attention (C)],
+    // the one input of that layer; attn2.to_out writes the slice, norm3 / ff.net.0.proj read it
+    const bool ffold = switches().ff_proj_fold == 2 || (switches().ff_proj_fold == 1 && ff_fold_measured(C, H, W));
+    ActBuf *kvb = tmp("xf.kv", 2 * C, ctx.buf->H, ctx.buf->W, 0), *gg = tmp("xf.geglu", (ffold ? 5 : 4) * C, H, W, 0);
     if (!g0 || !hA || !hB || !nb || !qkv || !ao || !kvb || !gg) return MF_ERR_HIP;
     const std::string t = p + ".transformer_blocks.0";
     const ActView vg{g0, 0, C}, vA{hA, 0, C}, vB{hB, 0, C}, vn{nb, 0, C}, va{ao, 0, C}, vq{qkv, 0, C};
+    const ActView vR = ffold ? ActView{gg, 4 * C, C} : vA;
     int rc;
     // The three LayerNorms are FOLDED into the GEMMs around them where the statistics buffer has room (it has, for the shipped configurations): the producer of
     // the residual stream (proj_in, attn1.to_out + x, attn2.to_out + x) leaves every token's (sum, sum of squares), the consumer (q | k | v, attn2.to_q, the
@@ -591,16 +608,79 @@ int Builder::transformer(const std::string& p, ActView x, ActView y, int C, int 
         } else if ((rc = linear_raw(cat_rows({wk, wv}, (size_t)C * X).data(), nullptr, ctx, ActView{kvb, 0, 2 * C}, X, 2 * C))) return rc;
     }
     if ((rc = attention(vq, kk, vv, va, heads))) return rc;
-    if ((rc = conv(t + ".attn2.to_out.0", va, vA, C, C, 1, 1, 0, producer(vB, st3)))) return rc;
+    if ((rc = conv(t + ".attn2.to_out.0", va, vR, C, C, 1, 1, 0, producer(vB, st3)))) return rc;
     // GEGLU feed-forward; GEGLU in the GEMM epilogue (act 5): the 8C-wide projection never reaches HBM, only value * gelu(gate)
     {
         ConvOpts o; o.act = 5;
-        if ((rc = norm(t + ".norm3", vA, st3, &o, &in))) return rc;
+        if ((rc = norm(t + ".norm3", vR, st3, &o, &in))) return rc;
         if ((rc = conv(t + ".ff.net.0.proj", in, ActView{gg, 0, 4 * C}, C, 8 * C, 1, 1, 0, o))) return rc;
     }
-    ConvOpts ff2, po; ff2.res = vA; po.res = x;
+    if (ffold) return ff_proj_out(t + ".ff.net.2", p + ".proj_out", ActView{gg, 0, 5 * C}, y, x, C);
+    ConvOpts ff2, po; ff2.res = vR; po.res = x;
     if ((rc = conv(t + ".ff.net.2", ActView{gg, 0, 4 * C}, vB, 4 * C, C, 1, 1, 0, ff2))) return rc;
     return conv(p + ".proj_out", vB, y, C, C, 1, 1, 0, po);
+}
+
+// The fold is taken by default only where the fused layer (K = 5C, N = C, block-input residual) has a measured row in the tuning table at this handle's capacity,
+// with or without the GroupNorm-statistics hand-off: a fused layer on the cost model's default tile is the likeliest way for the fold to lose, and the gain was
+// measured on the 8-frame handle (profiles/unet_ff_proj_fold.md).  Handles for more frames, and networks the table does not serve, keep the two-op chain.
+bool Builder::ff_fold_measured(int C, int H, int W) {
+    ActBuf b;
+    b.C = 5 * C; b.H = H; b.W = W;
+    const ActView in{&b, 0, 5 * C};
+    ConvPlan pl;
+    pl.d = desc_s1(5 * C, C, 1, 0, b, ActView{&b, 0, C});
+    pl.precision = precision; pl.Hq = pl.out_h = H; pl.Wq = pl.out_w = W;
+    if (mf_conv_tune_lookup(&pl, in, cap)) return true;
+    double stats_asked = 0.0;
+    pl.out_stats = &stats_asked;                     // (the key of a layer whose consumer GroupNorm takes its statistics)
+    return mf_conv_tune_lookup(&pl, in, cap) != 0;
+}
+
+// ff.net.2 (+ the residual stream r) followed by proj_out (+ the block's input x) as ONE 1x1 layer: nothing nonlinear lies between them, so
+//     y = W_po (W_f2 gg + b_f2 + r) + b_po + x = [W_po W_f2 | W_po] [gg ; r] + (W_po b_f2 + b_po) + x
+// with K = 5C over the buffer `in` = [gg | r].  The products are formed in double and rounded once (as the time embedding in mf_unet_create); the layer's FLOP
+// figure, 2 * 5C * C per token, is the sum of the two layers it replaces.  Per block: one launch, one write and one read of the token stream less.
+int Builder::ff_proj_out(const std::string& f2, const std::string& po, ActView in, ActView y, ActView x, int C) {
+    const int K4 = 4 * C, K = 5 * C;
+    const float *w2 = T(f2 + ".weight", (int64_t)C * K4), *b2 = T(f2 + ".bias", C);
+    const float *wp = T(po + ".weight", (int64_t)C * C), *bp = T(po + ".bias", C);
+    if (!w2 || !b2 || !wp || !bp) return MF_ERR_INVALID;
+    std::vector<float> w((size_t)C * K), b(C);
+    // W_po W_f2, eight output rows at a time against column blocks of W_f2 that stay in cache
+    const int OB = 8, KB = 512;
+    parallel_for((C + OB - 1) / OB, [&](int ob) {
+        const int o0 = ob * OB, on = std::min(OB, C - o0);
+        std::vector<double> acc((size_t)OB * KB);
+        for (int k0 = 0; k0 < K4; k0 += KB) {
+            const int kn = std::min(KB, K4 - k0);
+            std::fill(acc.begin(), acc.end(), 0.0);
+            for (int m = 0; m < C; ++m) {
+                const float* r2 = w2 + (size_t)m * K4 + k0;
+                for (int o = 0; o < on; ++o) {
+                    const double a = wp[(size_t)(o0 + o) * C + m];
+                    double* row = acc.data() + (size_t)o * KB;
+                    for (int k = 0; k < kn; ++k) row[k] += a * (double)r2[k];
+                }
+            }
+            for (int o = 0; o < on; ++o)
+                for (int k = 0; k < kn; ++k) w[(size_t)(o0 + o) * K + k0 + k] = (float)acc[(size_t)o * KB + k];
+        }
+        for (int o = o0; o < o0 + on; ++o) {
+            double bias = bp[o];
+            for (int m = 0; m < C; ++m) bias += (double)wp[(size_t)o * C + m] * (double)b2[m];
+            b[o] = (float)bias;
+            std::copy(wp + (size_t)o * C, wp + (size_t)(o + 1) * C, w.begin() + (size_t)o * K + K4);
+        }
+    });
+    ConvPlan* pl = new_plan();
+    stats_forget(y.buf);
+    int rc = mf_conv_plan_create(pl, desc_s1(K, C, 1, 0, *in.buf, x), w.data(), b.data(), nullptr, nullptr, nullptr, nullptr, precision);
+    if (rc) return rc;
+    if ((rc = mf_conv_bind(pl, *in.buf))) return rc;
+    push_conv(f2 + "+proj_out", pl, in, y, x);
+    stats_remember(pl, y);
+    return MF_OK;
 }
 
 // the VAE mid block's single-head attention over all channels (decoder and encoder): GroupNorm, q | k | v in one GEMM, attention, to_out + residual

@@ -42,6 +42,12 @@ for i, r in enumerate(rows):
         tq, tk, h, dh = (int(x) for x in mm.groups())
         by = B * (2 * tq + 2 * tk) * h * dh * 4.0
         kind = "attention"
+    elif name.endswith(".ff.net.2+proj_out") and flops > 0:          # the two layers folded into one over [GEGLU output | residual stream]: K = 5C
+        co = weight_of(name[:-len("+proj_out")])[0]
+        ci = 5 * co
+        tokens = flops / (2.0 * ci * co)
+        by = ci * co * 4.0 + tokens * (ci + co) * 4.0 + tokens * co * 4.0   # + the block-input residual
+        kind = "linear"
     elif m and flops > 0:
         ci, co = int(m.group(1)), int(m.group(2))
         tokens = flops / (2.0 * ci * co)
