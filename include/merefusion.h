@@ -366,6 +366,36 @@ int mf_whisper_decoder_logits(void* h, const int* tokens, int n, float* logits, 
 int mf_whisper_decoder_greedy(void* h, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new,
                               int check_every, int* out_tokens, int* out_lens, float* sum_logprobs, int batch, void* stream);
 
+/* mf_whisper_decoder_greedy under the reference's logit filters, applied in the launch that chooses the token, in the reference's order
+ * (decoding.py:387-441): SuppressBlank, SuppressTokens (suppress_mask), ApplyTimestampRules; then GreedyDecoder.update at temperature 0.  Each
+ * sequence reads its own history on the device (tokens sampled so far, the last two), so "first sampled position" is per sequence.
+ *   timestamp_begin              eot < timestamp_begin <= n_vocab; -1: no timestamp rules (no_timestamps and the cap are then not read)
+ *   no_timestamps                the <|notimestamps|> id, never chosen under the timestamp rules; -1: none
+ *   max_initial_timestamp_index  at the first sampled position timestamps above timestamp_begin + index are out; -1: none
+ *   blank                        at the first sampled position this id and eot are out; -1: off
+ *   no_speech                    -1: none.  Otherwise sot_index (HOST int32 [batch], the index of <|startoftranscript|> inside each prompt) names one
+ *                                more prefill row per sequence, and no_speech_probs (HOST fp32 [batch]) receives softmax(its logits)[no_speech]
+ * A step makes the launches of a greedy step, one for one (the rule kernel stands in k_dec_choose's place), and waits for no host read.  With timestamp_begin, blank and no_speech all -1 the tokens and the
+ * summed log-probabilities are those of mf_whisper_decoder_greedy, bit for bit.  Every id is checked against the vocabulary before anything
+ * is enqueued. */
+int mf_whisper_decoder_decode(void* h, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new, int check_every,
+                              int timestamp_begin, int no_timestamps, int max_initial_timestamp_index, int blank, int no_speech, const int* sot_index,
+                              int* out_tokens, int* out_lens, float* sum_logprobs, float* no_speech_probs, int batch, void* stream);
+
+/* `detect_language` (decoding.py:19-69) directly after mf_whisper_decoder_begin: forwards the single token `sot` per sequence, takes the argmax
+ * (lowest id on a tie) and the softmax over language_tokens (HOST int32 [n_languages], distinct ids) on the device, and reads both back at once.
+ * out_tokens: HOST int32 [batch]; out_probs: HOST fp32 [batch][n_languages] in the list's order.  Afterwards the handle stands as after begin:
+ * lengths 0, cache row 0 zeroed again. */
+int mf_whisper_decoder_detect_language(void* h, int sot, const int* language_tokens, int n_languages, int* out_tokens, float* out_probs, int batch,
+                                       void* stream);
+
+/* Test seam: the token choice of mf_whisper_decoder_decode alone.  logits: device fp32 [batch][n_vocab]; history: HOST int32 [batch][3] = tokens
+ * sampled so far, the last one, the one before it (read only as far as the count says); tokens / logprobs / done: HOST [batch], in and out --
+ * a sequence whose done flag is set on entry keeps all three; otherwise tokens = the argmax (-1: no admissible finite logit, done = 1),
+ * logprobs = its log-softmax under the filters, done = 1 at eot.  batch <= max_batch.  Touches none of the handle's decode state.  Synchronises. */
+int mf_whisper_decoder_choose(void* h, const float* logits, const int* history, const float* suppress_mask, int eot, int timestamp_begin, int no_timestamps,
+                              int max_initial_timestamp_index, int blank, int* tokens, float* logprobs, int* done, int batch, void* stream);
+
 /* Test seam: the self-attention cache of one layer and sequence, k and v HOST fp32 [n_text_ctx][n_state] each, and the sequence's length.
  * Synchronises the device. */
 int mf_whisper_decoder_cache_read(const void* h, int layer, int seq, float* k, float* v, int* len);

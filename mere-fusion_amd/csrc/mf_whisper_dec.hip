@@ -9,12 +9,15 @@
 //                  16 bytes per lane, 16 lanes per output column, up to 8 rows per pass held in LDS, fp32 accumulation, wave shuffles to reduce
 //   k_dec_attn     one query against the cached keys of its sequence (self: 0..position, cross: the T_audio encoder keys), softmax in fp32
 //   k_dec_choose   suppression mask, argmax (lowest index wins a tie), log-probability, end-of-text / budget / cache-full -> done flag
+//   k_dec_choose_rules   the same choice under the reference's logit filters (decoding.py:387-441: SuppressBlank, SuppressTokens,
+//                  ApplyTimestampRules), read from the sequence's own history on the device; takes k_dec_choose's place in a step, launch for launch
 // A step is 2 + 8 * n_layer launches and depends on no host read: a sequence whose done flag is set is skipped by every kernel (its cache rows,
 // its output and its counters are not written again), so the host reads the flags only every `check_every` steps.
 #include "mf_common.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -265,6 +268,152 @@ __global__ __launch_bounds__(256) void k_dec_choose(ChooseArgs a) {
     if (n_out + 1 >= a.max_new || len >= a.n_ctx) a.done[b] = 1;   // budget spent, or no cache row left to feed this token into
 }
 
+struct RuleArgs {
+    ChooseArgs c;
+    const int* hist;                   // test seam: [batch][3] = tokens sampled so far, the last, the one before; null: the sequence's own out_len / out_tok
+    int tb, no_ts, max_init, blank;    // timestamp_begin (n_vocab: no timestamp rules), <|notimestamps|>, max_initial_timestamp_index, blank; -1: none
+};
+
+// the logit of token n after SuppressBlank, SuppressTokens and the masks of ApplyTimestampRules (decoding.py:392-433).  first: nothing sampled yet;
+// pair: 0 none, 1 the last two were timestamps (or the only one was): [timestamp_begin:] is out, 2 a timestamp after text: [:eot] is out
+__device__ __forceinline__ float rule_logit(const RuleArgs& a, const float* lg, int n, bool first, int pair) {
+    const float v = lg[n] + (a.c.mask ? a.c.mask[n] : 0.f);
+    const bool out = (first && a.blank >= 0 && (n == a.blank || n == a.c.eot)) || n == a.no_ts || (pair == 1 && n >= a.tb) || (pair == 2 && n < a.c.eot) ||
+                     (first && a.max_init >= 0 && n > a.tb + a.max_init);
+    return out ? -INFINITY : v;
+}
+
+// first maximum of 256 (value, index) pairs and the sum of 256 partial sums, in k_dec_choose's order
+__device__ __forceinline__ void block_argmax(float* s_v, int* s_i, int tid) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            const float v = s_v[tid + o];
+            const int i = s_i[tid + o];
+            if (v > s_v[tid] || (v == s_v[tid] && i < s_i[tid])) { s_v[tid] = v; s_i[tid] = i; }
+        }
+        __syncthreads();
+    }
+}
+__device__ __forceinline__ void block_sum(float* s_v, int tid) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s_v[tid] += s_v[tid + o];
+        __syncthreads();
+    }
+}
+
+// one workgroup per sequence, two passes over its logits.  Pass 1: the first maximum of the filtered text range [:timestamp_begin] and of the
+// filtered timestamps.  Pass 2: sum exp(v - its range's maximum) per range.  Then one thread decides: if logsumexp(timestamps) > max(text), the
+// text range is out (decoding.py:436-441; log_softmax moves both sides by the same amount, so unnormalised logits give the same answer), and the
+// log-probability of the argmax is -log of the sums brought to its maximum.  With tb = n_vocab every token is text and the arithmetic is
+// k_dec_choose's, operation for operation.
+__global__ __launch_bounds__(256) void k_dec_choose_rules(RuleArgs a) {
+    __shared__ float s_tv[256], s_sv[256];
+    __shared__ int s_ti[256], s_si[256];
+    const int b = blockIdx.x, tid = threadIdx.x, V = a.c.n_vocab;
+    if (a.c.done[b]) return;
+    const float* lg = a.c.logits + (int64_t)b * V;
+    int n_hist, last = -1, prev = -1;
+    if (a.hist) {
+        n_hist = a.hist[3 * b]; last = a.hist[3 * b + 1]; prev = a.hist[3 * b + 2];
+    } else {
+        n_hist = a.c.out_len[b];
+        const int* t = a.c.out_tok + (int64_t)b * a.c.out_stride;
+        if (n_hist >= 1) last = t[n_hist - 1];
+        if (n_hist >= 2) prev = t[n_hist - 2];
+    }
+    const bool first = n_hist == 0;
+    const int pair = (a.tb < V && n_hist >= 1 && last >= a.tb) ? ((n_hist < 2 || prev >= a.tb) ? 1 : 2) : 0;
+    float bt = -INFINITY, bs = -INFINITY;
+    int it = INT_MAX, is = INT_MAX;
+    for (int n = tid; n < V; n += 256) {
+        const float v = rule_logit(a, lg, n, first, pair);
+        if (n < a.tb) { if (v > bt) { bt = v; it = n; } }
+        else if (v > bs) { bs = v; is = n; }
+    }
+    s_tv[tid] = bt; s_ti[tid] = it; s_sv[tid] = bs; s_si[tid] = is;
+    block_argmax(s_tv, s_ti, tid);
+    block_argmax(s_sv, s_si, tid);
+    bt = s_tv[0]; it = s_ti[0]; bs = s_sv[0]; is = s_si[0];
+    __syncthreads();
+    const bool has_t = it < V, has_s = is < V;
+    float st = 0.f, ss = 0.f;
+    for (int n = tid; n < V; n += 256) {
+        const float v = rule_logit(a, lg, n, first, pair);
+        if (n < a.tb) { if (has_t) st += expf(v - bt); }
+        else if (has_s) ss += expf(v - bs);
+    }
+    s_tv[tid] = st; s_sv[tid] = ss;
+    block_sum(s_tv, tid);
+    block_sum(s_sv, tid);
+    if (tid != 0) return;
+    st = s_tv[0]; ss = s_sv[0];
+    const int len = a.c.len[b] + (a.c.advance ? 1 : 0);
+    a.c.len[b] = len;
+    if (!has_t && !has_s) { a.c.done[b] = 1; a.c.cur_tok[b] = -1; return; }   // no admissible finite logit: stop the sequence
+    // ss >= 1 (its maximum's own term), so the logsumexp is never below bs: a timestamp above every text token always takes this branch
+    const bool ts_wins = has_s && (!has_t || bs + logf(ss) > bt);
+    const int idx = ts_wins ? is : it;
+    const float sum = ts_wins ? ss : (has_s ? st + ss * expf(bs - bt) : st);
+    a.c.sum_lp[b] += -logf(sum);
+    a.c.cur_tok[b] = idx;
+    if (idx == a.c.eot) { a.c.done[b] = 1; return; }
+    const int n_out = a.c.out_len[b];
+    a.c.out_tok[(int64_t)b * a.c.out_stride + n_out] = idx;
+    a.c.out_len[b] = n_out + 1;
+    if (n_out + 1 >= a.c.max_new || len >= a.c.n_ctx) a.c.done[b] = 1;
+}
+
+// softmax(logits of the <|startoftranscript|> row)[no_speech] per sequence (decoding.py:602-604); rows = the prefill head's second half
+__global__ __launch_bounds__(256) void k_dec_no_speech(const float* __restrict__ logits, int n_vocab, int no_speech, float* __restrict__ prob) {
+    __shared__ float s_v[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* lg = logits + (int64_t)b * n_vocab;
+    float mx = -INFINITY;
+    for (int n = tid; n < n_vocab; n += 256) mx = fmaxf(mx, lg[n]);
+    s_v[tid] = mx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s_v[tid] = fmaxf(s_v[tid], s_v[tid + o]);
+        __syncthreads();
+    }
+    mx = s_v[0];
+    __syncthreads();
+    float sum = 0.f;
+    for (int n = tid; n < n_vocab; n += 256) sum += expf(lg[n] - mx);
+    s_v[tid] = sum;
+    block_sum(s_v, tid);
+    if (tid == 0) prob[b] = expf(lg[no_speech] - mx) / s_v[0];
+}
+
+// detect_language (decoding.py:50-55): every token but the listed language tokens is out; argmax (lowest id on a tie) and softmax over the list.
+// out [batch][1 + n_lang]: the chosen id's bits, then the probabilities in the list's order
+__global__ __launch_bounds__(256) void k_dec_language(const float* __restrict__ logits, int n_vocab, const int* __restrict__ ids, int n_lang, float* __restrict__ out) {
+    __shared__ float s_v[256];
+    __shared__ int s_i[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* lg = logits + (int64_t)b * n_vocab;
+    float* o = out + (int64_t)b * (n_lang + 1);
+    float best = -INFINITY;
+    int idx = INT_MAX;
+    for (int j = tid; j < n_lang; j += 256) {
+        const float v = lg[ids[j]];
+        if (v > best || (v == best && ids[j] < idx)) { best = v; idx = ids[j]; }
+    }
+    s_v[tid] = best; s_i[tid] = idx;
+    block_argmax(s_v, s_i, tid);
+    best = s_v[0]; idx = s_i[0];
+    __syncthreads();
+    float sum = 0.f;
+    for (int j = tid; j < n_lang; j += 256) sum += expf(lg[ids[j]] - best);
+    s_v[tid] = sum;
+    block_sum(s_v, tid);
+    sum = s_v[0];
+    for (int j = tid; j < n_lang; j += 256) o[1 + j] = expf(lg[ids[j]] - best) / sum;
+    if (tid == 0) o[0] = __int_as_float(idx < n_vocab ? idx : -1);
+}
+
 __global__ void k_dec_rows_fill(int* seq, int* pos, const int* len, int n, int M) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
@@ -278,6 +427,9 @@ __global__ void k_dec_len_add(int* len, int n, int batch) {
 struct Planes { bf16_t* hi = nullptr; bf16_t* lo = nullptr; };
 
 }  // namespace
+
+// the rule parameters of a decode call (-1: none), checked against the vocabulary by rules_check
+struct DecodeRules { int tb, no_ts, max_init, blank, no_speech; };
 
 // the C ABI hands this out as an untyped handle (void*)
 struct mf_whisper_decoder {
@@ -294,7 +446,9 @@ struct mf_whisper_decoder {
         float* ckv_out;      // cross K | V [batch * T_audio][2C], written by begin()
     };
     std::vector<Layer> layers;
-    float *x = nullptr, *q = nullptr, *ao = nullptr, *h1 = nullptr, *logits = nullptr, *sum_lp = nullptr;
+    float *x = nullptr, *q = nullptr, *ao = nullptr, *h1 = nullptr, *logits = nullptr, *sum_lp = nullptr;   // logits [2 * max_batch][n_vocab]: the sot rows of a prefill follow the last rows
+    float *no_speech = nullptr, *lang_out = nullptr;   // [max_batch]; [max_batch][1 + lang_cap], grown by detect_language
+    int *lang_ids = nullptr, lang_cap = 0;
     int *row_tok = nullptr, *row_seq = nullptr, *row_pos = nullptr, *last_row = nullptr;
     int *len = nullptr, *done = nullptr, *cur_tok = nullptr, *out_len = nullptr, *out_tok = nullptr;
     int batch = 0, T_audio = 0;   // of the last begin(); 0: none yet
@@ -330,6 +484,9 @@ struct mf_whisper_decoder {
     int forward(int M, const int* tokens, Rows rows, hipStream_t s);
     int head(int M, const int* gather, float* out, Rows rows, hipStream_t s) const;
     int choose(const float* mask, int eot, int max_new, int advance, int B, hipStream_t s) const;
+    int choose_rules(const DecodeRules& r, const float* mask, int eot, int max_new, int advance, int B, hipStream_t s) const;
+    int decode(const char* who, const int* prompts, const int* prompt_lens, const float* mask, int eot, int max_new, int check_every, const DecodeRules* rules,
+               const int* sot_index, int* out_tokens, int* out_lens, float* sum_logprobs, float* no_speech_probs, int batch, hipStream_t s);
 };
 
 int mf_whisper_decoder::linear(LinArgs a, hipStream_t s) const {
@@ -404,6 +561,31 @@ int mf_whisper_decoder::choose(const float* mask, int eot, int max_new, int adva
     const ChooseArgs c{logits, n_vocab, mask, eot, max_new, n_ctx, advance, len, done, cur_tok, out_len, sum_lp, out_tok, n_ctx};
     hipLaunchKernelGGL(k_dec_choose, dim3(B), dim3(256), 0, s, c);
     MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+static RuleArgs rule_args(const ChooseArgs& c, const DecodeRules& r, const int* hist) {
+    const bool ts = r.tb >= 0;
+    return RuleArgs{c, hist, ts ? r.tb : c.n_vocab, ts ? r.no_ts : -1, ts ? r.max_init : -1, r.blank};
+}
+
+int mf_whisper_decoder::choose_rules(const DecodeRules& r, const float* mask, int eot, int max_new, int advance, int B, hipStream_t s) const {
+    const ChooseArgs c{logits, n_vocab, mask, eot, max_new, n_ctx, advance, len, done, cur_tok, out_len, sum_lp, out_tok, n_ctx};
+    hipLaunchKernelGGL(k_dec_choose_rules, dim3(B), dim3(256), 0, s, rule_args(c, r, nullptr));
+    MF_HIP(hipGetLastError());
+    return MF_OK;
+}
+
+// every id of a rule set against the vocabulary; timestamp_begin = -1 turns the timestamp rules off (no_timestamps and the initial cap are then not read)
+static int rules_check(const char* who, const DecodeRules& r, int eot, int n_vocab) {
+    MF_REQUIRE(eot >= 0 && eot < n_vocab, "%s: end-of-text token %d outside the vocabulary (%d)", who, eot, n_vocab);
+    MF_REQUIRE(r.tb == -1 || (eot < r.tb && r.tb <= n_vocab), "%s: timestamp_begin = %d; eot (%d) < timestamp_begin <= n_vocab (%d), or -1 for no timestamp rules",
+               who, r.tb, eot, n_vocab);
+    MF_REQUIRE(r.no_ts >= -1 && r.no_ts < n_vocab, "%s: no_timestamps token %d outside the vocabulary (%d)", who, r.no_ts, n_vocab);
+    MF_REQUIRE(r.max_init >= -1 && (r.tb < 0 || r.max_init < std::max(n_vocab - r.tb, 1)), "%s: max_initial_timestamp_index = %d, the vocabulary holds %d timestamps (-1: none)",
+               who, r.max_init, r.tb < 0 ? 0 : n_vocab - r.tb);
+    MF_REQUIRE(r.blank >= -1 && r.blank < n_vocab, "%s: blank token %d outside the vocabulary (%d)", who, r.blank, n_vocab);
+    MF_REQUIRE(r.no_speech >= -1 && r.no_speech < n_vocab, "%s: no_speech token %d outside the vocabulary (%d)", who, r.no_speech, n_vocab);
     return MF_OK;
 }
 
@@ -488,9 +670,9 @@ extern "C" int mf_whisper_decoder_create(const mf_tensor* weights, int n_weights
     }
     const size_t rows = (size_t)max_batch * h->n_ctx;
     if ((rc = h->dev_alloc(&h->x, rows * C)) || (rc = h->dev_alloc(&h->q, rows * C)) || (rc = h->dev_alloc(&h->ao, rows * C)) ||
-        (rc = h->dev_alloc(&h->h1, rows * 4 * C)) || (rc = h->dev_alloc(&h->logits, (size_t)max_batch * h->n_vocab)) ||
+        (rc = h->dev_alloc(&h->h1, rows * 4 * C)) || (rc = h->dev_alloc(&h->logits, (size_t)2 * max_batch * h->n_vocab)) || (rc = h->dev_alloc(&h->no_speech, max_batch)) ||
         (rc = h->dev_alloc(&h->row_tok, rows)) || (rc = h->dev_alloc(&h->row_seq, rows)) || (rc = h->dev_alloc(&h->row_pos, rows)) ||
-        (rc = h->dev_alloc(&h->out_tok, rows)) || (rc = h->dev_alloc(&h->last_row, max_batch)) || (rc = h->dev_alloc(&h->len, max_batch)) ||
+        (rc = h->dev_alloc(&h->out_tok, rows)) || (rc = h->dev_alloc(&h->last_row, 2 * max_batch)) || (rc = h->dev_alloc(&h->len, max_batch)) ||
         (rc = h->dev_alloc(&h->done, max_batch)) || (rc = h->dev_alloc(&h->cur_tok, max_batch)) || (rc = h->dev_alloc(&h->out_len, max_batch)) ||
         (rc = h->dev_alloc(&h->sum_lp, max_batch))) return rc;
     MF_HIP(hipMemset(h->x, 0, rows * C * sizeof(float)));
@@ -549,67 +731,200 @@ extern "C" int mf_whisper_decoder_logits(void* handle, const int* tokens, int n,
     return MF_OK;
 }
 
-extern "C" int mf_whisper_decoder_greedy(void* handle, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new,
-                                         int check_every, int* out_tokens, int* out_lens, float* sum_logprobs, int batch, void* stream) {
-    mf_whisper_decoder* h = static_cast<mf_whisper_decoder*>(handle);
-    MF_REQUIRE(h && prompts && prompt_lens && out_tokens && out_lens && sum_logprobs, "whisper_decoder_greedy: null argument");
-    MF_REQUIRE(h->batch > 0, "whisper_decoder_greedy: call mf_whisper_decoder_begin first");
-    MF_REQUIRE(batch == h->batch, "whisper_decoder_greedy: batch %d, mf_whisper_decoder_begin was given %d", batch, h->batch);
-    MF_REQUIRE(check_every >= 1, "whisper_decoder_greedy: check_every = %d", check_every);
-    MF_REQUIRE(eot >= 0 && eot < h->n_vocab, "whisper_decoder_greedy: end-of-text token %d outside the vocabulary (%d)", eot, h->n_vocab);
+// the body of both decode calls.  rules == null: mf_whisper_decoder_greedy, launch for launch what it always was (k_dec_choose, `batch` head rows)
+int mf_whisper_decoder::decode(const char* who, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new, int check_every,
+                               const DecodeRules* rules, const int* sot_index, int* out_tokens, int* out_lens, float* sum_logprobs, float* no_speech_probs, int batch,
+                               hipStream_t s) {
+    MF_REQUIRE(prompts && prompt_lens && out_tokens && out_lens && sum_logprobs, "%s: null argument", who);
+    MF_REQUIRE(this->batch > 0, "%s: call mf_whisper_decoder_begin first", who);
+    MF_REQUIRE(batch == this->batch, "%s: batch %d, mf_whisper_decoder_begin was given %d", who, batch, this->batch);
+    MF_REQUIRE(check_every >= 1, "%s: check_every = %d", who, check_every);
+    MF_REQUIRE(eot >= 0 && eot < n_vocab, "%s: end-of-text token %d outside the vocabulary (%d)", who, eot, n_vocab);
+    const bool want_nsp = rules && rules->no_speech >= 0;
+    if (rules) {
+        const int rc = rules_check(who, *rules, eot, n_vocab);
+        if (rc) return rc;
+        MF_REQUIRE(!want_nsp || (sot_index && no_speech_probs), "%s: a no_speech token needs the sot index of every prompt and an output array", who);
+    }
     int total = 0, shortest = INT_MAX;
-    std::vector<int> tok, seq, pos, last(batch);
+    std::vector<int> tok, seq, pos, last(want_nsp ? 2 * batch : batch);
     for (int b = 0; b < batch; ++b) {
         const int n = prompt_lens[b];
-        MF_REQUIRE(n >= 1 && n <= h->n_ctx / 2, "whisper_decoder_greedy: prompt %d has %d tokens; a prompt holds 1..n_text_ctx / 2 = %d", b, n, h->n_ctx / 2);
+        MF_REQUIRE(n >= 1 && n <= n_ctx / 2, "%s: prompt %d has %d tokens; a prompt holds 1..n_text_ctx / 2 = %d", who, b, n, n_ctx / 2);
         for (int i = 0; i < n; ++i) {
             const int t = prompts[total + i];
-            MF_REQUIRE(t >= 0 && t < h->n_vocab, "whisper_decoder_greedy: prompt %d token %d = %d is outside the vocabulary (%d)", b, i, t, h->n_vocab);
+            MF_REQUIRE(t >= 0 && t < n_vocab, "%s: prompt %d token %d = %d is outside the vocabulary (%d)", who, b, i, t, n_vocab);
             tok.push_back(t); seq.push_back(b); pos.push_back(i);
+        }
+        if (want_nsp) {
+            MF_REQUIRE(sot_index[b] >= 0 && sot_index[b] < n, "%s: sot index %d of prompt %d lies outside its %d tokens", who, sot_index[b], b, n);
+            last[batch + b] = total + sot_index[b];
         }
         total += n;
         last[b] = total - 1;
         shortest = std::min(shortest, n);
     }
     // a sequence of p prompt tokens can emit n_text_ctx - p + 1 tokens before no cache row is left to feed the last one into
-    MF_REQUIRE(max_new >= 1 && max_new <= h->n_ctx - shortest + 1, "whisper_decoder_greedy: max_new = %d, the cache holds at most %d new tokens after the shortest prompt (%d)",
-               max_new, h->n_ctx - shortest + 1, shortest);
-    hipStream_t s = (hipStream_t)stream;
-    h->fed = -1;
+    MF_REQUIRE(max_new >= 1 && max_new <= n_ctx - shortest + 1, "%s: max_new = %d, the cache holds at most %d new tokens after the shortest prompt (%d)",
+               who, max_new, n_ctx - shortest + 1, shortest);
+    fed = -1;
     int rc;
-    MF_HIP(hipMemcpyAsync(h->row_tok, tok.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
-    MF_HIP(hipMemcpyAsync(h->row_seq, seq.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
-    MF_HIP(hipMemcpyAsync(h->row_pos, pos.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
-    MF_HIP(hipMemcpyAsync(h->last_row, last.data(), batch * sizeof(int), hipMemcpyHostToDevice, s));
-    MF_HIP(hipMemcpyAsync(h->len, prompt_lens, batch * sizeof(int), hipMemcpyHostToDevice, s));
-    MF_HIP(hipMemsetAsync(h->done, 0, batch * sizeof(int), s));
-    MF_HIP(hipMemsetAsync(h->out_len, 0, batch * sizeof(int), s));
-    MF_HIP(hipMemsetAsync(h->sum_lp, 0, batch * sizeof(float), s));
-    MF_HIP(hipMemsetAsync(h->out_tok, 0, (size_t)batch * h->n_ctx * sizeof(int), s));
+    MF_HIP(hipMemcpyAsync(row_tok, tok.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemcpyAsync(row_seq, seq.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemcpyAsync(row_pos, pos.data(), total * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemcpyAsync(last_row, last.data(), last.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemcpyAsync(len, prompt_lens, batch * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemsetAsync(done, 0, batch * sizeof(int), s));
+    MF_HIP(hipMemsetAsync(out_len, 0, batch * sizeof(int), s));
+    MF_HIP(hipMemsetAsync(sum_lp, 0, batch * sizeof(float), s));
+    MF_HIP(hipMemsetAsync(out_tok, 0, (size_t)batch * n_ctx * sizeof(int), s));
     MF_HIP(hipStreamSynchronize(s));   // the host vectors above are read by then
-    // prefill: every prompt token in one pass, the logits of each sequence's last one
-    const Rows pre{h->row_seq, h->row_pos, h->len, nullptr};
-    if ((rc = h->forward(total, h->row_tok, pre, s))) return rc;
-    const Rows step{nullptr, nullptr, h->len, h->done};
-    if ((rc = h->head(batch, h->last_row, h->logits, step, s))) return rc;
-    if ((rc = h->choose(suppress_mask, eot, max_new, 0, batch, s))) return rc;
-    std::vector<int> done(batch);
+    // prefill: every prompt token in one pass, the logits of each sequence's last one (and, for the no-speech probability, of its sot token)
+    const Rows pre{row_seq, row_pos, len, nullptr};
+    if ((rc = forward(total, row_tok, pre, s))) return rc;
+    const Rows step{nullptr, nullptr, len, done};
+    auto pick = [&](int advance) { return rules ? choose_rules(*rules, suppress_mask, eot, max_new, advance, batch, s) : choose(suppress_mask, eot, max_new, advance, batch, s); };
+    if (want_nsp) {
+        // 2 * batch head rows: a row's arithmetic does not depend on how many rows share its pass.  No done flag is set yet, and none is read here
+        if ((rc = head(2 * batch, last_row, logits, Rows{nullptr, nullptr, len, nullptr}, s))) return rc;
+        hipLaunchKernelGGL(k_dec_no_speech, dim3(batch), dim3(256), 0, s, logits + (size_t)batch * n_vocab, n_vocab, rules->no_speech, no_speech);
+        MF_HIP(hipGetLastError());
+    } else if ((rc = head(batch, last_row, logits, step, s))) return rc;
+    if ((rc = pick(0))) return rc;
+    std::vector<int> flags(batch);
     for (int steps = 0; steps < max_new - 1;) {
         for (int i = 0; i < check_every && steps < max_new - 1; ++i, ++steps) {
-            if ((rc = h->forward(batch, h->cur_tok, step, s))) return rc;
-            if ((rc = h->head(batch, nullptr, h->logits, step, s))) return rc;
-            if ((rc = h->choose(suppress_mask, eot, max_new, 1, batch, s))) return rc;
+            if ((rc = forward(batch, cur_tok, step, s))) return rc;
+            if ((rc = head(batch, nullptr, logits, step, s))) return rc;
+            if ((rc = pick(1))) return rc;
         }
-        MF_HIP(hipMemcpyAsync(done.data(), h->done, batch * sizeof(int), hipMemcpyDeviceToHost, s));
+        MF_HIP(hipMemcpyAsync(flags.data(), done, batch * sizeof(int), hipMemcpyDeviceToHost, s));
         MF_HIP(hipStreamSynchronize(s));
-        if (std::all_of(done.begin(), done.end(), [](int d) { return d != 0; })) break;
+        if (std::all_of(flags.begin(), flags.end(), [](int d) { return d != 0; })) break;
     }
-    std::vector<int> all((size_t)batch * h->n_ctx);
-    MF_HIP(hipMemcpyAsync(all.data(), h->out_tok, all.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    MF_HIP(hipMemcpyAsync(out_lens, h->out_len, batch * sizeof(int), hipMemcpyDeviceToHost, s));
-    MF_HIP(hipMemcpyAsync(sum_logprobs, h->sum_lp, batch * sizeof(float), hipMemcpyDeviceToHost, s));
+    std::vector<int> all((size_t)batch * n_ctx);
+    MF_HIP(hipMemcpyAsync(all.data(), out_tok, all.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    MF_HIP(hipMemcpyAsync(out_lens, out_len, batch * sizeof(int), hipMemcpyDeviceToHost, s));
+    MF_HIP(hipMemcpyAsync(sum_logprobs, sum_lp, batch * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (want_nsp) MF_HIP(hipMemcpyAsync(no_speech_probs, no_speech, batch * sizeof(float), hipMemcpyDeviceToHost, s));
     MF_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < batch; ++b) std::copy(all.begin() + (size_t)b * h->n_ctx, all.begin() + (size_t)b * h->n_ctx + max_new, out_tokens + (size_t)b * max_new);
+    for (int b = 0; b < batch; ++b) std::copy(all.begin() + (size_t)b * n_ctx, all.begin() + (size_t)b * n_ctx + max_new, out_tokens + (size_t)b * max_new);
+    return MF_OK;
+}
+
+extern "C" int mf_whisper_decoder_greedy(void* handle, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new,
+                                         int check_every, int* out_tokens, int* out_lens, float* sum_logprobs, int batch, void* stream) {
+    mf_whisper_decoder* h = static_cast<mf_whisper_decoder*>(handle);
+    MF_REQUIRE(h, "whisper_decoder_greedy: null argument");
+    return h->decode("whisper_decoder_greedy", prompts, prompt_lens, suppress_mask, eot, max_new, check_every, nullptr, nullptr, out_tokens, out_lens, sum_logprobs, nullptr,
+                     batch, (hipStream_t)stream);
+}
+
+extern "C" int mf_whisper_decoder_decode(void* handle, const int* prompts, const int* prompt_lens, const float* suppress_mask, int eot, int max_new, int check_every,
+                                         int timestamp_begin, int no_timestamps, int max_initial_timestamp_index, int blank, int no_speech, const int* sot_index,
+                                         int* out_tokens, int* out_lens, float* sum_logprobs, float* no_speech_probs, int batch, void* stream) {
+    mf_whisper_decoder* h = static_cast<mf_whisper_decoder*>(handle);
+    MF_REQUIRE(h, "whisper_decoder_decode: null argument");
+    const DecodeRules r{timestamp_begin, no_timestamps, max_initial_timestamp_index, blank, no_speech};
+    return h->decode("whisper_decoder_decode", prompts, prompt_lens, suppress_mask, eot, max_new, check_every, &r, sot_index, out_tokens, out_lens, sum_logprobs, no_speech_probs,
+                     batch, (hipStream_t)stream);
+}
+
+extern "C" int mf_whisper_decoder_detect_language(void* handle, int sot, const int* language_tokens, int n_languages, int* out_tokens, float* out_probs, int batch, void* stream) {
+    mf_whisper_decoder* h = static_cast<mf_whisper_decoder*>(handle);
+    MF_REQUIRE(h && language_tokens && out_tokens && out_probs, "whisper_decoder_detect_language: null argument");
+    MF_REQUIRE(h->batch > 0 && h->fed == 0, "whisper_decoder_detect_language: runs directly after mf_whisper_decoder_begin, before any token is fed");
+    MF_REQUIRE(batch == h->batch, "whisper_decoder_detect_language: batch %d, mf_whisper_decoder_begin was given %d", batch, h->batch);
+    MF_REQUIRE(sot >= 0 && sot < h->n_vocab, "whisper_decoder_detect_language: sot token %d outside the vocabulary (%d)", sot, h->n_vocab);
+    MF_REQUIRE(n_languages >= 1 && n_languages <= h->n_vocab, "whisper_decoder_detect_language: %d language tokens", n_languages);
+    std::vector<char> seen(h->n_vocab, 0);
+    for (int j = 0; j < n_languages; ++j) {
+        const int t = language_tokens[j];
+        MF_REQUIRE(t >= 0 && t < h->n_vocab, "whisper_decoder_detect_language: language token %d = %d is outside the vocabulary (%d)", j, t, h->n_vocab);
+        MF_REQUIRE(!seen[t], "whisper_decoder_detect_language: language token %d is listed twice", t);
+        seen[t] = 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (n_languages > h->lang_cap) {
+        // a longer list than any before: the old pair is given back first (no launch of an earlier call is in flight, each call ends in a read-back)
+        for (void* old : {(void*)h->lang_ids, (void*)h->lang_out})
+            if (old) {
+                h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), old), h->owned.end());
+                (void)hipFree(old);
+            }
+        h->lang_ids = nullptr; h->lang_out = nullptr; h->lang_cap = 0;
+        if ((rc = h->dev_alloc(&h->lang_ids, n_languages)) || (rc = h->dev_alloc(&h->lang_out, (size_t)h->max_batch * (n_languages + 1)))) return rc;
+        h->lang_cap = n_languages;
+    }
+    const std::vector<int> tok(batch, sot);
+    MF_HIP(hipMemcpyAsync(h->row_tok, tok.data(), batch * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipMemcpyAsync(h->lang_ids, language_tokens, n_languages * sizeof(int), hipMemcpyHostToDevice, s));
+    MF_HIP(hipStreamSynchronize(s));
+    // one token per sequence at position 0 (every length is 0 after begin and stays 0); cache row 0 is zeroed again below
+    const Rows rows{nullptr, nullptr, h->len, nullptr};
+    if ((rc = h->forward(batch, h->row_tok, rows, s))) return rc;
+    if ((rc = h->head(batch, nullptr, h->logits, rows, s))) return rc;
+    hipLaunchKernelGGL(k_dec_language, dim3(batch), dim3(256), 0, s, h->logits, h->n_vocab, h->lang_ids, n_languages, h->lang_out);
+    MF_HIP(hipGetLastError());
+    const size_t pitch = (size_t)h->n_ctx * h->C * sizeof(float);
+    for (auto& L : h->layers) {
+        MF_HIP(hipMemset2DAsync(L.kc, pitch, 0, h->C * sizeof(float), batch, s));
+        MF_HIP(hipMemset2DAsync(L.vc, pitch, 0, h->C * sizeof(float), batch, s));
+    }
+    std::vector<float> got((size_t)batch * (n_languages + 1));
+    MF_HIP(hipMemcpyAsync(got.data(), h->lang_out, got.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    MF_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < batch; ++b) {
+        const float* g = got.data() + (size_t)b * (n_languages + 1);
+        std::memcpy(out_tokens + b, g, sizeof(int));
+        std::copy(g + 1, g + 1 + n_languages, out_probs + (size_t)b * n_languages);
+    }
+    return MF_OK;
+}
+
+extern "C" int mf_whisper_decoder_choose(void* handle, const float* logits, const int* history, const float* suppress_mask, int eot, int timestamp_begin, int no_timestamps,
+                                         int max_initial_timestamp_index, int blank, int* tokens, float* logprobs, int* done, int batch, void* stream) {
+    mf_whisper_decoder* h = static_cast<mf_whisper_decoder*>(handle);
+    MF_REQUIRE(h && logits && history && tokens && logprobs && done, "whisper_decoder_choose: null argument");
+    MF_REQUIRE(batch >= 1 && batch <= h->max_batch, "whisper_decoder_choose: batch %d exceeds the handle's max_batch %d", batch, h->max_batch);
+    const DecodeRules r{timestamp_begin, no_timestamps, max_initial_timestamp_index, blank, -1};
+    int rc = rules_check("whisper_decoder_choose", r, eot, h->n_vocab);
+    if (rc) return rc;
+    for (int b = 0; b < batch; ++b) {
+        const int n = history[3 * b];
+        MF_REQUIRE(n >= 0, "whisper_decoder_choose: sequence %d has sampled %d tokens", b, n);
+        for (int i = 1; i <= std::min(n, 2); ++i)
+            MF_REQUIRE(history[3 * b + i] >= 0 && history[3 * b + i] < h->n_vocab, "whisper_decoder_choose: sequence %d history token %d is outside the vocabulary (%d)",
+                       b, history[3 * b + i], h->n_vocab);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // scratch of its own: [0, 3B) history, then length, done, chosen, sampled count, output slot (B each) and the log-probabilities.  The handle's decode state is not touched
+    int* d = nullptr;
+    MF_HIP(hipMalloc((void**)&d, (size_t)9 * batch * sizeof(int)));
+    std::vector<int> host((size_t)9 * batch, 0);
+    std::copy(history, history + 3 * batch, host.begin());
+    // the kernel adds to the sum: the sequences that run start from 0, a done one keeps the log-probability the caller gave
+    for (int b = 0; b < batch; ++b) {
+        host[4 * batch + b] = done[b] != 0;
+        host[5 * batch + b] = tokens[b];
+        const float lp0 = done[b] ? logprobs[b] : 0.f;
+        std::memcpy(host.data() + 8 * batch + b, &lp0, sizeof(float));
+    }
+    hipError_t e = hipMemcpyAsync(d, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) {
+        const ChooseArgs c{logits, h->n_vocab, suppress_mask, eot, INT_MAX, INT_MAX, 0, d + 3 * batch, d + 4 * batch, d + 5 * batch, d + 6 * batch,
+                           reinterpret_cast<float*>(d + 8 * batch), d + 7 * batch, 1};
+        hipLaunchKernelGGL(k_dec_choose_rules, dim3(batch), dim3(256), 0, s, rule_args(c, r, d));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d, host.size() * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d);
+    MF_HIP(e);
+    for (int b = 0; b < batch; ++b) { done[b] = host[4 * batch + b]; tokens[b] = host[5 * batch + b]; }
+    std::memcpy(logprobs, host.data() + 8 * batch, batch * sizeof(float));
     return MF_OK;
 }
 

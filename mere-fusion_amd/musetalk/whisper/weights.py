@@ -43,9 +43,11 @@ def decoder_state_dict(state_dict, with_ln_post=True):
     return keep
 
 
-def make_decoder_state_dict(seed=0, dims=WHISPER_TINY_TEXT, emb_scale=0.1):
+def make_decoder_state_dict(seed=0, dims=WHISPER_TINY_TEXT, emb_scale=0.1, timestamp_begin=None, timestamp_gain=1.0):
     """Seeded decoder weights under the checkpoint's key names.  The token embedding is kept small against what the blocks add to the residual
-    stream: with tied weights a large embedding makes every step choose the token it was just fed, and a greedy run would test nothing."""
+    stream: with tied weights a large embedding makes every step choose the token it was just fed, and a greedy run would test nothing.
+    timestamp_gain scales the embedding rows >= timestamp_begin after they are drawn (the draws themselves do not move): with random weights
+    either text or timestamps may win every step of a run under the timestamp rules, and the gain sets the balance between the two."""
     rng = np.random.default_rng(21000 + seed)
     V, T, C = dims["n_vocab"], dims["n_text_ctx"], dims["n_text_state"]
     sd = {}
@@ -53,6 +55,8 @@ def make_decoder_state_dict(seed=0, dims=WHISPER_TINY_TEXT, emb_scale=0.1):
         s = shape(V, T, C)
         if k.endswith("token_embedding.weight"):
             a = rng.standard_normal(s) * emb_scale
+            if timestamp_begin is not None:
+                a[int(timestamp_begin):] *= timestamp_gain
         elif k.endswith("positional_embedding"):
             a = rng.standard_normal(s) * 0.3
         elif "ln.weight" in k:
